@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark: registration iterations/sec (3-D 256^3 fp32, affine + NCC) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]            # N = 1
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   # N = 1
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up the batch, settles the clocks, warms up, times the K steps and prints one JSON line.  `--full` adds
+every secondary measurement of the line (config.value_cold, the other optimiser, the legs at other poses, the flow loop,
+the converging run, the roofline objects, cfg2 / lncc_loop and cpu_baseline).  `--dump-outputs DIR` writes what the timed
+solver holds after its last step (theta, best theta / loss / index, the loss curve, the last gradient) as DIR/<name>.npy;
+the inputs are seeded, so two builds run with the same arguments can be compared array for array.
 
 Workload (BASELINE.json configs[3], the configuration the metric is quoted on): every GPU owns
 8 independent (moving, target) pairs of 256^3 fp32 volumes (1 GiB resident in HBM), affine mode,
@@ -15,7 +21,7 @@ value = N * 8 * K / max-over-ranks(elapsed)  [pair-iterations / s].
 `--scaling strong [--pairs-total 64]` fixes the TOTAL number of pairs instead (64 pairs over G GPUs, 64 / G each - the
 shard of rank r is sharding.pair_range(r, G, 64)); value = pairs_total * K / max-over-ranks(elapsed), "scaling": "strong".
 
-Extra objects in the JSON line (rank 0, N = 1 only):
+Extra objects in the JSON line (--full, rank 0, N = 1 only):
   roofline     - dominant kernel (the fused F1 pass) timed in isolation with events on the launch
                  stream; achieved = 8 B/voxel * 256^3 * 8 pairs / avg kernel time; peak 8.0 TB/s.
   cpu_baseline - the oracle's torch-CPU composition of the reference's loop (kind "port": the
@@ -35,7 +41,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 PAIRS_PER_GPU = 8
 SIZE = 256
-HBM_PEAK = 8.0e12          # MI355X spec, /opt/skills/guides/MI355X_MICROARCH.md
+HBM_PEAK = 8.0e12          # MI355X spec sheet
 ALG_BYTES_PER_VOXEL = 8    # read moving (4) + target (4) once per pair-iteration
 THETA_STAR = [[0.95, -0.1, 0.02, 0.05], [0.1, 0.97, 0.0, -0.03], [0.0, 0.03, 1.02, 0.02]]
 
@@ -123,16 +129,23 @@ def _cpu_loop(budget_s, max_iters):
     return n, el
 
 
+def host_cpus():
+    """CPUs this process may use: OMP_NUM_THREADS where the host sets one (a share of a large shared machine, which
+    os.cpu_count() does not show), else the affinity mask."""
+    n = os.environ.get("OMP_NUM_THREADS", "")
+    return int(n) if n.isdigit() and int(n) > 0 else len(os.sched_getaffinity(0))
+
+
 def cpu_baseline(budget_s=10.0):
     """Two bounded samples on the host cores, the better one is reported: (a) one pair with all threads (ATen's sampler
     does not thread over a single volume, so this mostly measures the element-wise ops), (b) one pair per process,
     P processes x T threads side by side - the fair many-core number for a batch of independent pairs."""
     import subprocess
-    ncpu = os.cpu_count() or 1
+    ncpu = host_cpus()
     n1, el1 = _cpu_loop(budget_s, 64)
     single = n1 / el1
     threads1 = torch.get_num_threads()
-    procs = max(1, min(16, ncpu // 8))
+    procs = max(1, min(8, ncpu // 8))   # (at most 8 workers: each one loads the GPU runtime with torch)
     tper = max(1, ncpu // procs)
     cmd = [sys.executable, os.path.abspath(__file__), "--cpu-worker", str(tper)]
     ps = [subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True) for _ in range(procs)]
@@ -158,6 +171,18 @@ def cpu_worker(threads):
     print(n, el, flush=True)
 
 
+def dump_outputs(solver, out_dir, suffix=""):
+    """--dump-outputs: what a caller of the timed solver receives after its last step, one .npy per array (a few KB in all):
+    theta [B,3,4], best_theta [B,3,4], best_loss [B], best_idx [B] (float64), losses [B, warm-up + timed steps], grad [B,12]
+    (the last step's gradient of the loss with respect to theta)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"theta": solver.current_theta, "best_theta": solver.best, "best_loss": solver.best_loss, "best_idx": solver.best_idx.double(),
+              "losses": solver.losses[:, :solver.enqueued], "grad": solver.grad[:, :12]}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), t.detach().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -167,9 +192,14 @@ def main():
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
                     help="weak: 8 pairs per GPU at every N (default, what the driver runs); strong: --pairs-total pairs split over the N GPUs")
     ap.add_argument("--pairs-total", type=int, default=64, help="strong scaling: the total number of pairs (BASELINE configs[3]: 64)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement (value_cold, the other optimiser, the pose / flow / converging-run legs, "
+                         "the roofline objects, cfg2 / lncc_loop, cpu_baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed solver holds after its last step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
     ap.add_argument("--no-pose-legs", action="store_true",
-                    help="skip the config.value_* / flow_value legs (profiling runs: every launch of the step kernel is then a headline-pose launch)")
+                    help="--full without the config.value_* / flow_value legs (profiling runs: every launch of the step kernel is then a headline-pose launch)")
     ap.add_argument("--optimizer", default="adam", choices=["adam", "sgd"],
                     help="optimiser on theta for the headline number (north_star: Adam; the reference's own loop: SGD)")
     ap.add_argument("--cpu-worker", type=int, default=0, help=argparse.SUPPRESS)
@@ -229,16 +259,19 @@ def main():
         torch.cuda.synchronize()
 
     # value_cold: what a registration that starts on an idle GPU gets - no preconditioning, no warm-up, the first `steps`
-    # iterations after 2 s of idleness (boost clocks for ~10 launches, then the power-cap transient, then the settled clock)
+    # iterations after 2 s of idleness (boost clocks for ~10 launches, then the power-cap transient, then the settled clock).
+    # A plain run makes the same iterations without the idle gap and reports nothing of them: they are part of the clock settling
+    # in front of the headline (without them the headline measured 0.3-0.6 % lower, alternating runs on one box).
     cold = new_solver(args.optimizer)
-    fence()
-    time.sleep(2.0)
+    if args.full:
+        fence()
+        time.sleep(2.0)
     fence()
     t0 = time.perf_counter()
     cold.run(args.steps)
     fence()
-    elapsed_cold = max_over_ranks_local = time.perf_counter() - t0
-    del cold, max_over_ranks_local
+    elapsed_cold = time.perf_counter() - t0
+    del cold
 
     scratch = new_solver(args.optimizer)
     scratch.run(PRECONDITION)
@@ -254,24 +287,27 @@ def main():
     elapsed = time.perf_counter() - t0
     from torchregister_amd.sharding import max_over_ranks
     elapsed = max_over_ranks(elapsed, device)
-    elapsed_cold = max_over_ranks(elapsed_cold, device)
     losses = solver.losses[:, : args.steps + args.warmup]
     assert torch.isfinite(losses).all(), "non-finite loss in the benchmark run"
     assert (losses[:, -1] < losses[:, 0]).all(), "the optimiser made no progress"
+    if args.dump_outputs:
+        dump_outputs(solver, args.dump_outputs, f"_rank{rank}" if world > 1 else "")
 
     # the other optimiser on the same workload (only theta's 12-float update differs), timed the same way: same
     # preconditioning, same warm-up (round 1 timed it inside the post-idle power transient: -20 %)
     other = "sgd" if args.optimizer == "adam" else "adam"
-    scratch = new_solver(other)
-    scratch.run(PRECONDITION)
-    del scratch
-    solver2 = new_solver(other)
-    solver2.run(args.warmup)
-    fence()
-    t0 = time.perf_counter()
-    solver2.run(args.steps)
-    fence()
-    elapsed2 = max_over_ranks(time.perf_counter() - t0, device)
+    if args.full:
+        elapsed_cold = max_over_ranks(elapsed_cold, device)
+        scratch = new_solver(other)
+        scratch.run(PRECONDITION)
+        del scratch
+        solver2 = new_solver(other)
+        solver2.run(args.warmup)
+        fence()
+        t0 = time.perf_counter()
+        solver2.run(args.steps)
+        fence()
+        elapsed2 = max_over_ranks(time.perf_counter() - t0, device)
 
     # ---- poses away from the identity (rank-local, same 8 x 256^3 batch): the headline starts at theta = I, where
     # every affine run starts; a run that converges to theta* ends 0.05-0.1 away from it and a rigid run starts at a random pose.
@@ -284,20 +320,21 @@ def main():
         return time.perf_counter() - t
 
     pose_steps = min(args.steps, 100)
+    legs = args.full and not args.no_pose_legs
     extra = {"value_theta_star": None, "value_rot": None, "value_rigid_randinit": None, "flow_value": None, "value_run": None, "run_loss_ratio_worst": None,
              "run_loss_first_last": None, "run_theta_err_worst": None, "body_histogram": None, "value_theta_star_inv": None}
     # (a) theta* (the map the synthetic moving volumes were made with) and its inverse - the pose a run of this batch CONVERGES to;
     # (b) R(0.5, 0.4, 0.3) x anisotropic scale; (c) the rigid mode from the
     # reference's own initial pose: torch.manual_seed(0); torch.rand(6) radians / tanh-translations (ref:utils.py:316-321)
-    th_star = torch.tensor(THETA_STAR, device=device)[None].expand(my_pairs, 3, 4).contiguous()
-    th_star_inv = theta_star_inv().to(device)[None].expand(my_pairs, 3, 4).contiguous()
-    th_rot = pose_rot(device, my_pairs)
-    for key, th0 in (() if args.no_pose_legs else (("value_theta_star", th_star), ("value_theta_star_inv", th_star_inv), ("value_rot", th_rot))):
-        sv = tr.AffineSolver(mov, tgt, mode="affine", loss=tr.LossSpec(w_ncc=1.0), optimizer=args.optimizer, lr=1e-6, init=th0,
-                             capacity=pose_steps + 40)
-        extra[key] = job_pairs * pose_steps / max_over_ranks(timed_run(sv, pose_steps), device)
-        del sv
-    if not args.no_pose_legs:
+    if legs:
+        th_star = torch.tensor(THETA_STAR, device=device)[None].expand(my_pairs, 3, 4).contiguous()
+        th_star_inv = theta_star_inv().to(device)[None].expand(my_pairs, 3, 4).contiguous()
+        th_rot = pose_rot(device, my_pairs)
+        for key, th0 in (("value_theta_star", th_star), ("value_theta_star_inv", th_star_inv), ("value_rot", th_rot)):
+            sv = tr.AffineSolver(mov, tgt, mode="affine", loss=tr.LossSpec(w_ncc=1.0), optimizer=args.optimizer, lr=1e-6, init=th0,
+                                 capacity=pose_steps + 40)
+            extra[key] = job_pairs * pose_steps / max_over_ranks(timed_run(sv, pose_steps), device)
+            del sv
         sv = tr.AffineSolver(mov, tgt, mode="rigid", loss=tr.LossSpec(w_ncc=1.0), optimizer=args.optimizer, lr=1e-6,
                              init=pose_rigid_randinit(device, my_pairs), capacity=pose_steps + 40)
         extra["value_rigid_randinit"] = job_pairs * pose_steps / max_over_ranks(timed_run(sv, pose_steps), device)
@@ -317,7 +354,7 @@ def main():
     # lr 1e-4 stay next to the identity; this run crosses to theta* (|theta* - I| = 0.1) in its first ~60 iterations and spends the rest there.
     # body_histogram: pair-iterations per kernel body, sampled from a replica run every RUN_CHUNK iterations (AffineSolver.bodies()).
     RUN_ITERS, RUN_LR, RUN_CHUNK = 300, 2e-3, 10
-    if not args.no_pose_legs:
+    if legs:
         sv = tr.AffineSolver(mov, tgt, mode="affine", loss=tr.LossSpec(w_ncc=1.0), optimizer="adam", lr=RUN_LR, capacity=RUN_ITERS)
         fence()
         t0 = time.perf_counter()
@@ -352,6 +389,9 @@ def main():
                                        f"(BASELINE.json configs[3], strong scaling), {args.optimizer.upper()} on theta"),
                           "pairs_per_gpu": my_pairs if args.scaling == "strong" else PAIRS_PER_GPU, "pairs_total": job_pairs, "volume": [args.size] * 3, "loss": "NCC(alpha=100)", "optimizer": args.optimizer,
                           "preconditioning": f"{PRECONDITION} untimed iterations before the warm-up (clock settling); value_cold has none",
+                          "parallelism": f"{world} x independent shards, no collective"}}
+        if args.full:
+            out["config"].update({
                           "value_cold": job_pairs * args.steps / elapsed_cold,
                           "value_cold_note": f"first {args.steps} iterations of a fresh solver after 2 s of idle GPU, no warm-up",
                           f"{other}_value": job_pairs * args.steps / elapsed2,
@@ -370,9 +410,8 @@ def main():
                                       f"{RUN_CHUNK} iterations)",
                           "flow_value": extra["flow_value"],
                           "flow_note": "iterations/s of BASELINE configs[2]: one 256^3 pair, direct flow field + NCC + smoothness regulariser, "
-                                       "Adam (extension; parity vs torch autograd, not the reference), 100 iterations in one trx_flow_run call",
-                          "parallelism": f"{world} x independent shards, no collective"}}
-        if world == 1:
+                                       "Adam (extension; parity vs torch autograd, not the reference), 100 iterations in one trx_flow_run call"})
+        if world == 1 and args.full:
             # ---- roofline leg: the fused F1 kernel alone, events on the launch stream, AT THE POSES OF THE TIMED REGION: a replica of
             # the measured solver (same start, same optimiser, same warm-up) is stepped one iteration at a time and, before each of its K
             # timed iterations, the F1 launch of that iteration's theta is timed on its own (the kernel picks its body per pair from theta:

@@ -52,7 +52,7 @@ def start_arbiter():
     the rest of the GPU suite instead of in front of this module (round 6: the suite had grown to 800-1000 s of a 1200 s limit)."""
     if not _POOL:
         ctx = multiprocessing.get_context("spawn")
-        ex = concurrent.futures.ProcessPoolExecutor(max_workers=len(JOBS), mp_context=ctx)
+        ex = concurrent.futures.ProcessPoolExecutor(max_workers=min(len(JOBS), tw.WORKERS), mp_context=ctx)
         _POOL["ex"] = ex
         _POOL["futs"] = {k: ex.submit(tw.run, j) for k, j in JOBS.items()}
     return _POOL

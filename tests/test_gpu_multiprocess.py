@@ -117,7 +117,7 @@ def test_bench_two_ranks_control_flow():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(29700 + os.getpid() % 200), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-           "--size", "64", "--backend", "gloo", "--single-device", "--no-cpu-baseline"]
+           "--size", "64", "--backend", "gloo", "--single-device", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -137,7 +137,7 @@ def test_bench_strong_scaling_two_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(29900 + os.getpid() % 90), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-           "--size", "64", "--backend", "gloo", "--single-device", "--no-cpu-baseline", "--scaling", "strong", "--pairs-total", "5"]
+           "--size", "64", "--backend", "gloo", "--single-device", "--full", "--no-cpu-baseline", "--scaling", "strong", "--pairs-total", "5"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -158,10 +158,41 @@ def test_bench_under_torchrun_nccl_single_rank():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(29400 + os.getpid() % 150), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
-           "--size", "64", "--no-cpu-baseline"]
+           "--size", "64", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout
     j = json.loads(lines[0])
     assert j["n_gpus"] == 1 and j["steps"] == 6 and j["value"] > 0 and "roofline" in j
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain bench.py run (no --full) times the headline alone: the line holds the headline keys and none of --full's legs.  With
+    --dump-outputs it writes the timed solver's arrays after its last step, and two runs with the same arguments write the same arrays
+    (seeded inputs; small tolerance: at this size the kernel form of a step may differ between runs)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--size", "64", "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        j = json.loads(lines[0])
+        assert j["n_gpus"] == 1 and j["steps"] == 6 and j["warmup"] == 2 and j["higher_is_better"] is True
+        assert j["unit"] == "pair-iterations/s" and j["dtype"] == "f32" and j["metric"].startswith("registration iterations/sec")
+        assert abs(j["value"] - 8 * 6 / (j["ms_per_step"] * 6e-3)) < 1e-6 * j["value"]
+        assert "roofline" not in j and "cpu_baseline" not in j and "value_cold" not in j["config"] and "value_run" not in j["config"]
+        runs.append({p.stem: np.load(p) for p in d.glob("*.npy")})
+    a, b = runs
+    assert set(a) == set(b) == {"theta", "best_theta", "best_loss", "best_idx", "losses", "grad"}
+    assert a["theta"].shape == (8, 3, 4) and a["losses"].shape == (8, 2 + 6) and a["grad"].shape == (8, 12)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values()) and np.isfinite(a["losses"]).all()
+    for name in a:
+        np.testing.assert_allclose(a[name], b[name], rtol=1e-5, atol=1e-5 * float(np.max(np.abs(b[name]))), err_msg=name)

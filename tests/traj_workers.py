@@ -7,6 +7,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path[:0] = [os.path.dirname(HERE), HERE]
 
+# Worker processes at a time.  Each one loads the GPU runtime with torch; beside pytest itself and a two-rank torchrun test of the rest of
+# the GPU suite (launcher + 2 ranks) that keeps the suite at 12 such processes at most.
+WORKERS = 8
+
 
 def theta0_np(eps=2.5e-3, seed=0):
     import numpy as np
@@ -38,8 +42,9 @@ def pair(shape, seed):
 def run(job):
     """job = (kind, shape, seed, dtype name, optimizer, lr, iters, extra) -> dict of numpy arrays"""
     import torch
+    from bench import host_cpus
     from oracle import compose
-    torch.set_num_threads(8)   # (16 jobs side by side under the rest of the GPU suite: leave the host cores that suite's own oracle calls need)
+    torch.set_num_threads(max(1, host_cpus() // WORKERS))   # (WORKERS jobs side by side under the rest of the GPU suite share the host's CPUs)
     kind, shape, seed, dtn, optimizer, lr, iters, extra = job
     dt = getattr(torch, dtn)
     mov, tgt = pair(shape, seed)

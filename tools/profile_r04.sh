@@ -15,8 +15,8 @@ bash tools/pmc_flow.sh final adam 1.0 30 > /dev/null 2>&1
 python3 tools/pmc_zsummary.py flow_ gpurun_out 2>/dev/null | grep zpmc_flow_final > $O/flow_pmc.txt
 python3 tools/summarize_traffic.py $1 > $O/traffic_summary.log 2>&1
 cp profiles/traffic.json profiles/traffic_rot.json profiles/traffic_flow.json $O/ 2>/dev/null; cp profiles/$1_bench_rocprof_summary.csv $O/
-python3 bench.py > $O/bench.json 2> $O/bench.err
-python3 bench.py --no-cpu-baseline --steps 20 > $O/bench_steps20.json 2>/dev/null
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
+python3 bench.py --full --no-cpu-baseline --steps 20 > $O/bench_steps20.json 2>/dev/null
 python3 tools/bench_rotation.py 0 2>&1 | grep -v amdgpu > $O/rotation_sweep.txt
 python3 tools/bench_configs.py 2>&1 | grep -v amdgpu > $O/configs.txt
 python3 tools/bench_lncc_loop.py 2>&1 | grep -v amdgpu > $O/lncc_loop.txt

@@ -11,7 +11,7 @@ import sys
 src, tag = sys.argv[1], sys.argv[2]
 note = sys.argv[3] if len(sys.argv) > 3 else ""
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-out = [f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --no-pose-legs  (MI355X; {note})",
+out = [f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-pose-legs  (MI355X; {note})",
        "Name,Calls,TotalDurationNs,AverageNs,Percentage,MinNs,MaxNs"]
 rows = list(csv.DictReader(open(sorted(glob.glob(f"{src}/stats/*/*_kernel_stats.csv"), key=os.path.getmtime)[-1])))
 for r in rows:
