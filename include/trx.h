@@ -39,7 +39,9 @@ extern "C" {
  *        front of it on every launch: the workspace still needs no initialisation by the caller).  No entry point changed its signature.
  *   240  round 6: TRX_FLAG_ONE_KERNEL (a step of a chip-filling launch next to the identity is ONE streaming launch + the finalise), trx_affine_near_identity;
  *        trx_affine_run folds the finalise of an iteration into the next iteration's kernel for launch-bound 3-D steps (TRX_FLAG_NO_CARRY keeps two launches);
- *        trx_affine_workspace_bytes grows by a second partial / note buffer and two carry buffers (3-D).  No entry point changed its signature. */
+ *        trx_affine_workspace_bytes grows by a second partial / note buffer and two carry buffers (3-D).  No entry point changed its signature.
+ *        Later addition under the same number: trx_resample / trx_resample_workspace_bytes (the levels of a coarse-to-fine pyramid and the flow
+ *        hand-over between them) - new entry points only, no existing signature or struct changed. */
 #define TRX_VERSION 240
 #define TRX_PSTRIDE 12  /* floats per pair in theta / param / adam / best_theta arrays */
 
@@ -383,6 +385,20 @@ int trx_nmi_lattice_lines(const trx_volumes *vol, const float *theta, const int 
  * (rigid, as trx_theta_chain); param_copy[TRX_PSTRIDE] (nullable) = the new theta. */
 int trx_nmi_loop_update(int ndim, float *theta, float *pose, const float *grad_a, const float *grad_b, float lr, const float *loss_terms,
                         int n_terms, const float *loss_b, float *hist_loss_t, float *hist_theta_t, float *param_copy, void *stream);
+
+/* ---- Resampling between grid sizes (the levels of a coarse-to-fine pyramid; extension, the reference registers at one resolution).
+ * in: N volumes [D][H][W], out: N volumes [Do][Ho][Wo], both contiguous fp32 (2-D: ndim 2, D = Do = 1).  Each axis on its own:
+ *   shrinks (So < S): separable 5-tap binomial blur [1,4,6,4,1]/16 along that axis on the input grid (replicate boundary), then linear
+ *                     interpolation at the output positions;
+ *   same size: identity (no blur);  grows (So > S): linear interpolation only.
+ * Output positions are F.interpolate(size=..., mode='bilinear' | 'trilinear', align_corners=...)'s: align_corners 0:
+ * u = max((j + 0.5) S / So - 0.5, 0), 1: u = j (S - 1) / (So - 1).  channel_scale [host] (nullable): volume n is multiplied by
+ * channel_scale[n % channels] (channels <= 64; a flow field's per-axis unit change when it moves to a finer grid).
+ * Deterministic (no atomics).  Workspace: trx_resample_workspace_bytes (0 = arguments rejected) - intermediates of the separable passes,
+ * a chunk of volumes at a time. */
+size_t trx_resample_workspace_bytes(int ndim, int N, int D, int H, int W, int Do, int Ho, int Wo);
+int trx_resample(const float *in, float *out, int ndim, int N, int D, int H, int W, int Do, int Ho, int Wo, int align_corners, int channels,
+                 const float *channel_scale /*[host]*/, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

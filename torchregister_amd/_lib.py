@@ -126,6 +126,8 @@ SIGNATURES = {
                                          ctypes.POINTER(FlowState), ctypes.c_int, _P, ctypes.c_size_t, _P]),
     "trx_lncc_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "trx_lncc_loss_grad": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_float, _P, _P, _P, ctypes.c_size_t, _P]),
+    "trx_resample_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 8),
+    "trx_resample": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 10 + [_P, _P, ctypes.c_size_t, _P]),
 }
 
 _lib = None

@@ -3,18 +3,28 @@
 Same constructor, `optim` and `__call__` signatures and the same criterion/weight branching
 (ref:torchregister.py:70-106).  Extensions are keyword-only and default to reference behaviour:
 optimizer ('sgd'|'adam'), honor_criterion, init, smooth_weight, flow_model ('unet' = the reference's
-U-Net-generated flow, 'direct' = the flow field itself is the parameter); after `optim`, `.losses`
-(the loss curve the reference only plots), `.final_theta` and `.best_idx` are available.
+U-Net-generated flow, 'direct' = the flow field itself is the parameter), levels (coarse-to-fine); after `optim`,
+`.losses` (the loss curve the reference only plots), `.final_theta` and `.best_idx` are available.
 """
 import torch
 from torch import cat
 
+from .pyramid import pyramid, pyramid_shapes, upsample_flow
 from .warpings import affine_register, flow_register, get_affine_warp, rigid_register
+
+
+def _per_level(value, levels, name):
+    """One value for every level, or a sequence of `levels` values (coarse to fine)."""
+    if isinstance(value, (list, tuple)):
+        if len(value) != levels:
+            raise ValueError(f"{name}: {len(value)} values for {levels} levels")
+        return list(value)
+    return [value] * levels
 
 
 class Register():
     def __init__(self, mode='rigid', device='cpu', criterion=None, weight=None, grad_edges=False, debug=False, *,
-                 optimizer='sgd', honor_criterion=False, init=None, smooth_weight=0.0, flow_model='unet'):
+                 optimizer='sgd', honor_criterion=False, init=None, smooth_weight=0.0, flow_model='unet', levels=1):
         '''
         Numerical registration on an AMD GPU (MI355X) behind the TorchRegister API.
 
@@ -28,10 +38,17 @@ class Register():
             reproduced unless honor_criterion=True.
         weight : list of floats associated with criterion.
         grad_edges : must stay False (the reference's edge filter crashes when enabled).
-        debug : print a one-line summary after optim.
+        debug : print a one-line summary after optim (one per level with levels > 1).
+        levels : (keyword-only extension) coarse-to-fine registration over a pyramid of this many levels (pyramid_shapes: each level
+            halves every axis that stays >= 8 voxels).  Rigid / affine hand the final parameters of a level to the next unchanged (theta is
+            in normalised coordinates); flow_model='direct' hands its final flow up through upsample_flow.  1 = single resolution.
         '''
         if mode not in ('rigid', 'affine', 'flow'):
             raise ValueError("mode must be 'rigid', 'affine' or 'flow'")
+        if not isinstance(levels, int) or isinstance(levels, bool) or levels < 1:
+            raise ValueError(f"levels must be an int >= 1, got {levels!r}")
+        if levels > 1 and mode == 'flow' and flow_model == 'unet':
+            raise ValueError("levels > 1 needs flow_model='direct': the U-Net is built for one image size")
         self.criterion = criterion
         self.weight = weight
         self.mode = mode
@@ -45,16 +62,22 @@ class Register():
         self.init = init
         self.smooth_weight = smooth_weight
         self.flow_model = flow_model
+        self.levels = levels
         self.losses = None
         self.final_theta = None
         self.best_idx = None
+        self.level_losses = None
+        self.level_shapes = None
 
     def optim(self, moving, target, lr=1E-5, max_epochs=1000, n=32, per=0.1):
         '''
         Optimisation loop: moving, target [1,1,x,y(,z)] float32 GPU tensors (a leading batch > 1 of
         independent pairs is an extension).  Sets self.theta (best theta [B,nd,nd+1], or the flow
         [B,nd,...] of the last forward in flow mode) and self.warp.  Returns None.
+        With levels > 1, lr and max_epochs may each be one value for every level or a sequence of `levels` values, coarse to fine.
         '''
+        if self.levels > 1:
+            return self._optim_levels(moving, target, lr, max_epochs, n, per)
         if self.mode == 'flow':
             kw = dict(mode='bilinear', n=n, lr=lr, max_epochs=max_epochs, optimizer=self.optimizer, smooth_weight=self.smooth_weight,
                       flow_model=self.flow_model)
@@ -83,6 +106,54 @@ class Register():
         self.final_theta = theta[0]
         self.losses = info.get('losses')
         self.best_idx = info.get('best_idx')
+
+    def _optim_levels(self, moving, target, lr, max_epochs, n, per):
+        '''Coarse-to-fine: the single-level machinery (flow_register / _affine_family) on each level of pyramid(moving) and
+        pyramid(target), coarsest first; each level starts from the previous level's FINAL parameters (rigid: the pose, drawn by
+        torch.rand for the coarsest level as a single-level run draws it; affine: theta; flow: upsample_flow of the flow).  Optimiser
+        state starts fresh at every level.  .theta / .warp / .losses / .best_idx / .final_theta are the finest level's.'''
+        L = self.levels
+        lrs, epochs = _per_level(lr, L, 'lr'), _per_level(max_epochs, L, 'max_epochs')
+        shapes = pyramid_shapes(target.shape[2:], L)
+        if tuple(moving.shape[2:]) != tuple(target.shape[2:]):
+            raise ValueError(f"moving {tuple(moving.shape)} and target {tuple(target.shape)} differ in spatial size")
+        flow = self.mode == 'flow'
+        movs, tgts = pyramid(moving, L, align_corners=flow), pyramid(target, L, align_corners=flow)
+        init = None if flow else self.init
+        self.level_losses, self.level_shapes = [], shapes
+        for k in range(L):
+            if flow:
+                kw = dict(mode='bilinear', n=n, lr=lrs[k], max_epochs=epochs[k], optimizer=self.optimizer, smooth_weight=self.smooth_weight,
+                          flow_model=self.flow_model)
+                if self.criterion is not None and self.weight is not None:
+                    kw.update(criterions=self.criterion, weights=self.weight)
+                elif self.weight is not None:
+                    kw.update(weights=self.weight)
+                reg = flow_register(shapes[k], **kw).to(moving.device)
+                reg.init_flow = None if init is None else upsample_flow(init, shapes[k])
+                reg.optimize(movs[k], tgts[k], self.device, False)
+                init = reg.final_flow
+                self.theta, self.warp, self.final_theta = reg.flow, reg.deform, reg.final_flow
+                self.losses = reg.losses
+            else:
+                fn = affine_register if self.mode == 'affine' else rigid_register
+                info = {}
+                kw = dict(lr=lrs[k], epochs=epochs[k], per=per, device=self.device, debug=False, grad_edges=self.grad_edges,
+                          honor_criterion=self.honor_criterion, optimizer=self.optimizer, init=init, info=info)
+                if self.criterion is not None and self.weight is not None:
+                    kw.update(criterions=self.criterion, weights=self.weight)
+                elif self.weight is not None:
+                    kw.update(weights=self.weight)
+                _, theta = fn(movs[k], tgts[k], **kw)
+                init = info['final_pose'] if self.mode == 'rigid' else theta[0]
+                self.theta, self.final_theta = theta[-1], theta[0]
+                self.losses, self.best_idx = info.get('losses'), info.get('best_idx')
+            self.level_losses.append(self.losses)
+            if self.debug:
+                ls = self.losses.detach().flatten().cpu()
+                ls = ls[~torch.isnan(ls)]
+                print(f"[{self.mode}] level {k + 1}/{L} {tuple(shapes[k])}: {epochs[k]} iterations, lr {lrs[k]:g}, " +
+                      (f"loss {ls[0].item():.6g} -> {ls[-1].item():.6g} (min {ls.min().item():.6g})" if len(ls) else "no iterations"))
 
     def __call__(self, moving):
         '''

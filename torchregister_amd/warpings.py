@@ -177,6 +177,8 @@ def _generic_loop(moving, target, mode, criterions, weights, lr, epochs, init, o
     final_theta = make().detach().clone()
     final_warped = get_affine_warp(final_theta, moving)
     res = dict(losses=torch.tensor(losses), final_theta=final_theta, best_theta=best[1], best_idx=int(torch.tensor(losses).argmin()))
+    if mode == "rigid":
+        res["final_pose"] = p.detach().reshape(1, -1).clone()
     return [final_warped, best[2]], [final_theta, best[1]], res
 
 
@@ -270,6 +272,8 @@ def _nmi_affine_loop(moving, target, mode, spec, nmi, w_nmi, lr, epochs, init):
         best_idx = int(torch.argmin(hist_loss[:epochs]))     # first minimum = first strict improvement (Q8); the loop's only other sync
         best_theta = unpad(hist_theta[best_idx])
     res = dict(losses=hist_loss[:epochs].clone(), final_theta=final_theta, best_theta=best_theta, best_idx=best_idx)
+    if rigid:
+        res["final_pose"] = pose[:, :npose].clone()
     return [get_affine_warp(final_theta, moving), get_affine_warp(best_theta, moving)], [final_theta, best_theta], res
 
 
@@ -280,6 +284,7 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
                                   "crashes for every realistic volume (SURVEY Q6); it is not part of the HIP path.")
     criterions, weights = _resolve_criterions(criterions, weights, honor_criterion, device)
     nd = moving.dim() - 2
+    npose = 6 if nd == 3 else 3
     if mode == "rigid" and init is None:
         init = torch.rand((6 if nd == 3 else 3), device=moving.device)      # ref:utils.py:316-321 (Q9)
     spec = loss_spec_from(criterions, weights)
@@ -291,7 +296,7 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
         warped, theta, res = out if out is not None else _generic_loop(moving, target, mode, criterions, weights, lr, epochs, init, optimizer)
     else:
         B = moving.shape[0]
-        init_b = None if init is None else (init.reshape(1, -1).expand(B, -1) if mode == "rigid" else init.reshape(-1, nd, nd + 1).expand(B, nd, nd + 1))
+        init_b = None if init is None else (init.reshape(-1, npose).expand(B, -1) if mode == "rigid" else init.reshape(-1, nd, nd + 1).expand(B, nd, nd + 1))
         solver = AffineSolver(moving, target, mode=mode, loss=spec, optimizer=optimizer, lr=lr, init=init_b, capacity=max(1, epochs))
         solver.run(epochs)
         final_theta, best_theta = solver.current_theta, solver.best
@@ -300,6 +305,8 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
         warped = [get_affine_warp(final_theta, moving), get_affine_warp(best_theta, moving)]
         theta = [final_theta, best_theta]
         res = dict(losses=solver.losses[:, :epochs], final_theta=final_theta, best_theta=best_theta, best_idx=solver.best_idx, solver=solver)
+        if mode == "rigid":
+            res["final_pose"] = solver.param[:, :npose].clone()
     if info is not None:
         info.update(res)
     if debug:
@@ -390,6 +397,7 @@ class flow_register(nn.Module):
         self.flow = None
         self.final_flow = None
         self.losses = None
+        self.init_flow = None      # flow_model='direct': the flow the optimisation starts from (None = zero; set by Register's coarse-to-fine loop)
 
     def forward(self, x, device=None):
         if self.model is not None:
@@ -423,7 +431,7 @@ class flow_register(nn.Module):
         # pair: a batch is B independent registrations), a pair that has converged ignores the remaining iterations, and the flow
         # of its last forward is kept beside the final one - exactly the state the reference leaves behind, with one host sync.
         solver = FlowSolver(moving, target, loss=spec, optimizer=self.optimizer_kind, lr=self.lr, capacity=max(1, self.max_epochs),
-                            smooth_weight=self.smooth_weight, stop_crit=self.stop_crit, keep_last=True, lncc=lncc)
+                            smooth_weight=self.smooth_weight, stop_crit=self.stop_crit, keep_last=True, lncc=lncc, init=self.init_flow)
         solver.run(self.max_epochs)
         done = solver.step.cpu()                       # iterations executed per pair (the only host sync)
         n = int(done.max()) if self.max_epochs > 0 else 0
@@ -464,7 +472,10 @@ class flow_register(nn.Module):
 
     def _optimize_generic(self, moving, target, debug):
         nd = moving.dim() - 2
-        fl = torch.zeros(moving.shape[0], nd, *moving.shape[2:], device=moving.device, requires_grad=True)
+        if self.init_flow is None:
+            fl = torch.zeros(moving.shape[0], nd, *moving.shape[2:], device=moving.device, requires_grad=True)
+        else:
+            fl = self.init_flow.detach().to(moving.device).reshape(moving.shape[0], nd, *moving.shape[2:]).clone().requires_grad_()
         opt = torch.optim.SGD([fl], self.lr) if self.optimizer_kind == "sgd" else torch.optim.Adam([fl], self.lr)
         losses, message = [], "Reached max epochs"
         for _ in range(self.max_epochs):
