@@ -43,3 +43,26 @@ def upsample_flow_ref(flow, size):
     sp = tuple(flow.shape[2:])
     scale = [1.0 if (S == s or s == 1) else (S - 1) / (s - 1) for S, s in zip(size, sp)]
     return resample_ref(flow, size, align_corners=True, channel_scale=scale)
+
+
+RESAMPLE_CHUNK_BYTES = 96 << 20   # csrc/pyramid.hip: intermediates of one chunk of volumes
+
+
+def resample_plan_ref(N, sp, size):
+    """The workspace plan of trx_resample, restated on the host: (chunk, t1, t2, t2_offset, ws_bytes).  Axes whose size changes run
+    strongest shrink first (smallest So / S; ties: the inner axis first); t1 / t2 are the floats per volume after pass 1 / pass 2 where
+    another pass follows; a chunk's intermediates fit RESAMPLE_CHUNK_BYTES; t2 starts on a 64-float boundary; at least 256 bytes."""
+    S = (1,) * (3 - len(sp)) + tuple(sp)
+    So = (1,) * (3 - len(size)) + tuple(size)
+    axes = [a for a in (2, 1, 0) if S[a] != So[a]]
+    axes.sort(key=lambda a: So[a] / S[a])             # stable: equal ratios keep the inner axis first
+    cur, after = list(S), []
+    for a in axes:
+        cur[a] = So[a]
+        after.append(cur[0] * cur[1] * cur[2])
+    t1 = after[0] if len(axes) >= 2 else 0
+    t2 = after[1] if len(axes) >= 3 else 0
+    per_vol = (t1 + t2) * 4
+    chunk = N if per_vol == 0 else max(1, min(N, RESAMPLE_CHUNK_BYTES // per_vol))
+    t2_offset = (chunk * t1 + 63) // 64 * 64
+    return chunk, t1, t2, t2_offset, max(256, (t2_offset + chunk * t2) * 4)

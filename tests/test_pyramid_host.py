@@ -79,3 +79,39 @@ def test_register_levels_validation_before_the_gpu():
     tr.Register("flow", levels=1)                            # the U-Net is fine at one level
     with pytest.raises(tr._lib.TrxError, match="no CPU fallback"):
         tr.Register("affine", levels=2).optim(mov, tgt, max_epochs=[3, 3])     # a valid schedule reaches the GPU check
+
+
+def test_resample_workspace_is_the_chunked_plan():
+    """trx_resample_workspace_bytes is exactly the plan's formula (resample_plan_ref): chunk, t1, t2, t2 on a 64-float boundary, 256 bytes
+    at least.  The chunked shapes are the ones tests/test_gpu_pyramid_edges.py runs, so a change to the plan shows up here first."""
+    from resample_ref import RESAMPLE_CHUNK_BYTES, resample_plan_ref
+    from torchregister_amd import _lib
+    lib = _lib.load()
+
+    def ws(N, sp, size):
+        S = (1,) * (3 - len(sp)) + tuple(sp)
+        So = (1,) * (3 - len(size)) + tuple(size)
+        return lib.trx_resample_workspace_bytes(len(sp), N, *S, *So)
+
+    # 5 x 256^3 -> 128^3: W, H, D halve (ties: inner axis first); 48 MiB of intermediates per volume -> chunks of 2 + 2 + 1
+    t1, t2 = 256 * 256 * 128, 256 * 128 * 128
+    assert resample_plan_ref(5, (256,) * 3, (128,) * 3) == (2, t1, t2, 2 * t1, (2 * t1 + 2 * t2) * 4)
+    assert ws(5, (256,) * 3, (128,) * 3) == (2 * t1 + 2 * t2) * 4 == 96 << 20
+    assert ws(5, (256,) * 3, (128,) * 3) < 5 * (t1 + t2) * 4                # smaller than the un-chunked need
+    # upsample_flow of one 128^3 flow to 256^3: 3 volumes, chunks of 2 + 1
+    t1, t2 = 128 * 128 * 256, 128 * 256 * 256
+    assert resample_plan_ref(3, (128,) * 3, (256,) * 3) == (2, t1, t2, 2 * t1, (2 * t1 + 2 * t2) * 4)
+    assert ws(3, (128,) * 3, (256,) * 3) == (2 * t1 + 2 * t2) * 4 < 3 * (t1 + t2) * 4
+    # the 64-float rounding of t2's offset: W, D, H: t1 = 9*11*6, t2 = 5*11*6; chunk * t1 = 1782 floats -> t2 starts at 1792
+    assert resample_plan_ref(3, (9, 11, 13), (5, 7, 6)) == (3, 594, 330, 1792, (1792 + 3 * 330) * 4)
+    assert ws(3, (9, 11, 13), (5, 7, 6)) == (1792 + 3 * 330) * 4
+    # the 256-byte floor: one pass has no intermediates, two small passes fewer than 64 floats
+    assert ws(7, (12, 10), (6, 10)) == 256 and resample_plan_ref(7, (12, 10), (6, 10))[4] == 256
+    assert ws(1, (3, 4), (7, 9)) == 256 and ws(4, (5, 5, 5), (5, 5, 5)) == 256
+    assert ws(70000, (3, 4), (7, 9)) == (70000 * 27 + 63) // 64 * 64 * 4       # 2-D grow, W first: t1 = 3 x 9 per volume, one chunk
+    # the same formula on a spread of shapes, chunked or not
+    for N, sp, size in [(1100 * 64, (12, 10), (6, 5)), (9, (200, 300, 64), (100, 150, 64)), (2, (37, 50, 61), (19, 25, 31)),
+                        (3, (9, 130, 7), (9, 65, 7)), (6, (64, 64, 300), (32, 150, 600)), (1, (1, 70), (3, 1)), (40, (160, 192, 224), (80, 96, 112))]:
+        plan = resample_plan_ref(N, sp, size)
+        assert ws(N, sp, size) == plan[4], (N, sp, size, plan)
+        assert plan[0] == N or (plan[0] + 1) * (plan[1] + plan[2]) * 4 > RESAMPLE_CHUNK_BYTES

@@ -75,6 +75,8 @@ class Register():
         independent pairs is an extension).  Sets self.theta (best theta [B,nd,nd+1], or the flow
         [B,nd,...] of the last forward in flow mode) and self.warp.  Returns None.
         With levels > 1, lr and max_epochs may each be one value for every level or a sequence of `levels` values, coarse to fine.
+        A level with max_epochs 0 runs no iteration and hands its starting parameters to the next level unchanged (its entry in
+        .level_losses is empty).
         '''
         if self.levels > 1:
             return self._optim_levels(moving, target, lr, max_epochs, n, per)

@@ -176,7 +176,9 @@ def _generic_loop(moving, target, mode, criterions, weights, lr, epochs, init, o
             best = (v, theta_fwd, warped.detach())
     final_theta = make().detach().clone()
     final_warped = get_affine_warp(final_theta, moving)
-    res = dict(losses=torch.tensor(losses), final_theta=final_theta, best_theta=best[1], best_idx=int(torch.tensor(losses).argmin()))
+    if best is None:                            # epochs == 0: the start is both the final and the best theta (as on the fused path)
+        best = (None, final_theta.clone(), final_warped)
+    res = dict(losses=torch.tensor(losses), final_theta=final_theta, best_theta=best[1], best_idx=int(torch.tensor(losses).argmin()) if losses else 0)
     if mode == "rigid":
         res["final_pose"] = p.detach().reshape(1, -1).clone()
     return [final_warped, best[2]], [final_theta, best[1]], res
@@ -478,6 +480,7 @@ class flow_register(nn.Module):
             fl = self.init_flow.detach().to(moving.device).reshape(moving.shape[0], nd, *moving.shape[2:]).clone().requires_grad_()
         opt = torch.optim.SGD([fl], self.lr) if self.optimizer_kind == "sgd" else torch.optim.Adam([fl], self.lr)
         losses, message = [], "Reached max epochs"
+        last = fl.detach().clone()                     # max_epochs == 0: the starting flow is the last and the final one
         for _ in range(self.max_epochs):
             opt.zero_grad()
             last = fl.detach().clone()
