@@ -8,5 +8,5 @@ name=$1; shift
 mkdir -p build/v_$name
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -fno-slp-vectorize -Wno-unused-variable "$@" -c torchregister_amd/csrc/$obj.hip -o build/v_$name/$obj.o
 objs=""
-for o in api affine flow lncc kde peer; do if [ $o = $obj ]; then objs="$objs build/v_$name/$o.o"; else objs="$objs build/$o.o"; fi; done
+for src in torchregister_amd/csrc/*.hip; do o=$(basename $src .hip); if [ $o = $obj ]; then objs="$objs build/v_$name/$o.o"; else objs="$objs build/$o.o"; fi; done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o build/libtrx_$name.so $objs

@@ -43,7 +43,7 @@ def slabs(xcd):      # the product: block g of the flat grid -> column (g & 7) *
     return out
 
 
-def patches(xcd):    # TRX_EF_PATCH = 1
+def patches(xcd):    # the 8 x 4 patch placement (a removed alternative of the exact-footprint kernel)
     PX, PZ = xcd % 2, xcd // 2
     return [[(PX * 8 + ix, yseg * 8 + t, PZ * 4 + iz) for t in range(8)] for yseg in range(2) for iz in range(4) for ix in range(8)]
 

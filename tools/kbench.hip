@@ -110,7 +110,6 @@ int main(int argc, char **argv)
         const trx::TileGeom ta = trx::tile_geom<trx::GeomA>(vol), tr = trx::tile_geom<trx::GeomR>(vol);
         const int gx = ta.blocks_per_pair > tr.blocks_per_pair ? ta.blocks_per_pair : tr.blocks_per_pair;
         rep("dual MODE0 (GeomA chosen)", time_it([&] { hipLaunchKernelGGL((trx::affine_tile_dual_kernel<0>), dim3(gx, B), dim3(512), 0, 0, vol, theta, ta, tr, 1, partials); }, 20));
-        rep("split MODE0 (GeomA chosen)", time_it([&] { hipLaunchKernelGGL((trx::affine_tile_dual_kernel<0, 1>), dim3(gx, B), dim3(512), 0, 0, vol, theta, ta, tr, 1, partials); hipLaunchKernelGGL((trx::affine_tile_dual_kernel<0, 2>), dim3(gx, B), dim3(512), 0, 0, vol, theta, ta, tr, 1, partials); }, 20));
     }
 #if TRX_TIMING
     {
@@ -138,7 +137,6 @@ int main(int argc, char **argv)
             const trx::TileGeom ta = trx::tile_geom<trx::GeomA>(vol), tr = trx::tile_geom<trx::GeomR>(vol);
             const int gx = ta.blocks_per_pair > tr.blocks_per_pair ? ta.blocks_per_pair : tr.blocks_per_pair;
             rep("dual MODE0 rot 0.5 (GeomR)", time_it([&] { hipLaunchKernelGGL((trx::affine_tile_dual_kernel<0>), dim3(gx, B), dim3(512), 0, 0, vol, theta, ta, tr, 1, partials); }, 10));
-            rep("split MODE0 rot 0.5 (GeomR)", time_it([&] { hipLaunchKernelGGL((trx::affine_tile_dual_kernel<0, 1>), dim3(gx, B), dim3(512), 0, 0, vol, theta, ta, tr, 1, partials); hipLaunchKernelGGL((trx::affine_tile_dual_kernel<0, 2>), dim3(gx, B), dim3(512), 0, 0, vol, theta, ta, tr, 1, partials); }, 10));
         }
         {   // a general rotation (Rz(0.6) Ry(0.8) Rx(0.7), what the reference's random rigid init looks like)
             const double a = 0.8, bz = 0.6, c = 0.7;
@@ -152,9 +150,8 @@ int main(int argc, char **argv)
             const trx::TileGeom ta = trx::tile_geom<trx::GeomA>(vol), tr = trx::tile_geom<trx::GeomR>(vol);
             const int gx = ta.blocks_per_pair > tr.blocks_per_pair ? ta.blocks_per_pair : tr.blocks_per_pair;
             rep("dual MODE0 rot .8/.6/.7", time_it([&] { hipLaunchKernelGGL((trx::affine_tile_dual_kernel<0>), dim3(gx, B), dim3(512), 0, 0, vol, theta, ta, tr, 1, partials); }, 10));
-            rep("split MODE0 rot .8/.6/.7", time_it([&] { hipLaunchKernelGGL((trx::affine_tile_dual_kernel<0, 1>), dim3(gx, B), dim3(512), 0, 0, vol, theta, ta, tr, 1, partials); hipLaunchKernelGGL((trx::affine_tile_dual_kernel<0, 2>), dim3(gx, B), dim3(512), 0, 0, vol, theta, ta, tr, 1, partials); }, 10));
             rep("tile MODE0 rot .8/.6/.7", time_it([&] { hipLaunchKernelGGL((trx::affine_tile_kernel<0>), tgrid, dim3(trx::kTileThreads), 0, 0, vol, theta, tgm, 1, partials); }, 10));
-            {   // a moderate general rotation (0.4 rad about every axis) and 0.3 rad about z: the single-geometry kernel only (GeomP = GeomR / GeomRD comparisons)
+            {   // a moderate general rotation (0.4 rad about every axis) and 0.3 rad about z: the single-geometry kernel only (GeomA)
                 for (int which = 0; which < 2; which++) {
                     const double a2 = which ? 0.0 : 0.4, b2 = which ? 0.3 : 0.4, c2 = which ? 0.0 : 0.4;
                     const double Ry2[9] = {cos(a2), 0, sin(a2), 0, 1, 0, -sin(a2), 0, cos(a2)}, Rz2[9] = {cos(b2), -sin(b2), 0, sin(b2), cos(b2), 0, 0, 0, 1},
@@ -179,7 +176,6 @@ int main(int argc, char **argv)
         const trx::TileGeom ta = trx::tile_geom<trx::GeomA>(vol), tr = trx::tile_geom<trx::GeomR>(vol);
         const int gx = ta.blocks_per_pair > tr.blocks_per_pair ? ta.blocks_per_pair : tr.blocks_per_pair;
         rep("dual MODE0 identity", time_it([&] { hipLaunchKernelGGL((trx::affine_tile_dual_kernel<0>), dim3(gx, B), dim3(512), 0, 0, vol, theta, ta, tr, 1, partials); }, 20));
-        rep("split MODE0 identity", time_it([&] { hipLaunchKernelGGL((trx::affine_tile_dual_kernel<0, 1>), dim3(gx, B), dim3(512), 0, 0, vol, theta, ta, tr, 1, partials); hipLaunchKernelGGL((trx::affine_tile_dual_kernel<0, 2>), dim3(gx, B), dim3(512), 0, 0, vol, theta, ta, tr, 1, partials); }, 20));
     }
     rep("tile MODE0 identity", time_it([&] { hipLaunchKernelGGL((trx::affine_tile_kernel<0>), tgrid, dim3(trx::kTileThreads), 0, 0, vol, theta, tgm, 1, partials); }, 20));
     {   // what bench.py's run looks like after its 125 Adam iterations: |theta - I| ~ 0.0125, plus a shift

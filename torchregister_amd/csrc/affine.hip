@@ -189,19 +189,15 @@ __global__ __launch_bounds__(TRX_BLOCK) void affine_accum_kernel(trx_volumes vol
 // Thread (x, z) is fixed for the whole column, so only sum(q grad) and sum(q grad yn) live in registers and
 // the xn / zn columns of the 41 sums are one multiply at the very end.
 // ------------------------------------------------------------------------------------------
-// Two geometries of the tile kernel:
-//  cfg 0: 512-thread blocks, tile 32 x 16 y 8 z, ONE 56.7 KB box, 2 blocks per CU (staging of one block overlaps the gather
-//         of the other), 7 DMA pieces of two box planes each;
-//  cfg 1: 1024-thread blocks, tile 32 x 16 y 16 z, TWO 81.3 KB boxes (all 160 KB of a CU's LDS), 1 block per CU: the DMA
-//         of tile t+1 runs during the gather of tile t inside the block, one barrier per tile, and the deeper tile cuts the
-//         z-halo share of the bytes a CU ingests from 13/8 to 21/16; 6 DMA pieces of four box planes each.
+// Every geometry: 512-thread blocks, ONE box, 2 blocks per CU (staging of one block overlaps the gather of the other).  Removed
+// alternative ("cfg 1"): 1024-thread blocks with two 81.3 KB boxes, one block per CU, 324-331 us against 315.
 // LDS box (floats), kBW % 4 == 0.  One LDS-DMA piece (one global_load_lds_dwordx4 per wave) covers kPP z planes of the
 // box - at most one float4 slot per thread - so piece k of a thread is its piece-0 slot shifted by k * kPP planes: one VGPR
 // offset + one packed slot id per thread instead of one per piece.
-template <int TX_, int TZ_, int THREADS_, int BW_, int BH_, int BD_, int PP_, int BUFS_, int TY_ = 16>
+template <int TX_, int TZ_, int THREADS_, int BW_, int BH_, int BD_, int PP_, int TY_ = 16>
 struct TileCfg {
     static constexpr int TX = TX_, TY = TY_, TZ = TZ_, Threads = THREADS_;
-    static constexpr int BW = BW_, BH = BH_, BD = BD_, PP = PP_, Bufs = BUFS_;
+    static constexpr int BW = BW_, BH = BH_, BD = BD_, PP = PP_;
     static constexpr int NH = Threads / (TX * TZ);          // y groups of a tile (2 halves of 8 rows, or 4 quarters of 4)
     static constexpr int Rows = TY / NH;                    // rows per thread
     static constexpr int Waves = Threads / 64;
@@ -211,56 +207,36 @@ struct TileCfg {
     static constexpr int PieceFloats = PP * BH * BW;        // floats of LDS per piece
     static constexpr int BoxFloats = BW * BH * BD;          // one box; lanes of the last piece past it are always masked
     static constexpr int ReduceScratch = Waves * 16 * 65 + Waves * 16;   // floats block_reduce_store_nw needs (aliases the box)
-    static constexpr int BoxAlloc = (Bufs * BoxFloats > ReduceScratch) ? Bufs * BoxFloats : ReduceScratch;
+    static constexpr int BoxAlloc = (BoxFloats > ReduceScratch) ? BoxFloats : ReduceScratch;
     static_assert(BW % 4 == 0 && PP * PlaneSlots <= Threads && (PP == 2 || PP == 4), "one DMA piece: at most one slot per thread");
 };
-using GeomA = TileCfg<32, 8, 512, 44, 23, TRX_GEOMA_BD, 2, 1>;      // near-identity transforms: 32 x 16 x 8 tile, 44 x 23 x 14 box (56.7 KB)
-using GeomDeep = TileCfg<32, 16, 1024, 44, 22, 21, 4, 2>;  // cfg 1 (measured alternative): 1024 threads, two 81 KB boxes
+using GeomA = TileCfg<32, 8, 512, 44, 23, TRX_GEOMA_BD, 2>;      // near-identity transforms: 32 x 16 x 8 tile, 44 x 23 x 14 box (56.7 KB)
 // Rotated transforms: the pre-image of a 32-wide tile grows by 31 sin(angle) rows / planes and stops fitting any box beyond
-// ~0.1 rad.  A more cubic tile (16 x 16 x 8, four y-quarters of 4 rows per thread) with a 28 x 26 x 16 box (46.6 KB) fits
-// every rotation about one axis up to ~0.5 rad at 55 us per 256^3 pair, whatever the angle (the global-gather fallback: 125 us).
-#if TRX_GEOMR_BIG
-// 28 x 27 x 26 box (78.6 KB, still two blocks per CU): the pre-image of the 16 x 16 x 8 tile under ANY rotation (span <= |(15,15,7)| = 22.3
-// voxels per axis) fits, i.e. every pose the reference's rigid mode can draw (angles uniform in [0,1) rad, ref:utils.py:316-330);
-// only the needed extent is fetched, so small angles cost what they cost with the 28 x 26 x 16 box.
+// ~0.1 rad.  A more cubic tile (16 x 16 x 8, four y-quarters of 4 rows per thread) with a 28 x 27 x 26 box (78.6 KB, still two blocks
+// per CU): the pre-image of the tile under ANY rotation (span <= |(15,15,7)| = 22.3 voxels per axis) fits, i.e. every pose the reference's
+// rigid mode can draw (angles uniform in [0,1) rad, ref:utils.py:316-330); only the needed extent is fetched, so small angles cost what
+// they cost with a 28 x 26 x 16 box (the removed alternative: rotations about one axis up to ~0.5 rad, 55 us per 256^3 pair).
 #ifndef TRX_GEOMR_BH
 #define TRX_GEOMR_BH 27
 #define TRX_GEOMR_BD 26
 #endif
-using GeomR = TileCfg<16, 8, 512, 28, TRX_GEOMR_BH, TRX_GEOMR_BD, 2, 1>;
-#else
-using GeomR = TileCfg<16, 8, 512, 28, 26, 16, 2, 1>;
-#endif
-// Wide tile (64 x 8 x 8, one row block of 8 per thread): a box row of 64 + halo voxels touches 3.3 L2 lines for 64 voxels where the
-// 32-wide tile touches 2.3 for 32, i.e. 366 instead of 444 box lines per 4096 voxels; the 76 x 13 x 14 box fits |rotation| < ~0.04 rad.
-using GeomW = TileCfg<64, 8, 512, 76, 13, 14, 2, 1, 8>;
+using GeomR = TileCfg<16, 8, 512, 28, TRX_GEOMR_BH, TRX_GEOMR_BD, 2>;
+// (Removed alternative, GeomW: a 64 x 8 x 8 tile with a 76 x 13 x 14 box, -3 % at the identity, fits |rotation| < ~0.04 rad only: profiles/HISTORY.md.)
 // Deep tile on 512 threads (32 x 16 x 16, sixteen rows per thread, ONE 44 x 23 x 19 box = 76.9 KB, two blocks per CU): per-tile work and the two
 // barriers are paid once per 8192 voxels instead of 4096 and the z halo is 18 / 16 instead of 10 / 8; the box has one plane of slack, so it
 // serves |theta - I| up to ~0.03 rad about x / y only.
-using GeomD = TileCfg<32, 16, 512, 44, 23, 19, 2, 1>;
+using GeomD = TileCfg<32, 16, 512, 44, 23, 19, 2>;
 // GeomR's box under a 16 x 16 x 16 tile (eight rows per thread): per-tile work is paid once per 4096 voxels instead of 2048 and the z halo is
 // 18 / 16 instead of 10 / 8; the pre-image fits the 26-plane box for rotations about z of any size GeomR serves and for general rotations up to
 // ~0.4 rad per axis.
-using GeomRD = TileCfg<16, 16, 512, 28, TRX_GEOMR_BH, TRX_GEOMR_BD, 2, 1>;
-#if TRX_TILE_CFG == 5
-using GeomP = GeomRD;
-#elif TRX_TILE_CFG == 4
-using GeomP = GeomD;
-#elif TRX_TILE_CFG == 1
-using GeomP = GeomDeep;   // primary geometry
-#elif TRX_TILE_CFG == 3
-using GeomP = GeomW;
-#elif TRX_TILE_CFG == 2
-using GeomP = GeomR;
-#else
-using GeomP = GeomA;
-#endif
+using GeomRD = TileCfg<16, 16, 512, 28, TRX_GEOMR_BH, TRX_GEOMR_BD, 2>;
+// The single-geometry kernel (affine_tile_kernel, TRX_FLAG_SINGLE_GEOM) runs GeomA.
 
 struct TileGeom {
     int ntx, nty, ntz, ntiles, blocks_per_pair, ysplit, tiles_per_seg;
 };
 
-template <class G = GeomP>
+template <class G = GeomA>
 static TileGeom tile_geom(const trx_volumes &v)
 {
     TileGeom t;
@@ -282,7 +258,6 @@ static TileGeom tile_geom(const trx_volumes &v)
     int ys = 1;
     if (target > 0) {
         ys = (int)((target + cols - 1) / cols);
-#if TRX_GEOM_MODEL
     } else if (cols * t.nty > 1024) {
         // Occupancy model of one launch, in units of "one tile on a CU that runs a single block": 512 block slots (two per CU); a block
         // costs its tiles + 1.5 of prologue / epilogue, times 1.6 when it shares its CU (the pair together: 1.25x a lone block); blocks
@@ -303,8 +278,7 @@ static TileGeom tile_geom(const trx_volumes &v)
             if (rem > 0) cost += (rem <= 256 ? 1.0 : 1.6) * (tps + 1.5);
             if (cost < best - 1e-9) { best = cost; ys = c; }
         }
-#endif
-    } else if (cols <= 512) {   // (with the model: launches of at most two tiles per block slot, where fixed costs decide and the model does not resolve them)
+    } else if (cols <= 512) {   // (launches of at most two tiles per block slot, where fixed costs decide and the model does not resolve them: the round-1 rules)
         ys = (int)((512 + cols - 1) / cols);
         const int cap = t.nty / 2 > 1 ? t.nty / 2 : 1;
         if (ys > cap && cols * cap >= 256) ys = cap;   // (tiny volumes: as many blocks as there are tiles - 1 x 64^3: 8.9 vs 12.1 us)
@@ -371,7 +345,7 @@ __device__ __forceinline__ void f1_accumulate_pk(const Samp3 &sm, float yv, floa
     }
 }
 
-constexpr int kTileThreads = GeomP::Threads;   // block size of the primary kernel (the dual kernel: 512)
+constexpr int kTileThreads = GeomA::Threads;   // block size of the primary kernel (the dual kernel: 512)
 
 // Work-item id of a 1-D block WITHOUT keeping v0 (the packed ids the hardware delivers) alive: lane id from v_mbcnt, wave index read once
 // at kernel entry into an SGPR (trx_wave_index).  With five bodies inlined behind a dispatch the allocator spilled v0 to scratch at entry and
@@ -447,7 +421,10 @@ __device__ __forceinline__ void tile_body(const trx_volumes &vol, const float *_
                                           float *__restrict__ partials, float *box, const int bx, const int by, const int rows_stride, const int wave_in)
 {
     // geometry of this instantiation (bx, by: the block's index in the (blocks_per_pair, pairs x channels) grid)
-    constexpr int kTX = G::TX, kTY = G::TY, kTZ = G::TZ, kBW = G::BW, kBH = G::BH, kBD = G::BD, kPP = G::PP, kBufs = G::Bufs;
+    constexpr int kTX = G::TX, kTY = G::TY, kTZ = G::TZ, kBW = G::BW, kBH = G::BH, kBD = G::BD, kPP = G::PP;
+    // One box per block in every geometry.  The two-box form of the fast loop (kBufs == 2: the removed 1024-thread "cfg 1") stays below:
+    // deleting it changes the instructions of the kernels that remain.
+    constexpr int kBufs = 1;
     constexpr int kNH = G::NH, kRows = G::Rows, kTileWaves = G::Waves, kBW4 = G::BW4, kPlaneSlots = G::PlaneSlots, kPieces = G::Pieces;
     constexpr int kPieceFloats = G::PieceFloats, kBoxFloats = G::BoxFloats;
     (void)kNH; (void)kBD; (void)kPlaneSlots;
@@ -695,11 +672,7 @@ __device__ __forceinline__ void tile_body(const trx_volumes &vol, const float *_
                   unsigned m0s;
                   static_assert((kPieces >= 6 && kPieces <= 8) || (kPieces >= 9 && kPieces <= 13), "the DMA block below is written for 6, 7, 8 or 9..13 pieces");
                   // one exec mask + one SGPR-base load per piece; s[100:101] walks the volume by kPP planes per piece
-#if TRX_DMA_EXECZ_SKIP
-#define TRX_DMA_SKIP "s_cbranch_execz 1f\n\t"
-#else
-#define TRX_DMA_SKIP
-#endif
+#define TRX_DMA_SKIP "s_cbranch_execz 1f\n\t"   // a piece none of whose lanes fetch is branched over (an LDS-DMA with exec = 0 still costs its issue)
 #define TRX_DMA_NEXT(K)                                  \
     "s_add_u32 s100, s100, %[vstr]\n\t"                  \
     "s_addc_u32 s101, s101, 0\n\t"                       \
@@ -843,14 +816,14 @@ __device__ __forceinline__ void tile_body(const trx_volumes &vol, const float *_
 #pragma unroll
               for (int j = 0; j < kRows; j++) {
                   Fetch nxt;
-                  if (TRX_SWP && j + 1 < kRows) nxt = fetch(j + 1);
+                  if (j + 1 < kRows) nxt = fetch(j + 1);
                   if (kBufs == 2 && j < kPieces && dma_next) issue_piece(j);
                   const Samp3 sm = lerp3_pairs<kGrad>(cur.r00, cur.r01, cur.r10, cur.r11, cur.fx, cur.fy, cur.fz);
                   if constexpr (MODE == 3) { if (act) wout[(size_t)Y0 * W + (unsigned)(toff + j * W)] = sm.v; }
                   else f1_accumulate_pk<MODE>(sm, tv[j], yn_r[j], acc);
                   if (kBufs == 2 && TRX_DBG_SKIP != 3 && MODE != 3)
                       asm volatile("global_load_dword %0, %1, %2" : "=v"(tv[j]) : "v"(toffb), "s"(tnext + (size_t)j * W));
-                  if (j + 1 < kRows) cur = TRX_SWP ? nxt : fetch(j + 1);
+                  if (j + 1 < kRows) cur = nxt;
               }
           };
           auto load_targets = [&](int g, float (&tv)[kRows]) {
@@ -912,9 +885,9 @@ __device__ __forceinline__ void tile_body(const trx_volumes &vol, const float *_
               __syncthreads();
               TRX_TM_STAMP(tm2);
               const int gn = (gl + 1 < nf) ? gl + 1 : gl;
-              if (gl + 1 < nf) issue_box(gl + 1, (gl + 1) & 1, TRX_DMA_SPREAD);
+              if (gl + 1 < nf) issue_box(gl + 1, (gl + 1) & 1, true);
               TRX_TM_STAMP(tm3);
-              gather_tile(gl, gl & 1, yn_l, yid_l, tv, tgt + (size_t)(ty + gn) * kTY * W, TRX_DMA_SPREAD && gl + 1 < nf);
+              gather_tile(gl, gl & 1, yn_l, yid_l, tv, tgt + (size_t)(ty + gn) * kTY * W, gl + 1 < nf);
               TRX_TM_TILE_DONE();
             }
             // the prefetch issued during the last tile is still in flight: its destination registers must not be reused,
@@ -1121,13 +1094,13 @@ __device__ __forceinline__ void tile_body(const trx_volumes &vol, const float *_
     block_reduce_store_nw<NP, kTileWaves>(vals, partials + ((size_t)by * rows_stride + bx) * NP, box, wave);
 }
 
-// The primary kernel: one geometry (GeomP) for every block.
+// The primary kernel: one geometry (GeomA) for every block.
 template <int MODE>
-__global__ __launch_bounds__(GeomP::Threads, TRX_TILE_MIN_WAVES) void affine_tile_kernel(trx_volumes vol, const float *__restrict__ theta,
+__global__ __launch_bounds__(GeomA::Threads, TRX_TILE_MIN_WAVES) void affine_tile_kernel(trx_volumes vol, const float *__restrict__ theta,
                                                                                           TileGeom tg, int channels, float *__restrict__ partials)
 {
-    __shared__ __attribute__((aligned(16))) float box[GeomP::BoxAlloc + TRX_DEV_LDS_PAD];
-    tile_body<MODE, GeomP>(vol, theta, tg, channels, partials, box, blockIdx.x, blockIdx.y, gridDim.x, trx_wave_index());
+    __shared__ __attribute__((aligned(16))) float box[GeomA::BoxAlloc + TRX_DEV_LDS_PAD];
+    tile_body<MODE, GeomA>(vol, theta, tg, channels, partials, box, blockIdx.x, blockIdx.y, gridDim.x, trx_wave_index());
 }
 
 #pragma clang diagnostic pop
@@ -1164,28 +1137,18 @@ __device__ __forceinline__ int dual_choice(const float *__restrict__ th, float f
 // The dual kernel: per pair, GeomA where its box holds the pre-image of a GeomA tile for this theta (decided from the
 // tile-independent maximum extent, the same bound the fast loop fetches), GeomR otherwise.  The grid is sized for the geometry
 // with more blocks; the surplus blocks of the other one write a zero partial row and leave.
-// WHICH = 0: every body in one kernel (3: only GeomA and GeomR, whatever the mode).  WHICH = 1 / 2: only the GeomA / GeomR body - the pair of launches (1 then 2) does the
-// same job with each body compiled on its own (measured alternative: bench.py 0.328 ms per step against 0.323 ms for the two-body
-// kernel and 0.311-0.320 ms for the single-geometry kernel): blocks of a pair that the other geometry owns leave at once.
-#ifndef TRX_EF_RULE
-#define TRX_EF_RULE 1   // 0: round 4's first rule (GeomRD keeps every pair whose rotation is mostly about z)
-#endif
+// WHICH = 0: every body in one kernel (3: only GeomA and GeomR, whatever the mode).  (Removed alternative: the GeomA and GeomR bodies as two
+// launches of single-body kernels, bench.py 0.328 ms per step against 0.323 ms for the two-body kernel)
 __device__ __forceinline__ bool eft_wants(int choice, const float *__restrict__ th, float fD, float fH, float fW)
 {
     if (choice == 2) return true;
     if (choice != 3) return false;
     const float tilt = fabsf(th[8] * fD / fW) + fabsf(th[9] * fD / fH);                 // how far the tile's pre-image leans out of its z planes
     const float zspan = (tilt + fabsf(th[10])) * (float)(ECfg::TZ - 1);
-#ifdef TRX_EF_ZSPAN
-    return zspan > TRX_EF_ZSPAN;   // development
-#endif
-#if TRX_EF_RULE == 0
-    return zspan > 17.0f;
-#else
+    // (removed alternative, round 4's first rule: zspan > 17 alone - profiles/r05d_eft_offer_rule.txt)
     if (zspan > 17.0f || tilt > 0.07f) return true;
     const float s = fmaxf(fabsf(th[1] * fW / fH), fabsf(th[4] * fH / fW));              // in-plane rotation (its sine, in voxels)
     return s > 0.15f && s < 0.37f;   // GeomRD's rows are at their longest just past GeomD's window (NaN compares false: GeomRD)
-#endif
 }
 
 // The kernel arguments of affine_tile_dual_kernel as one struct: the kernel reads its arguments THROUGH THE KERNARG SEGMENT at the point
@@ -1241,19 +1204,15 @@ __global__ __launch_bounds__(512, TRX_DUAL_MIN_WAVES) void affine_tile_dual_kern
     static_assert(GeomRD::BoxAlloc <= GeomR::BoxAlloc, "GeomRD lives in GeomR's box");
     // the step kernels (MODE 0 / 4) of the one-launch form also carry the deep tile for transforms next to the identity
     // WHICH = 4: the same without the z-streaming body - behind affine_zs_step_kernel, which has taken the pairs next to the identity
-    // WHICH = 5: WHICH = 4 plus the exact-footprint body - ONE kernel behind the z-streaming kernel instead of two (a launch boundary and an
-    // empty 512-block dispatch less per step: 4-5 us; inside the five-body kernel of round 4 the same merge cost the z-streaming loop 7-12 %,
-    // which no longer lives here)
+    // (removed alternative: the exact-footprint body merged into WHICH = 4 - headline unchanged, rotated poses -5.5 %: profiles/r05a_eft_merged.txt)
     // WHICH = 6: WHICH = 3 (GeomA / GeomR, classic grid) in the CARRY form - the block's prologue finalises the previous iteration of its pair and theta comes from LDS
     constexpr bool kCarry = WHICH == 6;
     static_assert(!kCarry || MODE == 0 || MODE == 4, "the carry form exists for the step kernels");
-    constexpr bool kDeep = (WHICH == 0 || WHICH == 4 || WHICH == 5) && (MODE == 0 || MODE == 4) && (TRX_TILE_CFG == 0) && (TRX_DEEP_TILE != 0);
+    constexpr bool kDeep = (WHICH == 0 || WHICH == 4) && (MODE == 0 || MODE == 4);
     constexpr bool kZs = kDeep && WHICH == 0;
-    constexpr bool kEft = kDeep && WHICH == 5;
     constexpr int kAllocAR = GeomA::BoxAlloc > GeomR::BoxAlloc ? GeomA::BoxAlloc : GeomR::BoxAlloc;
-    constexpr int kAllocD = WHICH == 1 ? GeomA::BoxAlloc : (WHICH == 2 ? GeomR::BoxAlloc : ((kDeep && GeomD::BoxAlloc > kAllocAR) ? GeomD::BoxAlloc : kAllocAR));
-    constexpr int kAllocZ = (kZs && ZS64::Alloc > kAllocD) ? ZS64::Alloc : kAllocD;
-    constexpr int kAlloc = (kEft && ECfg::Alloc > kAllocZ) ? ECfg::Alloc : kAllocZ;
+    constexpr int kAllocD = (kDeep && GeomD::BoxAlloc > kAllocAR) ? GeomD::BoxAlloc : kAllocAR;
+    constexpr int kAlloc = (kZs && ZS64::Alloc > kAllocD) ? ZS64::Alloc : kAllocD;
     __shared__ __attribute__((aligned(16))) float box[kAlloc];
     constexpr bool kPerChannel = (MODE == 2) || (MODE == 3);
     constexpr int NP = (MODE == 0) ? np_full(3) : (MODE == 2 ? 12 : (MODE == 4 ? kNpMse : 5));
@@ -1279,15 +1238,15 @@ __global__ __launch_bounds__(512, TRX_DUAL_MIN_WAVES) void affine_tile_dual_kern
         zs_planes = kZs && nZ > 0 ? a->zg.planes_per_seg : 0;   // (WHICH = 4: the z-streaming test is the kernel's in front - never repeated here, where it could round differently)
         rows_stride = a->rows_stride;
         theta = a->theta;
-        with_ef = kDeep && a->rows_used != nullptr && (((TRX_EFT_BODY != 0) && a->eft != 0) || WHICH == 4 || WHICH == 5);   // pairs with rows_used < 0 belong to a kernel that ran in front
-        if constexpr (WHICH == 4 || WHICH == 5) {   // the kernels in front left the number of pairs they did NOT take: none - the usual case next to the identity - and this launch is over
+        with_ef = kDeep && a->rows_used != nullptr && (a->eft != 0 || WHICH == 4);   // pairs with rows_used < 0 belong to a kernel that ran in front
+        if constexpr (WHICH == 4) {   // the kernels in front left the number of pairs they did NOT take: none - the usual case next to the identity - and this launch is over
             const int *plan = a->rows_used + a->vol.B;
             if (__builtin_amdgcn_readfirstlane(*plan) == 0) return;
         }
     }
     // 6 = taken by the exact-footprint kernel (affine_eft_step_kernel, launched IN FRONT of this one: it left rows_used[b] = -(its row
     // count) for the pairs it took - rotated pairs that GeomR would run and whose plan fits its buffers): no block here
-    // 7 = (WHICH = 5) the exact-footprint body inside this kernel: its 16^3 tiling is GeomRD's
+    // (7 = the exact-footprint body inside this kernel, a removed alternative: its case stays here because the instructions of every instance depend on it)
     auto blocks_of = [&](int choice) { return choice == 6 ? 0 : (choice == 7 ? nRD : (choice == 4 ? nZ : (choice == 0 ? nD : (choice == 3 ? nRD : (choice == 1 ? nA : nR))))); };
     // Work items of this block: (pair / slab `by`, block index v of that pair's geometry).  Classic grid: exactly one, from blockIdx.
     // FLAT grid (rows_stride > 0; the launcher's choice for big batches of the step kernels): gridDim.x persistent blocks share one list
@@ -1317,30 +1276,6 @@ __global__ __launch_bounds__(512, TRX_DUAL_MIN_WAVES) void affine_tile_dual_kern
         int cnt = 0, ch = 2;
         if (lane < B) ch = dual_choice(theta + (size_t)lane * TRX_PSTRIDE, fD, fH, fW, with_d, with_rd, zs_planes);
         if (with_ef && lane < B && rows_used[lane] < 0) ch = 6;   // taken by the exact-footprint kernel, which ran in front of this one
-        if constexpr (kEft) {
-            // the exact-footprint body's pairs (affine_eft_step_kernel's decision, here): those GeomR or (eft_wants) GeomRD would run and whose plan
-            // fits its buffers - counted exactly, one candidate pair per wave and round
-            const float *thl = theta + (size_t)(lane < B ? lane : 0) * TRX_PSTRIDE;
-            const bool cand_l = lane < B && (ch == 2 || ch == 3) && eft_wants(ch, thl, fD, fH, fW) && ef_candidate(thl, fD, fH, fW);
-            const unsigned long long cand = __builtin_amdgcn_ballot_w64(cand_l);
-            if (cand) {   // (block-uniform)
-                if (wave_idx == 0) s_pre[lane] = 0;
-                __syncthreads();
-                unsigned long long rest = cand;
-                for (int k = 0; rest; k++) {
-                    const int pb = __builtin_ctzll(rest);
-                    rest &= rest - 1;
-                    if ((k & 7) != wave_idx) continue;
-                    const EfMap m = ef_map(theta + (size_t)pb * TRX_PSTRIDE, fD, fH, fW);
-                    const EfDims d = ef_dims(m);
-                    const int g = ef_plan_granules_wave(m, d, lane);
-                    if (lane == 0) s_pre[pb] = (d.ok && g > 0 && g <= ECfg::GCap) ? 1 : 0;
-                }
-                __syncthreads();
-                if (cand_l && s_pre[lane] != 0) ch = 7;
-                __syncthreads();   // (s_pre is rewritten below)
-            }
-        }
         if (lane < B) {
             cnt = blocks_of(ch);
             if (rows_used && blockIdx.x == 0 && wave_idx == 0 && ch != 6) rows_used[lane] = ch == 7 ? -rows_note(cnt, 7) : rows_note(cnt, 1 + ch);   // for the step's finalise kernel
@@ -1360,8 +1295,6 @@ __global__ __launch_bounds__(512, TRX_DUAL_MIN_WAVES) void affine_tile_dual_kern
         const int b = kPerChannel ? blockIdx.y / channels : blockIdx.y;
         my_choice = __builtin_amdgcn_readfirstlane(dual_choice(theta + (size_t)b * TRX_PSTRIDE, fD, fH, fW, with_d, with_rd, zs_planes));
         if (with_ef && a->rows_used[b] < 0) my_choice = 6;   // taken by the exact-footprint kernel, which ran in front of this one
-        const bool useA = my_choice == 1;
-        if ((WHICH == 1 && !useA) || (WHICH == 2 && useA)) return;   // the other launch owns this pair (and its surplus rows)
         const int mine = blocks_of(my_choice);
         // zero_surplus = 0: surplus blocks write nothing; the reader (the step's finalise kernel) learns the pair's row count from
         // rows_used[], written here by the pair's first block - it does not repeat the choice (two inlined copies of a float test could
@@ -1380,7 +1313,7 @@ __global__ __launch_bounds__(512, TRX_DUAL_MIN_WAVES) void affine_tile_dual_kern
         if (flat) {
             const int pre = *(volatile int *)&s_pre[lane];
             // (round 5) odd iterations of a run (TRX_FLAG_WALK_DOWN) take the list backwards, in groups of 8 (item % 8 stays the XCD): they start on the pairs the Infinity Cache still holds
-            const int it = (TRX_DUAL_PINGPONG && WHICH == 4 && (args()->vol.flags & TRX_FLAG_WALK_DOWN) && (total & 7) == 0) ? total - 8 - (item & ~7) + (item & 7) : item;
+            const int it = (WHICH == 4 && (args()->vol.flags & TRX_FLAG_WALK_DOWN) && (total & 7) == 0) ? total - 8 - (item & ~7) + (item & 7) : item;
             const int pair = __builtin_amdgcn_readfirstlane(__builtin_popcountll(__builtin_amdgcn_ballot_w64(pre <= it)));   // lanes >= B hold the total: never counted
             const int off = pair > 0 ? __builtin_amdgcn_readlane(pre, pair - 1) : 0;
             choice = *(volatile int *)&s_choice[pair];
@@ -1404,15 +1337,6 @@ __global__ __launch_bounds__(512, TRX_DUAL_MIN_WAVES) void affine_tile_dual_kern
                 continue;
             }
         }
-        if constexpr (kEft) {
-            if (choice == 7) {   // (columns differ widely in cost: the column index is rotated per pair, by a multiple of 8 - see affine_eft_step_kernel)
-                const TileGeom t = tile_of(&a->tgRD);
-                const int ve = __builtin_amdgcn_readfirstlane((v + 104 * by) % t.blocks_per_pair);
-                EfPlanRegs pr;
-                eft_body<MODE>(vol, theta, t, partials, box, ve, by, stride, wave_idx, pr, true);
-                continue;
-            }
-        }
         if constexpr (kDeep) {
             if (choice == 0) {
                 const TileGeom t = tile_of(&a->tgD);
@@ -1425,19 +1349,15 @@ __global__ __launch_bounds__(512, TRX_DUAL_MIN_WAVES) void affine_tile_dual_kern
                 continue;
             }
         }
-        if constexpr (WHICH != 1) {
-            if (choice != 1) {
-                const TileGeom t = tile_of(&a->tgR);
-                if constexpr (kCarry) tile_body<MODE, GeomR, true>(vol, s_th, t, channels, partials, box, v, by, stride, wave_idx);
-                else tile_body<MODE, GeomR>(vol, theta, t, channels, partials, box, v, by, stride, wave_idx);
-                continue;
-            }
+        if (choice != 1) {
+            const TileGeom t = tile_of(&a->tgR);
+            if constexpr (kCarry) tile_body<MODE, GeomR, true>(vol, s_th, t, channels, partials, box, v, by, stride, wave_idx);
+            else tile_body<MODE, GeomR>(vol, theta, t, channels, partials, box, v, by, stride, wave_idx);
+            continue;
         }
-        if constexpr (WHICH != 2) {
-            const TileGeom t = tile_of(&a->tgA);
-            if constexpr (kCarry) tile_body<MODE, GeomA, true>(vol, s_th, t, channels, partials, box, v, by, stride, wave_idx);
-            else tile_body<MODE, GeomA>(vol, theta, t, channels, partials, box, v, by, stride, wave_idx);
-        }
+        const TileGeom t = tile_of(&a->tgA);
+        if constexpr (kCarry) tile_body<MODE, GeomA, true>(vol, s_th, t, channels, partials, box, v, by, stride, wave_idx);
+        else tile_body<MODE, GeomA>(vol, theta, t, channels, partials, box, v, by, stride, wave_idx);
     }
 }
 
@@ -1461,11 +1381,9 @@ __global__ __launch_bounds__(512, TRX_DUAL_MIN_WAVES) void affine_tile_dual_kern
 // rows_used[b] = -(its rows) for them and 0 for the rest, the number of pairs it did NOT take in rows_used[B] and the bit mask of those it
 // took in rows_used[B + 1, B + 2]: the two kernels behind it return at once when the count is zero (a launch boundary each, ~1.5 us), and
 // otherwise skip the pairs of the mask.
-#ifndef TRX_ZS_FLAT
-#define TRX_ZS_FLAT 1   // the z-streaming kernel also carries the FLAT tile (ZSF: 64 x 16 voxels per plane, ring of 8 planes of 80 x 30) for pairs the 64 x 32 tile
-                        // does not take: poses of the convergence basin (rotations up to ~0.15 rad about z, zooms to 1.15, 3.7 planes of tilt) run 10-11 %
-                        // faster on it than on the deep tile kernel (profiles/r05a_zs_flat_tile.txt); 0: never
-#endif
+// The z-streaming kernel also carries the FLAT tile (ZSF: 64 x 16 voxels per plane, ring of 8 planes of 80 x 30) for pairs the 64 x 32 tile
+// does not take: poses of the convergence basin (rotations up to ~0.15 rad about z, zooms to 1.15, 3.7 planes of tilt) run 10-11 %
+// faster on it than on the deep tile kernel (profiles/r05a_zs_flat_tile.txt).
 // FB (round 6): the ONE-KERNEL form of a step (TRX_FLAG_ONE_KERNEL) - nothing is launched behind this kernel, so the pairs its two streaming tiles do
 // not take run HERE, on GeomR's body (the tile whose box holds the pre-image under any rotation; 78.6 KB, inside the ring's allocation): a pair that
 // leaves the window costs ~2 x its usual time for as long as it stays outside, instead of two launches that find nothing to do on every step of every
@@ -1490,7 +1408,7 @@ __device__ __forceinline__ void zs_step_main(const trx_volumes &vol, const float
     int which = 0;
     if (lane < vol.B) {
         if (zs_nsub<ZS64>(theta + (size_t)lane * TRX_PSTRIDE, fD, fH, fW, zg.planes_per_seg) > 0) which = 1;
-        else if (TRX_ZS_FLAT && zgf.blocks_per_pair > 0 && zs_nsub<ZSF>(theta + (size_t)lane * TRX_PSTRIDE, fD, fH, fW, zgf.planes_per_seg) > 0) which = 2;
+        else if (zgf.blocks_per_pair > 0 && zs_nsub<ZSF>(theta + (size_t)lane * TRX_PSTRIDE, fD, fH, fW, zgf.planes_per_seg) > 0) which = 2;
         else if (FB) which = 3;
     }
     const unsigned long long take = __builtin_amdgcn_ballot_w64(which != 0), take1 = __builtin_amdgcn_ballot_w64(which == 1);
@@ -1511,7 +1429,7 @@ __device__ __forceinline__ void zs_step_main(const trx_volumes &vol, const float
         if (lane >= d) pre += t;
     }
     const int total = __builtin_amdgcn_readlane(pre, 63);
-    const int second = (int)(blockIdx.x * 2 >= gridDim.x);   // the later of the two blocks of a CU (TRX_ZS_PRIO)
+    const int second = (int)(blockIdx.x * 2 >= gridDim.x);   // the later of the two blocks of a CU (zstream_body's fair sharing)
     if constexpr (FB != 0) {
         // the pair's body rides in the low two bits of its prefix sum: the masks of the FB = 0 form (two scalar-register pairs, live across the streaming
         // loops, which have none to spare) would be three here
@@ -1531,7 +1449,7 @@ __device__ __forceinline__ void zs_step_main(const trx_volumes &vol, const float
                 asm volatile("" : "+s"(a));
                 const TileGeom t = {a->tgR.ntx, a->tgR.nty, a->tgR.ntz, a->tgR.ntiles, a->tgR.blocks_per_pair, a->tgR.ysplit, a->tgR.tiles_per_seg};
                 tile_body<MODE, GeomR>(vol, theta, t, 1, partials, ring, v, pair, stride, wave);
-            } else if (!TRX_ZS_FLAT || w == 1) zstream_body<MODE, ZS64>(vol, theta, zg, partials, ring, v, pair, stride, wave, second);
+            } else if (w == 1) zstream_body<MODE, ZS64>(vol, theta, zg, partials, ring, v, pair, stride, wave, second);
             else zstream_body<MODE, ZSF>(vol, theta, zgf, partials, ring, v, pair, stride, wave, second);
         }
         return;
@@ -1541,7 +1459,7 @@ __device__ __forceinline__ void zs_step_main(const trx_volumes &vol, const float
         const int off = pair > 0 ? __builtin_amdgcn_readlane(pre, pair - 1) : 0;
         const int v = __builtin_amdgcn_readfirstlane(item - off);
         if (item != (int)blockIdx.x) __syncthreads();   // the previous item's reduction scratch aliases the ring
-        if (!TRX_ZS_FLAT || ((take1 >> pair) & 1ull)) zstream_body<MODE, ZS64>(vol, theta, zg, partials, ring, v, pair, stride, wave, second);
+        if ((take1 >> pair) & 1ull) zstream_body<MODE, ZS64>(vol, theta, zg, partials, ring, v, pair, stride, wave, second);
         else zstream_body<MODE, ZSF>(vol, theta, zgf, partials, ring, v, pair, stride, wave, second);
     }
 }
@@ -1550,7 +1468,7 @@ template <int MODE>
 __global__ __launch_bounds__(ZS64::Threads, TRX_ZS_MIN_WAVES) void affine_zs_step_kernel(trx_volumes vol, const float *__restrict__ theta, ZGeom zg, ZGeom zgf, float *__restrict__ partials,
                                                                                          int *__restrict__ rows_used, int stride)
 {
-    constexpr int kAlloc = (TRX_ZS_FLAT && ZSF::Alloc > ZS64::Alloc) ? ZSF::Alloc : ZS64::Alloc;
+    constexpr int kAlloc = ZSF::Alloc > ZS64::Alloc ? ZSF::Alloc : ZS64::Alloc;
     __shared__ __attribute__((aligned(16))) float ring[kAlloc];
     zs_step_main<MODE, 0>(vol, theta, zg, zgf, partials, rows_used, stride, 0, ring);
 }
@@ -1559,7 +1477,7 @@ template <int MODE>
 __global__ __launch_bounds__(ZS64::Threads, TRX_ZS_MIN_WAVES) void affine_zs_one_kernel(trx_volumes vol, const float *__restrict__ theta, ZGeom zg, ZGeom zgf, float *__restrict__ partials,
                                                                                         int *__restrict__ rows_used, int stride, TileGeom tgR)
 {
-    constexpr int kAllocZ = (TRX_ZS_FLAT && ZSF::Alloc > ZS64::Alloc) ? ZSF::Alloc : ZS64::Alloc;
+    constexpr int kAllocZ = ZSF::Alloc > ZS64::Alloc ? ZSF::Alloc : ZS64::Alloc;
     constexpr int kAlloc = GeomR::BoxAlloc > kAllocZ ? GeomR::BoxAlloc : kAllocZ;
     __shared__ __attribute__((aligned(16))) float ring[kAlloc];
     zs_step_main<MODE, 1>(vol, theta, zg, zgf, partials, rows_used, stride, tgR.blocks_per_pair, ring);
@@ -1656,24 +1574,19 @@ __global__ __launch_bounds__(ECfg::Threads, 4) void affine_eft_step_kernel(trx_v
     // A block's items (pair-major index blockIdx + k gridDim) would be the SAME column in pair after pair - and columns differ widely in
     // cost (those that leave the source volume early are cheap): the column index is rotated per pair (by a multiple of 8: blocks b, b + 8,
     // ... still share an XCD's L2 with the neighbouring columns), which evens the blocks' loads without any shared counter.
-    // TRX_EF_CHUNK (round 5, measured alternative, off - see affine_eft.h): a block takes `ipb` CONSECUTIVE items of the pair-major list instead of every
-    // gridDim-th one, i.e. (when the pairs' item counts are multiples of ipb) items of ONE pair, whose plan it then makes once (eft_body's `replan`).
-    // Block jb of a pair (XCD jb & 7) takes the columns (jb & 7) + 8 (s nblk / 8 + jb / 8), s = 0 .. ipb - 1, of its XCD's slab.
-    // TRX_EF_TICKETS (round 5): behind affine_zs_step_kernel (which zeroes them) the flat grid's blocks DRAW their items - items cost 43 k ... 345 k ticks, and
+    // Tickets (round 5): behind affine_zs_step_kernel (which zeroes them) the flat grid's blocks DRAW their items - items cost 43 k ... 345 k ticks, and
     // with every gridDim-th item a launch waited 460 us for blocks whose median finished at 349 (profiles/r05c_eft_item_timeline.txt).  One queue per XCD
     // (block b draws from queue b & 7: the columns v = b & 7 (mod 8) of every pair, pair-major - the slab of its XCD's L2, as before); a block's first item is the
-    // one it had (no draw), the ticket of the next item is drawn when the current one is done (TRX_EF_TICKETS 2: at its START - no round trip to wait for, but every block then
-    // holds an item that nobody else can take: measured worse).
-    const bool tickets = TRX_EF_TICKETS && !TRX_EF_CHUNK && flat && zs_first && (tg.blocks_per_pair & 7) == 0 && (gridDim.x & 7) == 0 && (total % tg.blocks_per_pair) == 0;
-    const int ipb = __builtin_amdgcn_readfirstlane(flat ? (TRX_EF_CHUNK ? (total + (int)gridDim.x - 1) / (int)gridDim.x : 1) : 1);
-    const int it0 = flat ? (TRX_EF_CHUNK ? (int)blockIdx.x * ipb : (int)blockIdx.x) : 0, it_step = flat ? (TRX_EF_CHUNK ? 1 : (int)gridDim.x) : 1;
-    const int it_end = flat ? (TRX_EF_CHUNK ? min(total, it0 + ipb) : total) : 1;
+    // one it had (no draw), the ticket of the next item is drawn when the current one is done.  Removed alternatives (same profile): the ticket drawn at
+    // the START of an item (every block then holds an item nobody else can take: worse), and a block's items CONSECUTIVE - one plan per block - 12 % slower.
+    const bool tickets = flat && zs_first && (tg.blocks_per_pair & 7) == 0 && (gridDim.x & 7) == 0 && (total % tg.blocks_per_pair) == 0;
+    const int it0 = flat ? (int)blockIdx.x : 0, it_step = flat ? (int)gridDim.x : 1;
+    const int it_end = flat ? total : 1;
     EfPlanRegs pr;
     int planned = -1;   // the pair the registers and the row table in LDS belong to
     int q = blockIdx.x & 7;                                                                   // (tickets) the queue the current item came from: this block's XCD's, at the end any
     const int qlen = total >> 3, per_pair_q = tg.blocks_per_pair >> 3;                        // (tickets) a queue's length, a pair's items in it
     int qk = (int)blockIdx.x >> 3;                                                            // (tickets) position in the queue of the current item
-    int drawn = 0;                                                                            // (tickets 2; lane 0 of wave 0) the ticket drawn for the next item
     for (int item = __builtin_amdgcn_readfirstlane(it0); tickets ? (qk < qlen) : (item < it_end); item += it_step) {
         int v = blockIdx.x, pair = blockIdx.y;   // classic grid: the one item of this block
         if (flat) {
@@ -1682,20 +1595,13 @@ __global__ __launch_bounds__(ECfg::Threads, 4) void affine_eft_step_kernel(trx_v
                 // worse, 429 against 408 us: profiles/r05c_eft_item_timeline.txt)
                 int ord = qk / per_pair_q;                                    // the ord-th pair of those that fit ...
                 const int j = qk - ord * per_pair_q;                          // ... position in the XCD's slab
-                if (TRX_EF_PINGPONG && (vol.flags & TRX_FLAG_WALK_DOWN)) ord = total / tg.blocks_per_pair - 1 - ord;   // odd iterations of a run take the pairs in the opposite order: they start on what the Infinity Cache still holds
+                if (vol.flags & TRX_FLAG_WALK_DOWN) ord = total / tg.blocks_per_pair - 1 - ord;   // odd iterations of a run take the pairs in the opposite order: they start on what the Infinity Cache still holds
                 pair = __builtin_popcountll(__builtin_amdgcn_ballot_w64(pre <= ord * tg.blocks_per_pair));
                 v = q + 8 * j;
-                if (TRX_EF_TICKETS == 2 && wave == 0 && lane == 0) drawn = __hip_atomic_fetch_add(rows_used + vol.B + 3 + q, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             } else {
-            pair = __builtin_popcountll(__builtin_amdgcn_ballot_w64(pre <= item));
-            const int off = pair > 0 ? __builtin_amdgcn_readlane(pre, pair - 1) : 0;
-            if (TRX_EF_CHUNK) {
-                const int idx = item - off, nblk = tg.blocks_per_pair / ipb;
-                if (nblk * ipb == tg.blocks_per_pair && (nblk & 7) == 0 && (off % ipb) == 0) {
-                    const int jb = idx / ipb, sidx = idx - jb * ipb;
-                    v = (jb & 7) + 8 * (sidx * (nblk >> 3) + (jb >> 3));
-                } else v = idx;
-            } else v = (item - off + 104 * pair) % tg.blocks_per_pair;
+                pair = __builtin_popcountll(__builtin_amdgcn_ballot_w64(pre <= item));
+                const int off = pair > 0 ? __builtin_amdgcn_readlane(pre, pair - 1) : 0;
+                v = (item - off + 104 * pair) % tg.blocks_per_pair;
             }
         }
         v = __builtin_amdgcn_readfirstlane(v); pair = __builtin_amdgcn_readfirstlane(pair);
@@ -1705,16 +1611,13 @@ __global__ __launch_bounds__(ECfg::Threads, 4) void affine_eft_step_kernel(trx_v
 #if TRX_EF_STAMP
         if (flat && wave == 0 && lane == 0) { trx_ef_blocks[blockIdx.x * 8 + 1 + min((item - it0) / it_step, 5)] = __builtin_amdgcn_s_memrealtime(); }
 #endif
-        if (tickets) {   // the next item: the ticket drawn above, counted behind the (gridDim / 8) items the queue's blocks started with
+        if (tickets) {   // the next item: a ticket, counted behind the (gridDim / 8) items the queue's blocks started with
             if (wave == 0 && lane == 0) {
                 const int first = (int)gridDim.x >> 3;
-                int nq = blockIdx.x & 7, k = drawn + first;
-                if (TRX_EF_TICKETS != 2) {   // own queue first; when it is empty the others in turn (the XCDs' slabs differ in cost: edge slabs leave the source volume early)
-                    k = qlen;
-                    for (int t = 0; t < 8 && k >= qlen; t++) {
-                        nq = ((int)blockIdx.x + t) & 7;
-                        k = __hip_atomic_fetch_add(rows_used + vol.B + 3 + nq, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + first;
-                    }
+                int nq = blockIdx.x & 7, k = qlen;
+                for (int t = 0; t < 8 && k >= qlen; t++) {   // own queue first; when it is empty the others in turn (the XCDs' slabs differ in cost: edge slabs leave the source volume early)
+                    nq = ((int)blockIdx.x + t) & 7;
+                    k = __hip_atomic_fetch_add(rows_used + vol.B + 3 + nq, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + first;
                 }
                 s_ef[63] = k < qlen ? ((nq << 24) | k) : -1;
             }
@@ -1726,32 +1629,27 @@ __global__ __launch_bounds__(ECfg::Threads, 4) void affine_eft_step_kernel(trx_v
     }
 }
 
-// GeomA / GeomR per pair: one two-body launch or the pair of single-body launches (TRX_AFFINE_DUAL = 1 / 2, default 1: the pair costs one more launch and gains nothing).
+// GeomA / GeomR (and the step kernels' extra bodies) per pair in one launch
 template <int MODE>
-static void launch_dual(dim3 grid, hipStream_t s, const trx_volumes &v, const float *theta, const TileGeom &ta, const TileGeom &tr, int channels, float *out, int how,
+static void launch_dual(dim3 grid, hipStream_t s, const trx_volumes &v, const float *theta, const TileGeom &ta, const TileGeom &tr, int channels, float *out,
                         int zero_surplus = 1, TileGeom td = TileGeom{}, TileGeom trd = TileGeom{}, ZGeom zg = ZGeom{}, int *rows_used = nullptr, int rows_stride = 0,
                         int eft = 0, const CarryKArgs *carry = nullptr, bool *carry_used = nullptr)
 {
-    if (how == 1) {
-        // WHICH = 3: the two-body (GeomA / GeomR) instance for launches that offer nothing else - the five-body kernel's entry costs 2-3 us
-        // more (its arguments are fetched in front of the body that needs them), which is what a step of a small volume takes in all
-        // (and no exact-footprint kernel in front: the two-body instance does not read its marks and would run its pairs a second time - ADVICE r4)
-        if (td.blocks_per_pair == 0 && trd.blocks_per_pair == 0 && zg.blocks_per_pair == 0 && rows_stride == 0 && eft == 0) {
-            if constexpr (MODE == 0 || MODE == 4) {
-                if (carry != nullptr && rows_used != nullptr && zero_surplus == 0) {   // the carry form of the same launch (trx_affine_run): theta from the block's own prologue
-                    hipLaunchKernelGGL((affine_tile_dual_kernel<MODE, 6>), grid, dim3(512), 0, s, v, theta, ta, tr, channels, out, zero_surplus, td, trd, zg, rows_used, rows_stride, 0, *carry);
-                    *carry_used = true;
-                    return;
-                }
+    // WHICH = 3: the two-body (GeomA / GeomR) instance for launches that offer nothing else - the five-body kernel's entry costs 2-3 us
+    // more (its arguments are fetched in front of the body that needs them), which is what a step of a small volume takes in all
+    // (and no exact-footprint kernel in front: the two-body instance does not read its marks and would run its pairs a second time - ADVICE r4)
+    if (td.blocks_per_pair == 0 && trd.blocks_per_pair == 0 && zg.blocks_per_pair == 0 && rows_stride == 0 && eft == 0) {
+        if constexpr (MODE == 0 || MODE == 4) {
+            if (carry != nullptr && rows_used != nullptr && zero_surplus == 0) {   // the carry form of the same launch (trx_affine_run): theta from the block's own prologue
+                hipLaunchKernelGGL((affine_tile_dual_kernel<MODE, 6>), grid, dim3(512), 0, s, v, theta, ta, tr, channels, out, zero_surplus, td, trd, zg, rows_used, rows_stride, 0, *carry);
+                *carry_used = true;
+                return;
             }
-            hipLaunchKernelGGL((affine_tile_dual_kernel<MODE, 3>), grid, dim3(512), 0, s, v, theta, ta, tr, channels, out, zero_surplus, td, trd, zg, rows_used, rows_stride);
         }
-        else
-            hipLaunchKernelGGL((affine_tile_dual_kernel<MODE, 0>), grid, dim3(512), 0, s, v, theta, ta, tr, channels, out, zero_surplus, td, trd, zg, rows_used, rows_stride, eft);
-    } else {
-        hipLaunchKernelGGL((affine_tile_dual_kernel<MODE, 1>), grid, dim3(512), 0, s, v, theta, ta, tr, channels, out, 1);
-        hipLaunchKernelGGL((affine_tile_dual_kernel<MODE, 2>), grid, dim3(512), 0, s, v, theta, ta, tr, channels, out, 1);
+        hipLaunchKernelGGL((affine_tile_dual_kernel<MODE, 3>), grid, dim3(512), 0, s, v, theta, ta, tr, channels, out, zero_surplus, td, trd, zg, rows_used, rows_stride);
     }
+    else
+        hipLaunchKernelGGL((affine_tile_dual_kernel<MODE, 0>), grid, dim3(512), 0, s, v, theta, ta, tr, channels, out, zero_surplus, td, trd, zg, rows_used, rows_stride, eft);
 }
 
 #pragma clang diagnostic pop
@@ -2449,12 +2347,10 @@ constexpr int kTargetBlocks = 2048;
 
 using namespace trx;
 
-// 0 = primary geometry only (TRX_FLAG_SINGLE_GEOM), 1 = GeomA / GeomR chosen per pair inside one two-body kernel, 2 = the same choice
-// as a pair of single-body launches (compile-time alternative, TRX_DUAL_DEFAULT).
-static int use_dual(const trx_volumes *vol)
+// false: the single-geometry kernel only (TRX_FLAG_SINGLE_GEOM); true: GeomA / GeomR (and the step kernels' extra bodies) chosen per pair
+static bool use_dual(const trx_volumes *vol)
 {
-    if (vol->flags & TRX_FLAG_SINGLE_GEOM) return 0;
-    return TRX_TILE_CFG == 0 ? TRX_DUAL_DEFAULT : 0;
+    return !(vol->flags & TRX_FLAG_SINGLE_GEOM);
 }
 
 // Does a launch of the step kernels offer the z-streaming body to its pairs?  Sizes only (the theta part is zs_fits on the device):
@@ -2487,12 +2383,11 @@ static ZGeom zs_launch_geom(const trx_volumes &v)
 // partial rows per pair that a tile-path launch may write (the dual grid is sized for the geometry with more blocks)
 static size_t tile_rows_per_pair(const trx_volumes &v)
 {
-    size_t n = (size_t)tile_geom<GeomP>(v).blocks_per_pair;
-    const size_t a = (size_t)tile_geom<GeomA>(v).blocks_per_pair, r = (size_t)tile_geom<GeomR>(v).blocks_per_pair;
+    size_t n = (size_t)tile_geom<GeomA>(v).blocks_per_pair;
+    const size_t r = (size_t)tile_geom<GeomR>(v).blocks_per_pair;
     const size_t d = (size_t)tile_geom<GeomD>(v).blocks_per_pair, rd = (size_t)tile_geom<GeomRD>(v).blocks_per_pair;
     size_t z = zs_shape_ok<ZS64>(v) ? (size_t)zs_geom<ZS64>(v).blocks_per_pair : 0;
-    if (TRX_ZS_FLAT && zs_shape_ok<ZSF>(v) && (size_t)zs_geom<ZSF>(v).blocks_per_pair > z) z = (size_t)zs_geom<ZSF>(v).blocks_per_pair;
-    if (a > n) n = a;
+    if (zs_shape_ok<ZSF>(v) && (size_t)zs_geom<ZSF>(v).blocks_per_pair > z) z = (size_t)zs_geom<ZSF>(v).blocks_per_pair;
     if (r > n) n = r;
     if (d > n) n = d;
     if (rd > n) n = rd;
@@ -2543,7 +2438,7 @@ extern "C" int trx_affine_near_identity(const trx_volumes *vol, const float *the
     if (check_vol(vol, false) != TRX_OK || !theta_host || vol->ndim != 3) return 0;
     const ZGeom zg = zs_launch_geom(*vol);
     if (zg.blocks_per_pair == 0) return 0;
-    const bool flat_ok = TRX_ZS_FLAT && zs_shape_ok<ZSF>(*vol) && !(vol->flags & TRX_FLAG_NO_ZS_FLAT);
+    const bool flat_ok = zs_shape_ok<ZSF>(*vol) && !(vol->flags & TRX_FLAG_NO_ZS_FLAT);
     const ZGeom zgf = flat_ok ? zs_geom<ZSF>(*vol) : ZGeom{};
     const float fD = (float)vol->D, fH = (float)vol->H, fW = (float)vol->W;
     for (int b = 0; b < vol->B; b++) {
@@ -2611,7 +2506,7 @@ static int launch_f1(const trx_volumes *vol, const float *theta, float *partials
         if (dual && use_dual(vol)) {
             const TileGeom ta = tile_geom<GeomA>(*vol), tr = tile_geom<GeomR>(*vol);
             const int gx = ta.blocks_per_pair > tr.blocks_per_pair ? ta.blocks_per_pair : tr.blocks_per_pair;
-            const bool aware = rows_used != nullptr && use_dual(vol) == 1;
+            const bool aware = rows_used != nullptr;
             const bool step_kernel = aware && (MODE == 0 || MODE == 4);
             // the deep tile joins the choice only where the reader of the partial rows knows which rows were written (the step's finalise
             // kernel) and where its 128-row slabs still fill the chip (8192 voxels per tile: big batches)
@@ -2623,12 +2518,12 @@ static int launch_f1(const trx_volumes *vol, const float *theta, float *partials
                 const long blocks_d = (long)cand.blocks_per_pair * vol->B;
                 const long slots_d = persistent_blocks();   // block slots of these 512-thread kernels (MI355X: 512) - the same number the flat grid and the z-streaming / exact-footprint rules use
                 const long rem_d = blocks_d % slots_d;  // a last round that is less than ~60 % full costs more than the deeper tile saves (6 x 256^3: +6 %)
-                const bool small_ok = TRX_DEEP_SMALL && blocks_d >= slots_d && cand.tiles_per_seg >= 4 && (rem_d == 0 || rem_d >= slots_d * 5 / 8);
-                if (TRX_DEEP_TILE && (blocks_d >= 2 * slots_d || small_ok || (vol->flags & TRX_FLAG_DEEP_TILE))) td = cand;
+                const bool small_ok = blocks_d >= slots_d && cand.tiles_per_seg >= 4 && (rem_d == 0 || rem_d >= slots_d * 5 / 8);
+                if (blocks_d >= 2 * slots_d || small_ok || (vol->flags & TRX_FLAG_DEEP_TILE)) td = cand;
             }
             // GeomRD (GeomR's box under a 16 x 16 x 16 tile) joins under the same condition: rotations whose pre-image still fits that box
             TileGeom trd = TileGeom{};
-            if (step_kernel && TRX_ROT_DEEP_TILE && TRX_DEEP_TILE && !(vol->flags & TRX_FLAG_NO_ROT_DEEP_TILE)) {
+            if (step_kernel && !(vol->flags & TRX_FLAG_NO_ROT_DEEP_TILE)) {
                 const TileGeom cand = tile_geom<GeomRD>(*vol);
                 // tiny volumes (<= 64^3: at most 64 of these tiles) stay with GeomR's smaller tiles: measured +5 ... +14 % otherwise; and a launch
                 // of fewer than 1024 of these tiles (one pair up to 128^3) is a step of ~15 us, of which the five-body kernel's entry is 2-3
@@ -2636,32 +2531,30 @@ static int launch_f1(const trx_volumes *vol, const float *theta, float *partials
             }
             // the z-streaming body: pairs next to the identity (zs_fits) in launches that fill the chip
             ZGeom zg = ZGeom{};
-            if (step_kernel && TRX_DEEP_TILE) zg = zs_launch_geom(*vol);
+            if (step_kernel) zg = zs_launch_geom(*vol);
             int gxx = gx;
             if (td.blocks_per_pair > gxx) gxx = td.blocks_per_pair;
             if (trd.blocks_per_pair > gxx) gxx = trd.blocks_per_pair;
             if (zg.blocks_per_pair > gxx) gxx = zg.blocks_per_pair;
-            if (TRX_ZS_FLAT && zg.blocks_per_pair > 0 && zs_shape_ok<ZSF>(*vol) && zs_geom<ZSF>(*vol).blocks_per_pair > gxx) gxx = zs_geom<ZSF>(*vol).blocks_per_pair;
+            if (zg.blocks_per_pair > 0 && zs_shape_ok<ZSF>(*vol) && zs_geom<ZSF>(*vol).blocks_per_pair > gxx) gxx = zs_geom<ZSF>(*vol).blocks_per_pair;
             int *ru = aware ? (int *)((char *)ws_base + (odd ? ws.off_rows_used2 : ws.off_rows_used)) : nullptr;
             // big batches of the step kernels: a flat grid of persistent blocks over a pair-major work list (no surplus blocks; see the kernel)
             const int slots = persistent_blocks();
             // (B <= 64: the flat grid keeps one pair's state per lane)
-            const bool flat = step_kernel && TRX_DEEP_TILE && TRX_FLAT_GRID && vol->B <= 64 && (long)gxx * vol->B >= 2 * slots;
+            const bool flat = step_kernel && vol->B <= 64 && (long)gxx * vol->B >= 2 * slots;
             // the exact-footprint kernel (rotated pairs that GeomR would take) behind launches that fill the chip: columns of at most 64 of its tiles
             const TileGeom tef = tile_geom<GeomRD>(*vol);   // (its 16^3 tiling is GeomRD's)
             // (sizes: its row / plane pitches are 24-bit multiplier operands, its byte offsets 32-bit)
             const bool eft_sizes = (long)vol->H * vol->W * 4 < (1l << 24) && (size_t)vol->D * vol->H * vol->W < ((size_t)1 << 29);
-            const int eft = (TRX_EFT_BODY && step_kernel && TRX_DEEP_TILE && ru && tef.tiles_per_seg <= 64 && eft_sizes && !(vol->flags & TRX_FLAG_NO_EFT) &&
+            const int eft = (step_kernel && ru && tef.tiles_per_seg <= 64 && eft_sizes && !(vol->flags & TRX_FLAG_NO_EFT) &&
                              (flat || (vol->flags & TRX_FLAG_EFT))) ? tef.blocks_per_pair : 0;   // = the partial rows per pair of that kernel
             if (eft && tef.blocks_per_pair > gxx) gxx = tef.blocks_per_pair;
             // flat launches that offer the z-streaming body run it as a kernel of its own, FIRST (affine_zs_step_kernel): it alone evaluates the
             // test, the kernels behind it skip its pairs and return at once when it has taken them all
             const bool zs_first = flat && zg.blocks_per_pair > 0 && ru != nullptr && !(vol->flags & TRX_FLAG_ZS_FUSED);
-            // ... and the exact-footprint body then rides in the tile kernel (WHICH = 5) when its tiling is the one GeomRD is offered with
-            const bool eft_merged = TRX_EFT_MERGED && zs_first && eft != 0 && trd.blocks_per_pair == tef.blocks_per_pair && (MODE == 0 || MODE == 4);
             if constexpr (MODE == 0 || MODE == 4) {
                 if (zs_first) {
-                    const ZGeom zgf = (TRX_ZS_FLAT && zs_shape_ok<ZSF>(*vol) && !(vol->flags & TRX_FLAG_NO_ZS_FLAT)) ? zs_geom<ZSF>(*vol) : ZGeom{};
+                    const ZGeom zgf = (zs_shape_ok<ZSF>(*vol) && !(vol->flags & TRX_FLAG_NO_ZS_FLAT)) ? zs_geom<ZSF>(*vol) : ZGeom{};
                     if (vol->flags & TRX_FLAG_ONE_KERNEL) {
                         // the one-kernel form of a step: the streaming kernel also runs the pairs outside its window (GeomR's body), nothing behind it
                         hipLaunchKernelGGL((affine_zs_one_kernel<MODE>), dim3(slots, 1), dim3(ZS64::Threads), 0, s, v, theta, zg, zgf, partials, ru, gxx, tr);
@@ -2673,17 +2566,16 @@ static int launch_f1(const trx_volumes *vol, const float *theta, float *partials
                     hipLaunchKernelGGL((affine_zs_step_kernel<MODE>), dim3(slots, 1), dim3(ZS64::Threads), 0, s, v, theta, zg, zgf, partials, ru, gxx);
                     TRX_CHECK_LAUNCH();
                 }
-                if (eft && !eft_merged) {   // in front of the tile kernel: takes its pairs and marks them rows_used < 0 (none - the usual case next to the identity - costs ~3 us, ~1.5 behind the z-streaming kernel)
+                if (eft) {   // in front of the tile kernel: takes its pairs and marks them rows_used < 0 (none - the usual case next to the identity - costs ~3 us, ~1.5 behind the z-streaming kernel)
                     const int wd = td.blocks_per_pair > 0, wrd = trd.blocks_per_pair > 0, zp = zs_first ? -1 : (zg.blocks_per_pair > 0 ? zg.planes_per_seg : 0);   // (-1: the z-streaming kernel ran in front)
                     if (flat) hipLaunchKernelGGL((affine_eft_step_kernel<MODE>), dim3(slots, 1), dim3(ECfg::Threads), 0, s, v, theta, tef, partials, ru, gxx, wd, wrd, zp);
                     else hipLaunchKernelGGL((affine_eft_step_kernel<MODE>), dim3(tef.blocks_per_pair, vol->B), dim3(ECfg::Threads), 0, s, v, theta, tef, partials, ru, -gxx, wd, wrd, zp);
                     TRX_CHECK_LAUNCH();
                 }
             }
-            if (eft_merged) hipLaunchKernelGGL((affine_tile_dual_kernel<MODE, 5>), dim3(slots, 1), dim3(512), 0, s, v, theta, ta, tr, 1, partials, 0, td, trd, zg, ru, gxx, eft);
-            else if (zs_first) hipLaunchKernelGGL((affine_tile_dual_kernel<MODE, 4>), dim3(slots, 1), dim3(512), 0, s, v, theta, ta, tr, 1, partials, 0, td, trd, zg, ru, gxx, eft);
-            else if (flat) launch_dual<MODE>(dim3(slots, 1), s, v, theta, ta, tr, 1, partials, 1, 0, td, trd, zg, ru, gxx, eft);
-            else launch_dual<MODE>(dim3(gxx, vol->B), s, v, theta, ta, tr, 1, partials, use_dual(vol), aware ? 0 : 1, td, trd, zg, ru, 0, eft, cl ? &cl->args : nullptr, cl ? &cl->used : nullptr);
+            if (zs_first) hipLaunchKernelGGL((affine_tile_dual_kernel<MODE, 4>), dim3(slots, 1), dim3(512), 0, s, v, theta, ta, tr, 1, partials, 0, td, trd, zg, ru, gxx, eft);
+            else if (flat) launch_dual<MODE>(dim3(slots, 1), s, v, theta, ta, tr, 1, partials, 0, td, trd, zg, ru, gxx, eft);
+            else launch_dual<MODE>(dim3(gxx, vol->B), s, v, theta, ta, tr, 1, partials, aware ? 0 : 1, td, trd, zg, ru, 0, eft, cl ? &cl->args : nullptr, cl ? &cl->used : nullptr);
             TRX_CHECK_LAUNCH();
             *nblk = gxx;
             if (aware) *rows_used = ru;
@@ -2768,7 +2660,7 @@ extern "C" int trx_affine_run(const trx_volumes *vol, const trx_loss_cfg *loss, 
     // CARRY (CarryKArgs): launch-bound 3-D steps - one (GeomA / GeomR) kernel and a finalise kernel behind it - run as ONE launch per iteration: the finalise
     // of iteration k rides in the prologue of iteration k + 1's kernel, and one finalise kernel behind the last launch flushes the run.  The launches alternate
     // between the workspace's two partial / note / carry buffers; the LAST one writes the primary set (what trx_affine_workspace_rows_offset describes).
-    if (iters >= 2 && TRX_CARRY && !(vol->flags & TRX_FLAG_NO_CARRY) && check_vol(vol, true) == TRX_OK && vol->ndim == 3 && use_tile_path(vol) && loss && opt && workspace &&
+    if (iters >= 2 && !(vol->flags & TRX_FLAG_NO_CARRY) && check_vol(vol, true) == TRX_OK && vol->ndim == 3 && use_tile_path(vol) && loss && opt && workspace &&
         st->param && st->theta && st->best_theta && st->best_loss && st->best_idx && st->step && (opt->kind == TRX_OPT_SGD || (opt->kind == TRX_OPT_ADAM && st->adam_m && st->adam_v)) &&
         (st->mode == TRX_PARAM_AFFINE || st->mode == TRX_PARAM_RIGID) && workspace_bytes >= trx_affine_workspace_bytes(vol)) {
         hipStream_t s = (hipStream_t)stream;
@@ -2851,7 +2743,7 @@ extern "C" int trx_affine_warp(const trx_volumes *vol, const float *theta, int c
             const TileGeom ta = tile_geom<GeomA>(v), tr = tile_geom<GeomR>(v);
             v.B = vol->B;
             const int gx = ta.blocks_per_pair > tr.blocks_per_pair ? ta.blocks_per_pair : tr.blocks_per_pair;
-            launch_dual<3>(dim3(gx, vol->B * channels), s, v, theta, ta, tr, channels, out, use_dual(vol));
+            launch_dual<3>(dim3(gx, vol->B * channels), s, v, theta, ta, tr, channels, out);
             TRX_CHECK_LAUNCH();
             return TRX_OK;
         }
@@ -2893,7 +2785,7 @@ extern "C" int trx_affine_warp_backward(const trx_volumes *vol, const float *the
         if (use_dual(vol)) {
             const TileGeom ta = tile_geom<GeomA>(*vol), tr = tile_geom<GeomR>(*vol);
             rows = ta.blocks_per_pair > tr.blocks_per_pair ? ta.blocks_per_pair : tr.blocks_per_pair;
-            launch_dual<2>(dim3(rows, vol->B), s, v, theta, ta, tr, 1, partials, use_dual(vol));
+            launch_dual<2>(dim3(rows, vol->B), s, v, theta, ta, tr, 1, partials);
         } else {
             hipLaunchKernelGGL((affine_tile_kernel<2>), dim3(t.blocks_per_pair, vol->B), dim3(kTileThreads), 0, s, v, theta, t, 1, partials);
         }

@@ -19,9 +19,6 @@
 #ifndef TRX_EF_DBG
 #define TRX_EF_DBG 0   // development ablation (tools/ebench.hip): bits: 1 = no staging loads, 2 = no target loads, 4 = no gather
 #endif
-#ifndef TRX_EF_STAGES
-#define TRX_EF_STAGES 2   // rows in flight in the gather (3: also the table reads of row j + 2 - measured alternative)
-#endif
 #ifndef TRX_EF_STAMP
 #define TRX_EF_STAMP 0   // development (tools/ebench.hip): per-wave s_memtime sums of a tile step's phases and the block's start / end -> trx_ef_stamps
 #endif
@@ -33,44 +30,6 @@ __device__ unsigned long long trx_ef_stamps[1024 * 8 * 8];   // [item][wave][iss
 #endif
 #if !TRX_EF_STAMP
 #define TRX_EF_ST2(k) do { } while (0)
-#endif
-#ifndef TRX_EF_PRIO
-#define TRX_EF_PRIO 0       // 1: the two blocks of a CU alternate at s_setprio 1 in time slices of 2^TRX_EF_PRIO_BIT cycles (development)
-#endif
-#ifndef TRX_EF_PRIO_BIT
-#define TRX_EF_PRIO_BIT 14
-#endif
-#ifndef TRX_EF_PARTFIX
-#define TRX_EF_PARTFIX 0   // 1: granules that straddle a face in x travel by DMA like full ones and are patched in LDS afterwards, instead of element by element with
-                           // ordinary loads (and a wait for everything in flight) - measured alternative: 19.0-19.2 k against 19.2-19.3 k pair-it/s at the rotated
-                           // pose (profiles/r05c_eft_item_timeline.txt): the long request phases of boundary tiles are their per-granule tests, not those loads
-#endif
-#ifndef TRX_EF_SHAPE
-#define TRX_EF_SHAPE 0   // voxels of a wave per row: 0 = 16 x by 4 z, 1 = 8 x by 8 z
-#endif
-#ifndef TRX_EF_PINGPONG
-#define TRX_EF_PINGPONG 1   // the ticket queues run the pairs backwards when TRX_FLAG_WALK_DOWN is set (odd iterations of trx_affine_run)
-#endif
-#ifndef TRX_EF_TICKETS
-#define TRX_EF_TICKETS 1   // flat grid of the step kernel behind the z-streaming kernel: the blocks draw their items from one queue per XCD (0: every gridDim-th item)
-#endif
-#ifndef TRX_EF_CHUNK
-#define TRX_EF_CHUNK 0   // 1: flat grid of the step kernel: a block's items are consecutive (one pair, ONE plan for all of them) instead of every gridDim-th one - measured
-                         // alternative (profiles/r05c_eft_item_timeline.txt): the plan is made once instead of four times (an item's plan is done after 11.5 k ticks
-                         // instead of 19.7 k) and the launch is 12 % SLOWER: an XCD then holds 8 columns of each of 8 pairs instead of whole 32-column slabs of 2
-                         // pairs, and a tile step takes 10.4 k ticks instead of 8.8 k
-#endif
-#ifndef TRX_EF_ISSUE_PRIO
-#define TRX_EF_ISSUE_PRIO 0   // s_setprio of a wave while it requests the next tile (the stamps of tools/ebench.hip: 3 500 of a tile step's 8 900 cycles pass there) - development
-#endif
-#ifndef TRX_EF_ROWSTEP
-#define TRX_EF_ROWSTEP 1   // row terms of the coordinates and yn by stepping from the first row of a call instead of one v_readlane per row and term (0: measured alternative)
-#endif
-#ifndef TRX_EF_V2
-#define TRX_EF_V2 1   // round 5, by the price list of profiles/r05a_mfma_coissue_and_op_costs.txt (with TRX_EF_ROWSTEP): the row table in BYTES, so that the four data
-                      // addresses of a voxel are plain v_add_u32 (2.6 cycles) instead of v_add_lshl_u32 (5.0), and (x, y) stepped per row by one v_pk_add with a
-                      // scalar pair instead of two adds with scalar operands.  (The z-streaming body's lerp + accumulate, also tried here: 22 packed
-                      // instructions per voxel against this body's 17.5 - it has no v_mov to save - measured in profiles/r05c_eft_v2.txt.)
 #endif
 #ifndef TRX_EF_EPS
 #define TRX_EF_EPS 0.05f   // slack of every window bound: fp32 rounding of the coordinates + non-uniformity of ATen's coordinate tables
@@ -184,10 +143,6 @@ __device__ __forceinline__ bool ef_candidate(const float *__restrict__ th, float
     return ef_dims(m).ok;
 }
 
-#ifndef TRX_EF_PATCH
-#define TRX_EF_PATCH 0   // 1: an XCD's columns form 8 x 4 patches of the (x, z) tile grid instead of slabs of whole x rows - measured alternative: the kernel alone on a
-                         // classic grid -2 % (412 -> 405 us), inside the step's flat grid +1 ... +8 % (the per-pair column rotation balances slabs, not patches)
-#endif
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef int i2u __attribute__((ext_vector_type(2), aligned(4)));
 
@@ -224,8 +179,6 @@ __device__ __forceinline__ void eft_body(const trx_volumes &vol, const float *__
     constexpr int NP = (MODE == 0) ? np_full(3) : (MODE == 4 ? kNpMse : 5);
     constexpr bool kGrad = MODE != 1;
     constexpr int kRows = C::Rows, K = C::K;
-    constexpr bool kV2 = (TRX_EF_V2 != 0) && (TRX_EF_ROWSTEP != 0);
-    constexpr int kTabShift = kV2 ? 2 : 0;   // the row table holds byte offsets (V2) or dword indices
     const int b = by;
     const int D = vol.D, H = vol.H, W = vol.W;
     const float *__restrict__ th = uni_ptr(theta + (size_t)b * TRX_PSTRIDE);
@@ -235,11 +188,8 @@ __device__ __forceinline__ void eft_body(const trx_volumes &vol, const float *__
     const int lane = trx_lane_id();
     const int wave = __builtin_amdgcn_readfirstlane(wave_in);
     const int tid = wave * 64 + lane;
-#if TRX_EF_SHAPE == 1   // (measured alternative) a wave = 8 x by 8 z voxels of a row instead of 16 x by 4 z: waves 0-3 / 4-7 the two row halves, a wave's quadrant of the (x, z) face by its low two bits
-    const int lx = (tid & 7) + 8 * (wave & 1), lz = ((tid >> 3) & 7) + 8 * ((wave >> 1) & 1), lh = wave / (C::Waves / C::NH);
-#else
+    // (removed alternative: a wave = 8 x by 8 z voxels of a row instead of 16 x by 4 z - -1.7 % at the rotated pose)
     const int lx = tid & (C::TX - 1), lz = (tid / C::TX) & (C::TZ - 1), lh = wave / (C::Waves / C::NH);
-#endif
     const float fW = (float)W, fH = (float)H, fD = (float)D;
     const float hW = 0.5f * fW, hH = 0.5f * fH, hD = 0.5f * fD;
     const float t00 = th[0], t01 = th[1], t02 = th[2], t03 = th[3];
@@ -252,17 +202,9 @@ __device__ __forceinline__ void eft_body(const trx_volumes &vol, const float *__
     const int yseg = bx / ncol, cb = bx - yseg * ncol;
     int col = cb;
     if ((ncol & 7) == 0) col = (cb & 7) * (ncol >> 3) + (cb >> 3);
-    int colx = col % tg.ntx, colz = col / tg.ntx;
-#if TRX_EF_PATCH
-    // an XCD's columns as a compact patch of the (x, z) tile grid instead of a slab of whole x rows: the tiles its blocks work on at the
-    // same time share more of their footprints' faces (and of the 128-byte lines both touch) inside one L2
-    if ((tg.ntx & 7) == 0 && (tg.ntz & 3) == 0 && (ncol & 7) == 0 && ((ncol >> 3) & 31) == 0) {
-        const int per = ncol >> 3, k = cb & 7, i = cb >> 3;                    // XCD k, its i-th column
-        const int npx = tg.ntx >> 3, patches = per >> 5;                       // 8 x 4 patches: `patches` of them per XCD
-        const int pi = k * patches + (i >> 5), ii = i & 31;
-        colx = (pi % npx) * 8 + (ii & 7); colz = (pi / npx) * 4 + (ii >> 3);
-    }
-#endif
+    // (removed alternative: an XCD's columns as 8 x 4 patches of the (x, z) tile grid instead of slabs of whole x rows - the kernel alone -2 %,
+    // inside the step's flat grid +1 ... +8 %: DESIGN.md 4.1d, tools/eft_l2_model.py)
+    const int colx = col % tg.ntx, colz = col / tg.ntx;
     const int X0 = colx * C::TX, Z0 = colz * C::TZ;
     const int nx = min(C::TX, W - X0), nz = min(C::TZ, D - Z0);
     const bool act = (lx < nx) && (lz < nz);
@@ -288,9 +230,6 @@ __device__ __forceinline__ void eft_body(const trx_volumes &vol, const float *__
 #if TRX_EF_STAMP
     unsigned long long ef_stamp[6] = {0, 0, 0, 0, 0, 0}, ef_issue[2] = {0, 0};   // (ef_issue: of a tile step's request phase, the origin of the next tile / yn + eight target rows; the rest is the DMA pieces)
     const unsigned long long ef_t0 = __builtin_amdgcn_s_memtime();
-#endif
-#if TRX_EF_PRIO
-    const int ef_second = (int)((blockIdx.y * gridDim.x + blockIdx.x) * 2 >= gridDim.x * gridDim.y);
 #endif
     int w4_s, hw4_s;   // row / plane pitch of the volume in bytes, pinned in SGPRs (v_mad_u32_u24 operands)
     asm("s_mov_b32 %0, %1" : "=s"(w4_s) : "s"(W * 4));
@@ -351,8 +290,8 @@ __device__ __forceinline__ void eft_body(const trx_volumes &vol, const float *__
 #pragma unroll
         for (int h = 0; h < 2; h++) {
             const int r = tid + h * C::Threads, iy = r & (C::NY - 1), iz = r >> 5;
-            // E = dword index of (x = 0) of this row inside a buffer; rows nobody touches point at granule 0 (never read)
-            tab[iz * C::TP + iy] = (pre_r[h] * 4 - wlo_r[h]) * (1 << kTabShift);
+            // E = byte offset of (x = 0) of this row inside a buffer; rows nobody touches point at granule 0 (never read)
+            tab[iz * C::TP + iy] = (pre_r[h] * 4 - wlo_r[h]) * 4;
             for (int k = 0; k < cnt_r[h]; k++) desc[pre_r[h] + k] = (iz << 20) | (iy << 12) | ((wlo_r[h] + 4 * k - dm.xmin) << 2);
         }
     }
@@ -423,23 +362,8 @@ __device__ __forceinline__ void eft_body(const trx_volumes &vol, const float *__
         // sits at byte 16 g of the buffer: the 64 lanes of a wave write 1 KB of consecutive LDS per k, which is exactly what the DMA does
         // (LDS address = M0 + 16 lane), while every lane brings its own global address (any 4-byte alignment).  All K pieces of a tile are
         // issued at once, a whole tile ahead of their use.  Boundary tiles: granules outside the volume are not fetched (exec mask) but
-        // zero-filled with ds_write here and now - the target buffer is idle; one that straddles a face in x is patched element by element
-        // (rare, behind a wave-uniform test).
-        unsigned fixbits = 0;   // (TRX_EF_PARTFIX) per granule slot k of this thread, four bits: the elements of the tile in flight to zero once it has landed
-        [[maybe_unused]] const unsigned vol_last16 = (unsigned)D * (unsigned)H * (unsigned)W * 4u - 16u;
-        auto fix_tile = [&](int buf) {   // (after the wait for the tile, before the barrier that hands it to the gather)
-            if (__builtin_amdgcn_ballot_w64(fixbits != 0) == 0) return;
-#pragma unroll
-            for (int k = 0; k < K; k++) {
-                const unsigned m = (fixbits >> (4 * k)) & 15u;
-                float *p = lds + buf * C::BufFloats + (tid + k * C::Threads) * 4;
-                if (m & 1u) p[0] = 0.f;
-                if (m & 2u) p[1] = 0.f;
-                if (m & 4u) p[2] = 0.f;
-                if (m & 8u) p[3] = 0.f;
-            }
-            fixbits = 0;
-        };
+        // zero-filled with ds_write here and now - the target buffer is idle; one that straddles a face in x is filled element by element
+        // with ordinary loads (removed alternative: fetched by the DMA and patched in LDS after landing, -0.5 %: profiles/r05c_eft_item_timeline.txt).
         auto issue_tile = [&](const TileOrg &o, int buf) {
             const char *bs = uni_ptr(o.base);
 #pragma unroll
@@ -455,21 +379,7 @@ __device__ __forceinline__ void eft_body(const trx_volumes &vol, const float *__
                     const bool full = rowin && (gx >= 0) && (gx + 3 < W);
                     const bool part = rowin && !full && (gx + 3 >= 0) && (gx < W);
                     off = (unsigned)((int)off + o.dP);
-#if TRX_EF_PARTFIX
-                    // A granule that straddles a face in x and whose 16 bytes lie inside this pair's volume (all but the left overhang of the first row and the
-                    // right one of the last) is fetched by the DMA like a full one - it brings the neighbouring row's elements along - and the elements
-                    // outside the row are zeroed in LDS once the tile has landed (fix_tile).  Element by element with ordinary loads, as below, every such
-                    // granule cost the wave a wait for EVERYTHING it had in flight: the dearest tenth of the items spent 7.1 k ticks per tile requesting
-                    // the next one against 4.1 k on average (profiles/r05c_eft_item_timeline.txt).
-                    const bool dma_part = fetch && part && off <= vol_last16;
-                    if (dma_part) {
-                        const int lo = max(0, -gx), hi = min(4, W - gx);   // elements [lo, hi) are inside the row
-                        fixbits |= (unsigned)(~(((1 << hi) - 1) & ~((1 << lo) - 1)) & 15) << (4 * k);
-                    }
-#else
-                    const bool dma_part = false;
-#endif
-                    if (fetch && !full && !dma_part) {
+                    if (fetch && !full) {
                         f4 v = (f4)(0.f);
                         if (part) {
                             const float *row = mov + ((size_t)gz * H + gy) * W;
@@ -480,7 +390,7 @@ __device__ __forceinline__ void eft_body(const trx_volumes &vol, const float *__
                         }
                         *reinterpret_cast<f4 *>(lds + buf * C::BufFloats + g * 4) = v;
                     }
-                    fetch = fetch && (full || dma_part);
+                    fetch = fetch && full;
                 }
                 if (TRX_EF_DBG & 1) continue;
                 const unsigned long long mk = __builtin_amdgcn_ballot_w64(fetch);
@@ -513,12 +423,10 @@ __device__ __forceinline__ void eft_body(const trx_volumes &vol, const float *__
             if (TRX_EF_DBG & 2) { tvj = 1.f; return; }
             asm volatile("global_load_dword %0, %1, %2" TRX_TGT_POLICY : "=v"(tvj) : "v"(toffb), "s"(trow) : "memory");
         };
-#if TRX_EF_ROWSTEP
         // per-row steps of the row terms (wave-uniform): yn advances by dyn per row, the un-normalised y by H / 2 * dyn (= 1 up to rounding)
         const float dyn_s = uni(H > 1 ? ytab[1] - ytab[0] : 0.f);
         const float dpx_s = uni(sx * dyn_s), dpy_s = uni((hH + sy) * dyn_s), dpz_s = uni(sz * dyn_s);
-        const unsigned long long dxy2 = sgpr_pair(dpx_s, dpy_s);   // (V2) per-row step of (x, y)
-#endif
+        const unsigned long long dxy2 = sgpr_pair(dpx_s, dpy_s);   // per-row step of (x, y)
         // ---- gather of rows [ja, jb) of tile `ty` from buffer `buf`
         auto gather_rows = [&](int ty, const TileOrg &o, int buf, float yn_l, float (&tv)[kRows], int ja, int jb, bool more) {
             if (TRX_EF_DBG & 4) {
@@ -531,57 +439,42 @@ __device__ __forceinline__ void eft_body(const trx_volumes &vol, const float *__
             // coordinates relative to the plan's row origin: x to R_x, y / z to R + (dy0, dz0)
             const float bxt = base_x - (float)o.rx, byt = base_y - (float)(o.ry + dm.dy0), bzt = base_z - (float)(o.rz + dm.dz0);
             const int tab_s = (int)lds0 + 2 * C::BufFloats * 4;
-            int tp_s, bufdw_s;   // table pitch and the buffer's dword index inside the LDS array, pinned in SGPRs
+            int tp_s, bufb_s;   // table pitch and the buffer's byte address, pinned in SGPRs
             asm("s_mov_b32 %0, %1" : "=s"(tp_s) : "i"(C::TP));
-            asm("s_mov_b32 %0, %1" : "=s"(bufdw_s) : "s"(kV2 ? (int)lds0 + buf * C::BufFloats * 4 : (int)(lds0 >> 2) + buf * C::BufFloats));   // (V2: in bytes)
+            asm("s_mov_b32 %0, %1" : "=s"(bufb_s) : "s"((int)lds0 + buf * C::BufFloats * 4));
             struct S1 { int e00, e01, e10, e11, xi; float fx, fy, fz; };
             struct S2 { f2 r00, r01, r10, r11; float fx, fy, fz; };
-#if TRX_EF_ROWSTEP
             // Row terms by STEPPING (round 5): the row term of row ja comes from its lane (three v_readlane per call of four rows), rows ja + 1 ..
             // add the per-row step - yn is an arithmetic progression in the row index up to one fp32 ulp (ATen's linspace table), i.e. up to
             // ~1e-5 voxels over a tile, below the fp32 resolution of the coordinates themselves; this kernel only runs rotated poses, where no
             // sample sits on the lattice by construction.  Per voxel: three adds instead of three v_readlane (4.5 cycles each) + three adds.
-            float ixr = bxt + lane_bcast(px_l, ja), iyr = byt + lane_bcast(py_l, ja), izr = bzt + lane_bcast(pz_l, ja);
+            // The row table holds BYTE offsets, so that the four data addresses of a voxel are plain v_add_u32 (2.6 cycles) instead of
+            // v_add_lshl_u32 (5.0), and (x, y) step per row by one v_pk_add with a scalar pair (profiles/r05a_mfma_coissue_and_op_costs.txt).
+            // Removed alternatives: a dword-index table, and the row terms by one v_readlane per row (6 % more vector cycles: DESIGN.md 4.1d).
+            const float ixr = bxt + lane_bcast(px_l, ja), iyr = byt + lane_bcast(py_l, ja);
+            float izr = bzt + lane_bcast(pz_l, ja);
             float ynr = lane_bcast(yn_l, ja);
-            f2 xyr = {ixr, iyr};   // (V2)
-            auto stage1 = [&](int j) -> S1 {
-                float ix, iy, iz = izr;
-                if constexpr (kV2) {
-                    ix = xyr.x; iy = xyr.y;
-                    asm("v_pk_add_f32 %0, %1, %2" : "=v"(xyr) : "v"(xyr), "s"(dxy2));
-                } else {
-                    ix = ixr; iy = iyr;
-                    ixr += dpx_s; iyr += dpy_s;
-                }
+            f2 xyr = {ixr, iyr};
+            auto stage1 = [&]() -> S1 {
+                const float ix = xyr.x, iy = xyr.y, iz = izr;
+                asm("v_pk_add_f32 %0, %1, %2" : "=v"(xyr) : "v"(xyr), "s"(dxy2));
                 izr += dpz_s;
-#else
-            auto stage1 = [&](int j) -> S1 {
-                const float ix = bxt + lane_bcast(px_l, j), iy = byt + lane_bcast(py_l, j), iz = bzt + lane_bcast(pz_l, j);
-#endif
                 int t, ta;
                 asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(t) : "v"(floor_to_int(iz)), "s"(tp_s), "v"(floor_to_int(iy)));
                 asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(ta) : "v"(t), "s"(tab_s));
                 S1 s;
                 const i2u ea = *(lds_i2)(unsigned)ta, eb = *(lds_i2)(unsigned)(ta + C::TP * 4);
                 s.e00 = ea.x; s.e01 = ea.y; s.e10 = eb.x; s.e11 = eb.y;
-                if constexpr (kV2) asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(s.xi) : "v"(floor_to_int(ix)), "s"(bufdw_s));   // byte address of x inside this buffer, before the row's E
-                else asm("v_add_u32 %0, %1, %2" : "=v"(s.xi) : "s"(bufdw_s), "v"(floor_to_int(ix)));   // dword index of x inside this buffer, before the row's E
+                asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(s.xi) : "v"(floor_to_int(ix)), "s"(bufb_s));   // byte address of x inside this buffer, before the row's E
                 s.fx = __builtin_amdgcn_fractf(ix); s.fy = __builtin_amdgcn_fractf(iy); s.fz = __builtin_amdgcn_fractf(iz);
                 return s;
             };
             auto stage2 = [&](const S1 &s) -> S2 {
                 int a00, a01, a10, a11;
-                if constexpr (kV2) {
-                    asm("v_add_u32 %0, %1, %2" : "=v"(a00) : "v"(s.xi), "v"(s.e00));
-                    asm("v_add_u32 %0, %1, %2" : "=v"(a01) : "v"(s.xi), "v"(s.e01));
-                    asm("v_add_u32 %0, %1, %2" : "=v"(a10) : "v"(s.xi), "v"(s.e10));
-                    asm("v_add_u32 %0, %1, %2" : "=v"(a11) : "v"(s.xi), "v"(s.e11));
-                } else {
-                    asm("v_add_lshl_u32 %0, %1, %2, 2" : "=v"(a00) : "v"(s.xi), "v"(s.e00));
-                    asm("v_add_lshl_u32 %0, %1, %2, 2" : "=v"(a01) : "v"(s.xi), "v"(s.e01));
-                    asm("v_add_lshl_u32 %0, %1, %2, 2" : "=v"(a10) : "v"(s.xi), "v"(s.e10));
-                    asm("v_add_lshl_u32 %0, %1, %2, 2" : "=v"(a11) : "v"(s.xi), "v"(s.e11));
-                }
+                asm("v_add_u32 %0, %1, %2" : "=v"(a00) : "v"(s.xi), "v"(s.e00));
+                asm("v_add_u32 %0, %1, %2" : "=v"(a01) : "v"(s.xi), "v"(s.e01));
+                asm("v_add_u32 %0, %1, %2" : "=v"(a10) : "v"(s.xi), "v"(s.e10));
+                asm("v_add_u32 %0, %1, %2" : "=v"(a11) : "v"(s.xi), "v"(s.e11));
                 S2 f;
                 f.r00 = *(lds_f2)(unsigned)a00; f.r01 = *(lds_f2)(unsigned)a01;
                 f.r10 = *(lds_f2)(unsigned)a10; f.r11 = *(lds_f2)(unsigned)a11;
@@ -593,48 +486,20 @@ __device__ __forceinline__ void eft_body(const trx_volumes &vol, const float *__
             // two named register sets taken in turns (a conditional `next = ...` made the compiler copy 11 registers per row)
             auto consume = [&](const S2 &f, int j) {
                 const Samp3 sm = lerp3_pairs<kGrad>(f.r00, f.r01, f.r10, f.r11, f.fx, f.fy, f.fz);
-#if TRX_EF_ROWSTEP
                 if (j < je) f1_accumulate_pk<MODE>(sm, tv[j], ynr, acc);   // (uniform: rows of the last, partial tile)
                 ynr += dyn_s;
-#else
-                if (j < je) f1_accumulate_pk<MODE>(sm, tv[j], lane_bcast(yn_l, j), acc);   // (uniform: rows of the last, partial tile)
-#endif
                 if (more) issue_target(ty + 1, j, tv[j]);
             };
             static_assert(kRows / 2 == 4, "four rows per call");
-#if TRX_EF_STAGES == 4   // (measured alternative) the table reads of all four rows of a call first
-            S1 ta = stage1(ja), tb = stage1(ja + 1), tc = stage1(ja + 2), td = stage1(ja + 3);
-            S2 fa = stage2(ta);
-            S2 fb = stage2(tb);
+            // (removed alternative: three or four rows' table reads in flight, -1 % / -3 %: DESIGN.md 4.1d)
+            S2 fa = stage2(stage1());
+            S2 fb = stage2(stage1());
             consume(fa, ja);
-            fa = stage2(tc);
+            fa = stage2(stage1());
             consume(fb, ja + 1);
-            fb = stage2(td);
+            fb = stage2(stage1());
             consume(fa, ja + 2);
             consume(fb, ja + 3);
-#elif TRX_EF_STAGES == 3
-            S1 ta = stage1(ja);
-            S1 tb = stage1(ja + 1);
-            S2 fa = stage2(ta);
-            ta = stage1(ja + 2);
-            S2 fb = stage2(tb);
-            consume(fa, ja);
-            tb = stage1(ja + 3);
-            fa = stage2(ta);
-            consume(fb, ja + 1);
-            fb = stage2(tb);
-            consume(fa, ja + 2);
-            consume(fb, ja + 3);
-#else
-            S2 fa = stage2(stage1(ja));
-            S2 fb = stage2(stage1(ja + 1));
-            consume(fa, ja);
-            fa = stage2(stage1(ja + 2));
-            consume(fb, ja + 1);
-            fb = stage2(stage1(ja + 3));
-            consume(fa, ja + 2);
-            consume(fb, ja + 3);
-#endif
         };
 
         // ---------------- the column walk: tile t gathered from buffer t & 1 while tile t + 1 lands in the other one ----------------
@@ -689,7 +554,6 @@ __device__ __forceinline__ void eft_body(const trx_volumes &vol, const float *__
         TRX_EF_ST2(6);
         if (t0 < t1) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            fix_tile(0);
 #pragma unroll
             for (int j = 0; j < kRows; j++) asm volatile("" : "+v"(tvA[j]));
             asm volatile("" : "+v"(ynA));
@@ -699,10 +563,6 @@ __device__ __forceinline__ void eft_body(const trx_volumes &vol, const float *__
         const unsigned long long ef_first = __builtin_amdgcn_s_memtime() - ef_t0;
 #endif
         auto tile_step = [&](int ty, int par, float (&use)[kRows], float &yn_use, float (&load)[kRows], float &yn_load) {
-#if TRX_EF_PRIO
-            // fair sharing of a CU between its two blocks (see TRX_ZS_PRIO in affine_zstream.h): they take turns at the higher priority in time slices
-            if (((__builtin_amdgcn_s_memtime() >> TRX_EF_PRIO_BIT) + ef_second) & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
-#endif
 #if TRX_EF_STAMP
             const unsigned long long es0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -715,9 +575,6 @@ __device__ __forceinline__ void eft_body(const trx_volumes &vol, const float *__
                     __syncthreads();
                 }
                 nxt = tile_org(ty + 1);
-#if TRX_EF_ISSUE_PRIO
-                __builtin_amdgcn_s_setprio(TRX_EF_ISSUE_PRIO);
-#endif
 #if TRX_EF_STAMP
                 const unsigned long long ei0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -729,9 +586,6 @@ __device__ __forceinline__ void eft_body(const trx_volumes &vol, const float *__
                 ef_issue[0] += ei0 - es0; ef_issue[1] += ei1 - ei0;
 #endif
                 issue_tile(nxt, par ^ 1);
-#if TRX_EF_ISSUE_PRIO
-                __builtin_amdgcn_s_setprio(0);
-#endif
             }
 #if TRX_EF_STAMP
             const unsigned long long es1 = __builtin_amdgcn_s_memtime();
@@ -746,7 +600,6 @@ __device__ __forceinline__ void eft_body(const trx_volumes &vol, const float *__
 #pragma unroll
                 for (int j = 0; j < kRows; j++) asm volatile("" : "+v"(load[j]));
                 asm volatile("" : "+v"(yn_load));
-                fix_tile(par ^ 1);
             }
             cur = nxt;
             __syncthreads();
@@ -775,9 +628,6 @@ __device__ __forceinline__ void eft_body(const trx_volumes &vol, const float *__
             unsigned long long *o = trx_ef_stamps + ((size_t)((by * rows_stride + bx) & 1023) * 8 + wave) * 8;
             o[6] = ef_first; o[7] = ef_walk;
         }
-#endif
-#if TRX_EF_PRIO
-        __builtin_amdgcn_s_setprio(0);
 #endif
     } else {
         // the plan does not fit (dual_choice tests the same numbers, so this is a safety net): every voxel gathers from global memory
@@ -813,11 +663,7 @@ __device__ __forceinline__ void eft_body(const trx_volumes &vol, const float *__
     {
         int tt = tid;   // (re-formed from the thread id: not kept live across the walk)
         asm volatile("" : "+v"(tt));
-#if TRX_EF_SHAPE == 1
-        const int lx2 = (tt & 7) + 8 * (wave & 1), lz2 = ((tt >> 3) & 7) + 8 * ((wave >> 1) & 1);
-#else
         const int lx2 = tt & (C::TX - 1), lz2 = (tt / C::TX) & (C::TZ - 1);
-#endif
         const int xx = X0 + ((lx2 < nx && lz2 < nz) ? lx2 : 0), zz = Z0 + ((lx2 < nx && lz2 < nz) ? lz2 : 0);
         const float xn_e = xtab[xx], zn_e = ztab[zz];
 #pragma unroll

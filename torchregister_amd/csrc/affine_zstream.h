@@ -23,20 +23,8 @@
 #ifndef TRX_ZS_MIN_WAVES
 #define TRX_ZS_MIN_WAVES 4
 #endif
-#ifndef TRX_ZS_V2
-#define TRX_ZS_V2 1   // step kernels: row coordinates and yn products on SGPR PAIRS (one packed instruction per two rows / two components), accumulators
-                      // as (x, y) pairs - an instruction with a scalar-register operand costs a SIMD 4.3 cycles where an all-VGPR one costs 2.5
-                      // (profiles/r05a_mfma_coissue_and_op_costs.txt), so the scalar operand should serve two results; 0 = the round-3 form
-#endif
-#ifndef TRX_ZS_PRIO
-#define TRX_ZS_PRIO 2   // Fair sharing of a CU between its two resident blocks.  The SIMD arbiter serves the OLDER wave first: of the two blocks of a
-                        // CU the one dispatched first ran its 128 steps in 172 us, the other one needed 262 us and spent the last 90 us alone on the
-                        // CU at 2 waves per SIMD (profiles/r05a_zstream_block_timeline.txt).  2 = the block of the launch's second half of the grid
-                        // raises its priority in alternate time slices of 2^TRX_ZS_PRIO_BIT shader cycles (s_memtime), the other one in the
-                        // slices between: end skew 112 -> 44 us, launch -1.5 ... -2 %; 1 = by step parity (measured alternative); 0 = off
-#endif
 #ifndef TRX_ZS_PRIO_BIT
-#define TRX_ZS_PRIO_BIT 14
+#define TRX_ZS_PRIO_BIT 14   // fair sharing of a CU between its two resident blocks: time slices of 2^TRX_ZS_PRIO_BIT shader cycles (see zstream_body)
 #endif
 #ifndef TRX_ZS_STAMP
 #define TRX_ZS_STAMP 0   // development (tools/zbench.hip): per-wave s_memtime sums of the four phases of a step -> trx_zs_stamps
@@ -44,12 +32,12 @@
 #if TRX_ZS_STAMP
 __device__ unsigned long long trx_zs_stamps[512 * 8 * 8];   // [block][wave][wait, barrier, issue, gather, total ticks, steps, realtime start, realtime end]
 #endif
-#ifndef TRX_ZS_LEAD
-#define TRX_ZS_LEAD 1   // steps between the issue of a ring plane and the first step that may touch it (1: one more resident plane, Span = NZ - 1)
-#endif
 
-// Running sums of the z-streaming step body (TRX_ZS_V2): for the weightings q = 1, y, w: Axy = (sum q gx, sum q gy), Bxy = the same times yn,
-// ABz = (sum q gz, sum q gz yn); M01 = (Sy, Sw), M23 = (Syy, Sww), M4 = Syw.
+// Running sums of the z-streaming step body: for the weightings q = 1, y, w: Axy = (sum q gx, sum q gy), Bxy = the same times yn,
+// ABz = (sum q gz, sum q gz yn); M01 = (Sy, Sw), M23 = (Syy, Sww), M4 = Syw.  Row coordinates and yn products come on SGPR PAIRS (one packed
+// instruction per two rows / two components): an instruction with a scalar-register operand costs a SIMD 4.3 cycles where an all-VGPR one
+// costs 2.5 (profiles/r05a_mfma_coissue_and_op_costs.txt), so the scalar operand should serve two results.  (Removed alternative: the
+// round-3 body)
 struct ZAcc {
     f2 Axy[3], Bxy[3], ABz[3], M01, M23;
     float M4;
@@ -95,25 +83,19 @@ struct ZCfg {
     static constexpr int LPP = (PlaneSlots + 15) / 16;                 // lanes per DMA piece: 16 pieces per plane, two per wave
     static constexpr int PlaneFloats = BW * BH, PlaneBytes = PlaneFloats * 4;
     static constexpr int RingFloats = NZ * PlaneFloats;
-    static constexpr int Span = NZ - TRX_ZS_LEAD;                                // source planes a step may touch: [p - Span + 1, p], p = pbase + step
+    static constexpr int Lead = 1;        // steps between the issue of a ring plane and the first step that may touch it (removed alternative, 2: profiles/r05a_zstream_block_timeline.txt)
+    static constexpr int Span = NZ - Lead;   // source planes a step may touch: [p - Span + 1, p], p = pbase + step
     static constexpr int ReduceScratch = Waves * 16 * 65 + Waves * 16;
     static constexpr int Alloc = (RingFloats + 4 > ReduceScratch) ? RingFloats + 4 : ReduceScratch;   // + one float4 the dummy DMAs write
     static_assert(TX % 64 == 0 && Waves % XW == 0 && TY % RG == 0 && BW % 4 == 0 && LPP <= 64 && NZ >= 4 && NZ <= 8 && Span <= 7, "geometry");   // (the slot tables hold eight planes: floor(z) - zlo <= Span - 1 and its upper neighbour <= 7)
 };
 // 64 x 32 voxels per plane, ring of 7 planes of 72 x 40 floats = 80.6 KB: two blocks per CU.  The ring size is not a power of two: the
-// slot of a source plane comes from an 8-entry byte table (v_perm_b32), at the instruction count of a mask.
-#ifndef TRX_ZS_GEOM
-#define TRX_ZS_GEOM 0   // 1: ring of 6 planes of 80 x 42 floats - the same 80.6 KB with 9.7 / 5.4 instead of 1.7 / 3.4 voxels of slack in x / y, one plane less in z:
-                        // measured alternative (profiles/r05a_zs_window_variants.txt: R_z(0.1) joins the window, the identity loses 4 %, a converging run 12 %)
-#endif
-// development (tools/zbench.hip): a FLAT tile - 64 x 16 voxels per plane under a ring of 8 planes of 80 x 30 floats (76.8 KB): 9.7 / 10.7 voxels of slack in
-// x / y and 3.7 planes of tilt, for poses of the convergence basin that the 64 x 32 tile leaves to the deep tile kernel
+// slot of a source plane comes from an 8-entry byte table (v_perm_b32), at the instruction count of a mask.  (Removed alternative: 6 planes of
+// 80 x 42 - R_z(0.1) joins the window, the identity loses 4 %, a converging run 12 %: profiles/r05a_zs_window_variants.txt.)
+// The FLAT tile - 64 x 16 voxels per plane under a ring of 8 planes of 80 x 30 floats (76.8 KB): 9.7 / 10.7 voxels of slack in x / y and 3.7
+// planes of tilt, for poses of the convergence basin that the 64 x 32 tile leaves to the deep tile kernel
 using ZSF = ZCfg<64, 16, 8, 80, 30>;
-#if TRX_ZS_GEOM == 1
-using ZS64 = ZCfg<64, 32, 6, 80, 42>;
-#else
 using ZS64 = ZCfg<64, 32, 7, 72, 40>;
-#endif
 
 struct ZGeom {
     int ntx, nty, nzseg, planes_per_seg, blocks_per_pair;
@@ -229,7 +211,7 @@ __device__ __forceinline__ void zstream_body(const trx_volumes &vol, const float
         ey_r[j] = uni(unnorm<3>(yn, fH) + (hH * (t11 - 1.0f)) * yn);
         sz_r[j] = uni((hD * t21) * yn);
     }
-    constexpr bool kV2 = (TRX_ZS_V2 != 0) && MODE == 0 && (R % 2 == 0);
+    constexpr bool kV2 = MODE == 0 && (R % 2 == 0);   // the SGPR-pair form (ZAcc); the MSE-only step (MODE 4) runs the round-3 form
     unsigned long long sx2[(R + 1) / 2], ey2[(R + 1) / 2], sz2[(R + 1) / 2], yn2[R];   // scalar-register pairs: rows (2k, 2k + 1) of sx / ey / sz, (yn, yn) per row
     if constexpr (kV2) {
 #pragma unroll
@@ -504,25 +486,25 @@ __device__ __forceinline__ void zstream_body(const trx_volumes &vol, const float
         //   D(s+2): ring plane pbase + s + 2 into the slot of plane pbase + s + 2 - NZ, which no step >= s reads
         const ptrdiff_t tstep = (ptrdiff_t)dir * H * W, dstep = (ptrdiff_t)dir * (ptrdiff_t)plane_bytes;
         const float *tnext = tgt + (ptrdiff_t)(zf + dir) * H * W;    // target plane of the next step
-        const char *dnext = plane_ptr(pbase + dir * TRX_ZS_LEAD);     // ring plane TRX_ZS_LEAD steps ahead ...
-        int dslot = pmod(pbase + dir * TRX_ZS_LEAD);                  // ... and its slot
+        const char *dnext = plane_ptr(pbase + dir * C::Lead);     // ring plane C::Lead steps ahead ...
+        int dslot = pmod(pbase + dir * C::Lead);                  // ... and its slot
         auto step = [&](int s, float (&use)[R], float (&load)[R]) {
 #if TRX_ZS_STAMP
             const unsigned long long st0 = __builtin_amdgcn_s_memtime();
             unsigned long long st1 = st0, st2 = st0;
 #endif
-#if TRX_ZS_PRIO == 1
-            if ((s + second_slot) & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
-#elif TRX_ZS_PRIO == 2
+            // Fair sharing of a CU between its two resident blocks.  The SIMD arbiter serves the OLDER wave first: of the two blocks of a CU the one
+            // dispatched first ran its 128 steps in 172 us, the other one needed 262 us and spent the last 90 us alone on the CU at 2 waves per SIMD
+            // (profiles/r05a_zstream_block_timeline.txt).  The block of the launch's second half of the grid raises its priority in alternate time
+            // slices of 2^TRX_ZS_PRIO_BIT shader cycles (s_memtime), the other one in the slices between: end skew 112 -> 44 us, launch -1.5 ... -2 %
+            // (removed alternative: alternating by step parity)
             if (((__builtin_amdgcn_s_memtime() >> TRX_ZS_PRIO_BIT) + second_slot) & 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
-#endif
             if (s > 0) {
                 if ((s & 63) == 0) {   // next chunk of the z tables (compiler-counted loads: the pipeline drains here, once per 64 steps)
                     load_ztab(s);
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 } else if (TRX_ZS_DBG & 16) {
-                } else if (TRX_ZS_LEAD == 2 && s + 1 <= last) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #if TRX_ZS_STAMP
                 st1 = __builtin_amdgcn_s_memtime();
 #endif
@@ -535,8 +517,8 @@ __device__ __forceinline__ void zstream_body(const trx_volumes &vol, const float
 #pragma unroll
             for (int j = 0; j < R; j++) asm volatile("" : "+v"(use[j]));
             if (s + 1 <= last) { issue_targets(tnext, load); tnext += tstep; }
-            if (s + TRX_ZS_LEAD <= last) {
-                issue_plane(pbase + dir * (s + TRX_ZS_LEAD), dslot, dnext);
+            if (s + C::Lead <= last) {
+                issue_plane(pbase + dir * (s + C::Lead), dslot, dnext);
                 dnext += dstep;
                 dslot += dir;
                 dslot = (dslot == C::NZ) ? 0 : (dslot < 0 ? C::NZ - 1 : dslot);
@@ -559,7 +541,7 @@ __device__ __forceinline__ void zstream_body(const trx_volumes &vol, const float
         __syncthreads();   // the ring is zeroed
         // fill the pipeline: the planes steps 0 and 1 touch, the targets of step 0
         {
-            const int ahead = min(last, TRX_ZS_LEAD - 1);
+            const int ahead = min(last, C::Lead - 1);
             const int pa = down ? pbase - ahead : pbase - (C::Span - 1), pb = down ? pbase + (C::Span - 1) : pbase + ahead;
             for (int p = pa; p <= pb; p++) issue_plane(p, pmod(p), plane_ptr(p));
         }
@@ -577,9 +559,7 @@ __device__ __forceinline__ void zstream_body(const trx_volumes &vol, const float
         __syncthreads();   // every wave is done with the ring (it is re-zeroed by the next anchor / becomes the reduction scratch)
     }
 
-#if TRX_ZS_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     if (!ok) {
         if (tid < NP) partials[((size_t)by * rows_per_pair + bx) * NP + tid] = __builtin_nanf("");
         return;

@@ -454,12 +454,9 @@ __device__ __forceinline__ float lerp_corners3(const Corners3 &c, float *d)
 #ifndef TRX_FLOW_DBG
 #define TRX_FLOW_DBG 0
 #endif
-#ifndef TRX_FLOW_NT
-#define TRX_FLOW_NT 7      // bit 0: stores of flow / m / v, bit 1: loads of m / v, bit 2: loads of the target (0: development baseline)
-#endif
-template <typename T> __device__ __forceinline__ void st_stream(T *p, T v) { if constexpr (TRX_FLOW_NT & 1) __builtin_nontemporal_store(v, p); else *p = v; }
-template <typename T> __device__ __forceinline__ T ld_stream(const T *p) { if constexpr (TRX_FLOW_NT & 2) return __builtin_nontemporal_load(p); else return *p; }
-template <typename T> __device__ __forceinline__ T ld_stream4(const T *p) { if constexpr (TRX_FLOW_NT & 4) return __builtin_nontemporal_load(p); else return *p; }
+// (the hints sit on the stores of flow / m / v and the loads of m / v and of the target)
+template <typename T> __device__ __forceinline__ void st_stream(T *p, T v) { __builtin_nontemporal_store(v, p); }
+template <typename T> __device__ __forceinline__ T ld_stream(const T *p) { return __builtin_nontemporal_load(p); }
 
 // Block shape: as wide in x as the rows allow without idle lanes - every stream then moves 1 KB of one row per block and trip (64 x 4
 // blocks moved four 256-byte pieces of four rows: 5 % slower at W = 256) - falling back to narrower blocks when W is not a multiple.
@@ -599,7 +596,7 @@ __global__ __launch_bounds__(TRX_BLOCK, SMOOTH ? 4 : 5) void flow_update3_kernel
         const unsigned dyl = y > 0 ? (unsigned)W : 0u, dyh = y + 1 < H ? (unsigned)W : 0u, dxl = x > 0 ? 1u : 0u, dxh = x + 1 < W ? 1u : 0u;
         const size_t hidx = (size_t)y * W + x;
         unsigned i = cw.i;
-        float fc[3], fm[3] = {0.f, 0.f, 0.f}, tc = ld_stream4(tgt + i);
+        float fc[3], fm[3] = {0.f, 0.f, 0.f}, tc = ld_stream(tgt + i);
 #pragma unroll
         for (int ch = 0; ch < 3; ch++) fc[ch] = fl[ch * (size_t)nvox + i];
         if constexpr (SMOOTH) {   // the plane below the segment's first: the flow itself, the lower slab's plane, or (first plane of the volume) the voxel itself
@@ -653,11 +650,8 @@ __global__ __launch_bounds__(TRX_BLOCK, SMOOTH ? 4 : 5) void flow_update3_kernel
             const unsigned in = i + (z_hi ? HW : 0u);
             float fn[3];
 #pragma unroll
-            for (int ch = 0; ch < 3; ch++) {
-                if constexpr ((TRX_FLOW_NT & 8) && !SMOOTH) fn[ch] = __builtin_nontemporal_load(fl + ch * (size_t)nvox + in);
-                else fn[ch] = fl[ch * (size_t)nvox + in];
-            }
-            const float tn = ld_stream4(tgt + in);
+            for (int ch = 0; ch < 3; ch++) fn[ch] = fl[ch * (size_t)nvox + in];
+            const float tn = ld_stream(tgt + in);
             const Side nxt = load_side(in);   // (the last trip of the volume re-reads its own voxel: harmless, discarded)
             float d[3];
             const float w = lerp_corners3(gc, d);

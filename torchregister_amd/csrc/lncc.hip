@@ -24,24 +24,10 @@
 
 namespace trx {
 
-#ifndef TRX_LNCC_SHARE
-#define TRX_LNCC_SHARE 0
-#endif
-#ifndef TRX_LNCC_RCP
-#define TRX_LNCC_RCP 0
-#endif
-#ifndef TRX_LNCC_DIRECT
-#define TRX_LNCC_DIRECT 1   // round 5: ONE barrier per plane (1: in the builds where it wins - windows 7 and 9 at two blocks per CU; 2: everywhere; 0: nowhere).  The x window is summed in registers straight from the global loads (a thread of the
-                            // x pass loads the 12 consecutive cells of its row as three aligned float4 per input, forms the product fields, slides
-                            // the sums) and only the x sums go to LDS, double-buffered by plane parity - the raw tile, its commit and two of the
-                            // three barriers of a plane are gone.  0: the round 1-4 form (tile -> LDS -> x pass -> LDS -> y pass, three barriers)
-#endif
-#ifndef TRX_LNCC_PREFETCH
-#define TRX_LNCC_PREFETCH 1   // planes of the tile in flight ahead of the window passes (2: measured alternative - +20 registers, 8 x 256^3 w = 5 1818 -> 1932 us, w = 9 2274 -> 2251)
-#endif
-#ifndef TRX_LNCC_TWO_ROWS
-#define TRX_LNCC_TWO_ROWS 1   // 1: a thread owns two y-adjacent outputs (32 x 16 tile per plane); 0: one output (32 x 8 tile) - measured alternative
-#endif
+// Two forms of a plane's window sums.  The DIRECT form (round 5): ONE barrier per plane.  The x window is summed in registers straight from
+// the global loads (a thread of the x pass loads the 12 consecutive cells of its row as three aligned float4 per input, forms the product
+// fields, slides the sums) and only the x sums go to LDS, double-buffered by plane parity - the raw tile, its commit and two of the three
+// barriers of a plane are gone.  The TILE form (rounds 1-4): tile -> LDS -> x pass -> LDS -> y pass, three barriers.
 // Registers: the two-row version takes 140 VGPRs up to w = 5 and 180 for w = 7, 9 (the z ring: 2 x 9 x 5) = two 256-thread blocks per
 // CU; under __launch_bounds__(256, 3) the same code fits 160 without spilling = three blocks.  Measured on one box (256^3, w = 9, loss +
 // gradient): one pair 371 us with two blocks per CU, 336 us with three (six z segments fill 768 slots); eight pairs 2.62 ms with two,
@@ -51,8 +37,8 @@ namespace trx {
 // spills and loses 40 % (profiles/r05a_lncc_direct.txt) - so it is chosen per build: windows 7 / 9 at two blocks per CU, and windows 3 / 5 (whose
 // strip is 8 cells, two of them halo float2s: 102-128 VGPRs at four blocks per CU, 8 x 256^3 w = 5 1817 -> 1750 us).
 template <int R, int MW>
-constexpr bool lncc_direct() { return TRX_LNCC_DIRECT == 2 || (TRX_LNCC_DIRECT == 1 && ((MW == 1 && R >= 3) || R <= 2)); }
-constexpr int kLO = TRX_LNCC_TWO_ROWS ? 2 : 1;      // outputs per thread: rows kLO * (tid >> 5) + o of the tile
+constexpr bool lncc_direct() { return (MW == 1 && R >= 3) || R <= 2; }
+constexpr int kLO = 2;   // outputs per thread: rows kLO * (tid >> 5) + o of a 32 x 16 tile per plane (removed alternative: one output, a 32 x 8 tile - DESIGN.md 4.5)
 constexpr int kLX = 32, kLY = 8 * kLO;      // output tile of a block in x, y
 constexpr int kLRows = kLY + 8, kLCols = kLX + 8;   // tile + halo 4 (the largest radius)
 
@@ -134,16 +120,8 @@ __device__ __forceinline__ void plane_window_sums(const PlaneRegs<NL> &r, Expand
         float v[2 * R + kLO];
 #pragma unroll
         for (int k = 0; k < 2 * R + kLO; k++) v[k] = xs[f][ox][oy + 4 - R + k];
-#if TRX_LNCC_SHARE
-        {   // measured alternative: the second output's window from the first's (two adds instead of 2R + 1; no longer its own fixed-order sum)
-            float s = 0.f;
-#pragma unroll
-            for (int k = 0; k <= 2 * R; k++) s += v[k];
-            P[0][f] = s;
-#pragma unroll
-            for (int o = 1; o < kLO; o++) { s += v[2 * R + o] - v[o - 1]; P[o][f] = s; }
-        }
-#else
+        // (removed alternative: the second output's window from the first's - two adds instead of 2R + 1, no longer its own fixed-order sum -
+        // profiles/r04h_lncc_variants.txt)
 #pragma unroll
         for (int o = 0; o < kLO; o++) {
             float s = 0.f;
@@ -151,11 +129,10 @@ __device__ __forceinline__ void plane_window_sums(const PlaneRegs<NL> &r, Expand
             for (int k = 0; k <= 2 * R; k++) s += v[o + k];
             P[o][f] = s;
         }
-#endif
     }
 }
 
-// ---- the direct form (TRX_LNCC_DIRECT) ----
+// ---- the direct form ----
 // The inputs of one plane for one thread of the x pass: 12 consecutive cells (output quad + halo 4 on both sides) of one tile row, NL inputs.
 template <int NL>
 struct StripRegs {
@@ -283,11 +260,7 @@ __device__ __forceinline__ void column_walk(int nd, int D, int H, int W, int X0,
 #pragma unroll
         for (int f = 0; f < NF; f++) Z[o][f] = 0.f;
     }
-    plane_fetch<NL>(z0 - R, D, H, W, X0, Y0, fetch, regs);
-#if TRX_LNCC_PREFETCH == 2
-    PlaneRegs<NL> regs2;
-    plane_fetch<NL>(z0 - R + 1, D, H, W, X0, Y0, fetch, regs2);
-#endif
+    plane_fetch<NL>(z0 - R, D, H, W, X0, Y0, fetch, regs);   // (removed alternative: two planes in flight - +20 registers, 8 x 256^3 w = 5 1818 -> 1932 us, w = 9 2274 -> 2251)
     for (int base = z0 - R; base < z1 + R; base += WN) {
 #pragma unroll
         for (int k = 0; k < WN; k++) {
@@ -301,20 +274,10 @@ __device__ __forceinline__ void column_walk(int nd, int D, int H, int W, int X0,
                 }
                 if (zin >= 0 && zin < D) {   // uniform
                     PlaneRegs<NL> cur = regs;
-#if TRX_LNCC_PREFETCH == 2
-                    regs = regs2;
-                    plane_fetch<NL>(zin + 2, D, H, W, X0, Y0, fetch, regs2);   // two planes in flight during this plane's passes
-#else
                     plane_fetch<NL>(zin + 1, D, H, W, X0, Y0, fetch, regs);   // next plane in flight during this plane's passes
-#endif
                     plane_window_sums<R, NF, NL>(cur, expand, raw, xs, P);
                 } else {                     // planes outside the volume are zero padding
-#if TRX_LNCC_PREFETCH == 2
-                    regs = regs2;
-                    plane_fetch<NL>(zin + 2, D, H, W, X0, Y0, fetch, regs2);
-#else
                     plane_fetch<NL>(zin + 1, D, H, W, X0, Y0, fetch, regs);
-#endif
 #pragma unroll
                     for (int o = 0; o < kLO; o++)
 #pragma unroll
@@ -417,12 +380,10 @@ __device__ __forceinline__ void column_walk_direct(int nd, int D, int H, int W, 
     }
 }
 
-#ifndef TRX_LNCC_NT
-#define TRX_LNCC_NT 7   // non-temporal hints - bit 0 stores of the fields, bit 1 store of the gradient, bit 2 loads of I, J at the emit of the gradient kernel
-                        // (8 x 256^3: w = 5 1890 -> 1826 us, w = 9 2323 -> 2278; one pair within the noise; profiles/r04h_lncc_variants.txt)
-#endif
-template <int BIT> __device__ __forceinline__ void st_nt(float *p, float v) { if constexpr ((TRX_LNCC_NT >> BIT) & 1) __builtin_nontemporal_store(v, p); else *p = v; }
-template <int BIT> __device__ __forceinline__ float ld_nt(const float *p) { if constexpr ((TRX_LNCC_NT >> BIT) & 1) return __builtin_nontemporal_load(p); else return *p; }
+// non-temporal hints on the stores of the fields, the store of the gradient and the loads of I, J at the emit of the gradient kernel
+// (8 x 256^3: w = 5 1890 -> 1826 us, w = 9 2323 -> 2278; one pair within the noise; profiles/r04h_lncc_variants.txt)
+__device__ __forceinline__ void st_nt(float *p, float v) { __builtin_nontemporal_store(v, p); }
+__device__ __forceinline__ float ld_nt(const float *p) { return __builtin_nontemporal_load(p); }
 template <int R, int MW>
 __global__ __launch_bounds__(TRX_BLOCK, MW) void lncc_fields_kernel(const float *__restrict__ tgt, const float *__restrict__ wrp, int nd, int D, int H,
                                                                int W, int zsplit, float eps, float *__restrict__ fields, float *__restrict__ partials)
@@ -459,16 +420,11 @@ __global__ __launch_bounds__(TRX_BLOCK, MW) void lncc_fields_kernel(const float 
         const float Is = Z[0], Js = Z[1];
         const float c = Z[4] - Is * Js * inv_n, a = Z[2] - Is * Is * inv_n, bv = Z[3] - Js * Js * inv_n;
         const float den = a * bv + eps;
-#if TRX_LNCC_RCP
-        float rden = __builtin_amdgcn_rcpf(den);           // v_rcp_f32 (1 ulp) + one Newton step instead of the ten-instruction IEEE division
-        rden = fmaf(fmaf(-den, rden, 1.0f), rden, rden);
-#else
-        const float rden = 1.0f / den;
-#endif
+        const float rden = 1.0f / den;   // (removed alternative: v_rcp_f32 + one Newton step - profiles/r04h_lncc_variants.txt)
         const float Pq = 2.0f * c * rden, Qq = Pq * c * a * rden;
         lsum += c * c * rden;
         const size_t off = ((size_t)z * H + y + o) * W + x;
-        st_nt<0>(F + off, Pq); st_nt<0>(F + n + off, Qq); st_nt<0>(F + 2 * n + off, (Qq * Js - Pq * Is) * inv_n);
+        st_nt(F + off, Pq); st_nt(F + n + off, Qq); st_nt(F + 2 * n + off, (Qq * Js - Pq * Is) * inv_n);
     };
     if constexpr (kDirect) {
         const float *const src[2] = {I, J};
@@ -520,14 +476,14 @@ __global__ __launch_bounds__(TRX_BLOCK, MW) void lncc_grad_kernel(const float *_
         IJ v = {0.f, 0.f};
         if (x < W && y + o < H) {
             const size_t off = ((size_t)z * H + y + o) * W + x;
-            v.i = ld_nt<2>(I + off); v.j = ld_nt<2>(J + off);
+            v.i = ld_nt(I + off); v.j = ld_nt(J + off);
         }
         return v;
     };
     auto emit = [&](int z, const float (&Z)[3], int o, const IJ &v) {
         if (x >= W || y + o >= H) return;
         const size_t off = ((size_t)z * H + y + o) * W + x;
-        st_nt<1>(G + off, scale * (v.i * Z[0] - v.j * Z[1] + Z[2]));
+        st_nt(G + off, scale * (v.i * Z[0] - v.j * Z[1] + Z[2]));
     };
     if constexpr (kDirect) {
         const float *const src[3] = {F, F + n, F + 2 * n};
@@ -565,7 +521,7 @@ static int lncc_zsplit(int nd, int B, int D, int H, int W, long want)
 }
 // block slots of the register builds: windows 3 and 5 fit four 256-thread blocks per CU (116 / 106 VGPRs under __launch_bounds__(256, 4),
 // no scratch; 4 x 35 KB of LDS), windows 7 and 9 three (the z ring: 2 x 9 x 5 registers) or two
-constexpr long kLnccSlots4 = 1024, kLnccSlots3 = TRX_LNCC_TWO_ROWS ? 768 : 1024;
+constexpr long kLnccSlots4 = 1024, kLnccSlots3 = 768;
 
 template <int R, int MW>
 static int launch_lncc_mw(const float *target, const float *warped, int nd, int B, int D, int H, int W, float alpha, float eps, float *loss, float *grad,
@@ -590,10 +546,10 @@ template <int R>
 static int launch_lncc(const float *target, const float *warped, int nd, int B, int D, int H, int W, float alpha, float eps, float *loss, float *grad,
                        float *fields, float *partials, hipStream_t s)
 {
-    if (TRX_LNCC_TWO_ROWS && R <= 2)   // small windows: the four-blocks-per-CU build, whatever the batch (8 x 256^3: 1024 columns resident in one round)
+    if (R <= 2)   // small windows: the four-blocks-per-CU build, whatever the batch (8 x 256^3: 1024 columns resident in one round)
         return launch_lncc_mw<R, 4>(target, warped, nd, B, D, H, W, alpha, eps, loss, grad, fields, partials, lncc_zsplit(nd, B, D, H, W, kLnccSlots4), s);
     const int zsplit = lncc_zsplit(nd, B, D, H, W, kLnccSlots3);
-    if (TRX_LNCC_TWO_ROWS && R >= 3 && zsplit > 1)   // a small batch of a wide window: the three-blocks-per-CU build (see the note on registers above)
+    if (R >= 3 && zsplit > 1)   // a small batch of a wide window: the three-blocks-per-CU build (see the note on registers above)
         return launch_lncc_mw<R, 3>(target, warped, nd, B, D, H, W, alpha, eps, loss, grad, fields, partials, zsplit, s);
     return launch_lncc_mw<R, 1>(target, warped, nd, B, D, H, W, alpha, eps, loss, grad, fields, partials, zsplit, s);
 }
