@@ -332,7 +332,7 @@ def test_rotated_deep_tile_vs_oracle(eng, shape, tname, loss):
 def test_rotated_deep_tile_is_the_default_from_1024_tiles(eng):
     """From 1024 tiles of 16^3 per launch (five pairs of 96^3: 216 tiles each, every volume >= 128 tiles) GeomRD is offered without any
     flag: the default run equals the flagged run bit for bit and differs from the GeomR run (fp32 summation order) while agreeing with
-    it to 2e-6.  (Smaller launches run the two-body kernel: their steps are launch-bound, see launch_dual.)"""
+    it to 2e-6.  (Smaller launches run the two-body kernel: their steps are launch-bound, see f1_plan.)"""
     from torchregister_amd import _lib
     shape = (96, 96, 96)
     tgt = ph.blobs(shape, 77).cuda().repeat(5, 1, 1, 1, 1)

@@ -1629,29 +1629,6 @@ __global__ __launch_bounds__(ECfg::Threads, 4) void affine_eft_step_kernel(trx_v
     }
 }
 
-// GeomA / GeomR (and the step kernels' extra bodies) per pair in one launch
-template <int MODE>
-static void launch_dual(dim3 grid, hipStream_t s, const trx_volumes &v, const float *theta, const TileGeom &ta, const TileGeom &tr, int channels, float *out,
-                        int zero_surplus = 1, TileGeom td = TileGeom{}, TileGeom trd = TileGeom{}, ZGeom zg = ZGeom{}, int *rows_used = nullptr, int rows_stride = 0,
-                        int eft = 0, const CarryKArgs *carry = nullptr, bool *carry_used = nullptr)
-{
-    // WHICH = 3: the two-body (GeomA / GeomR) instance for launches that offer nothing else - the five-body kernel's entry costs 2-3 us
-    // more (its arguments are fetched in front of the body that needs them), which is what a step of a small volume takes in all
-    // (and no exact-footprint kernel in front: the two-body instance does not read its marks and would run its pairs a second time - ADVICE r4)
-    if (td.blocks_per_pair == 0 && trd.blocks_per_pair == 0 && zg.blocks_per_pair == 0 && rows_stride == 0 && eft == 0) {
-        if constexpr (MODE == 0 || MODE == 4) {
-            if (carry != nullptr && rows_used != nullptr && zero_surplus == 0) {   // the carry form of the same launch (trx_affine_run): theta from the block's own prologue
-                hipLaunchKernelGGL((affine_tile_dual_kernel<MODE, 6>), grid, dim3(512), 0, s, v, theta, ta, tr, channels, out, zero_surplus, td, trd, zg, rows_used, rows_stride, 0, *carry);
-                *carry_used = true;
-                return;
-            }
-        }
-        hipLaunchKernelGGL((affine_tile_dual_kernel<MODE, 3>), grid, dim3(512), 0, s, v, theta, ta, tr, channels, out, zero_surplus, td, trd, zg, rows_used, rows_stride);
-    }
-    else
-        hipLaunchKernelGGL((affine_tile_dual_kernel<MODE, 0>), grid, dim3(512), 0, s, v, theta, ta, tr, channels, out, zero_surplus, td, trd, zg, rows_used, rows_stride, eft);
-}
-
 #pragma clang diagnostic pop
 
 
@@ -2348,15 +2325,10 @@ constexpr int kTargetBlocks = 2048;
 using namespace trx;
 
 // false: the single-geometry kernel only (TRX_FLAG_SINGLE_GEOM); true: GeomA / GeomR (and the step kernels' extra bodies) chosen per pair
-static bool use_dual(const trx_volumes *vol)
-{
-    return !(vol->flags & TRX_FLAG_SINGLE_GEOM);
-}
+static bool use_dual(const trx_volumes *vol) { return !(vol->flags & TRX_FLAG_SINGLE_GEOM); }
 
-// Does a launch of the step kernels offer the z-streaming body to its pairs?  Sizes only (the theta part is zs_fits on the device):
-// the shape must tile, and the launch must fill the chip with blocks of useful length (small problems stay with the tile kernels).
 // Block slots of the device for the 512-thread step kernels: two per CU (LDS and registers allow exactly two) - 512 on MI355X (256 CUs).
-// The size of the flat grid and the yardstick of the offer rules below; queried per launch (the runtime caches device attributes).
+// The size of the flat grid and the yardstick of the offer rules in f1_plan; queried once per launch (the runtime caches device attributes).
 static int persistent_blocks()
 {
     int dev = 0, cus = 0;
@@ -2365,34 +2337,101 @@ static int persistent_blocks()
     return 2 * cus;
 }
 
-static ZGeom zs_launch_geom(const trx_volumes &v)
+// What a launch of the 3-D dual path consists of, decided from sizes and flags alone (f1_plan): launch_f1 launches what it says, the workspace
+// is sized from the same list of geometries, and trx_affine_near_identity asks it which z-streaming tiles a step offers.
+enum DualInstance { kTwoBody = 3, kFiveBody = 0, kBehindZs = 4, kCarry = 6 };   // (the values are affine_tile_dual_kernel's WHICH)
+template <int W> struct Which { static constexpr int value = W; };
+struct F1Plan {
+    TileGeom ta, tr, td, trd, tef;   // the geometries offered to the pairs; blocks_per_pair == 0: not offered (tef: the exact-footprint kernel's 16^3 tiling - GeomRD's)
+    ZGeom zg, zgf;                   // ... the z-streaming body's 64 x 32 tile and its flat tile
+    int rows, slots;                 // partial rows per pair: the row stride the kernels and the finalise get (nblk); block slots of the device = the flat grid
+    bool flat;                       // a flat grid of persistent blocks over a pair-major work list (else the classic grid rows x pairs)
+    bool zs_first, one_kernel;       // the z-streaming body runs as a kernel of its own in front (affine_zs_step_kernel); ... and alone (affine_zs_one_kernel)
+    int eft;                         // the exact-footprint kernel runs in front of the tile kernel: its partial rows per pair (0: it does not)
+    DualInstance dual;               // the instance of affine_tile_dual_kernel that runs behind them
+};
+
+// Every geometry a launch may choose from.  The ONE list: the workspace reserves rows for all of them, a plan offers a subset.
+static F1Plan f1_candidates(const trx_volumes &v)
 {
-    ZGeom none = ZGeom{};
-    if ((v.flags & TRX_FLAG_NO_ZSTREAM) || !zs_shape_ok<ZS64>(v)) return none;
-    const ZGeom g = zs_geom<ZS64>(v);
-    if (v.flags & TRX_FLAG_ZSTREAM) return g;
-    const long zb = (long)g.blocks_per_pair * v.B;
-    if (zb < TRX_ZS_MIN_BLOCKS || g.planes_per_seg < TRX_ZS_MIN_PLANES) return none;
-    // between one block per CU and a full round the streaming blocks share CUs unevenly; where the tile kernels fit ONE round of block
-    // slots they win that case (3 x 192^3: 62 us against 69), everywhere else measured the streaming body is ahead
-    const int slots = persistent_blocks();
-    if (zb > slots / 2 && zb < slots && (long)tile_geom<GeomA>(v).blocks_per_pair * v.B <= slots) return none;
-    return g;
+    F1Plan p = F1Plan{};
+    p.ta = tile_geom<GeomA>(v); p.tr = tile_geom<GeomR>(v); p.td = tile_geom<GeomD>(v); p.trd = p.tef = tile_geom<GeomRD>(v);
+    if (zs_shape_ok<ZS64>(v)) p.zg = zs_geom<ZS64>(v);
+    if (zs_shape_ok<ZSF>(v)) p.zgf = zs_geom<ZSF>(v);
+    return p;
 }
 
-// partial rows per pair that a tile-path launch may write (the dual grid is sized for the geometry with more blocks)
-static size_t tile_rows_per_pair(const trx_volumes &v)
+// partial rows per pair that a launch of these geometries may write (the grid is sized for the geometry with the most blocks)
+static int f1_rows(const F1Plan &p)
 {
-    size_t n = (size_t)tile_geom<GeomA>(v).blocks_per_pair;
-    const size_t r = (size_t)tile_geom<GeomR>(v).blocks_per_pair;
-    const size_t d = (size_t)tile_geom<GeomD>(v).blocks_per_pair, rd = (size_t)tile_geom<GeomRD>(v).blocks_per_pair;
-    size_t z = zs_shape_ok<ZS64>(v) ? (size_t)zs_geom<ZS64>(v).blocks_per_pair : 0;
-    if (zs_shape_ok<ZSF>(v) && (size_t)zs_geom<ZSF>(v).blocks_per_pair > z) z = (size_t)zs_geom<ZSF>(v).blocks_per_pair;
-    if (r > n) n = r;
-    if (d > n) n = d;
-    if (rd > n) n = rd;
-    if (z > n) n = z;
-    return n;
+    return max(max(max(p.ta.blocks_per_pair, p.tr.blocks_per_pair), max(p.td.blocks_per_pair, p.trd.blocks_per_pair)),
+               max(p.tef.blocks_per_pair, max(p.zg.blocks_per_pair, p.zgf.blocks_per_pair)));
+}
+
+// The plan of one launch.  No HIP call, nothing launched.  slots: persistent_blocks().  step: a step kernel (MODE 0 / 4) whose reader knows which
+// rows were written (the step's finalise kernel reads the row count of every pair from rows_used) - every other launch is GeomA / GeomR on the
+// classic grid.  carry: trx_affine_run asks for the carry form.
+static F1Plan f1_plan(const trx_volumes &v, int slots, bool step, bool carry)
+{
+    if (!step) {
+        F1Plan p = F1Plan{tile_geom<GeomA>(v), tile_geom<GeomR>(v)};
+        p.rows = f1_rows(p); p.dual = kTwoBody;
+        return p;
+    }
+    F1Plan p = f1_candidates(v);
+    p.slots = slots;
+    // the deep tile joins the choice only where the reader of the partial rows knows which rows were written (the step's finalise
+    // kernel) and where its 128-row slabs still fill the chip (8192 voxels per tile: big batches)
+    // big batches as before; smaller ones where the deep tiling still fills every block slot with blocks of at least four tiles
+    // (1 or 2 pairs of 256^3: -3 %; never where it would leave slots empty - 2 x 128^3 measured +29 % with it)
+    const long blocks_d = (long)p.td.blocks_per_pair * v.B, slots_d = slots;   // block slots of these 512-thread kernels (MI355X: 512) - the same number the flat grid and the z-streaming / exact-footprint rules use
+    const long rem_d = blocks_d % slots_d;  // a last round that is less than ~60 % full costs more than the deeper tile saves (6 x 256^3: +6 %)
+    const bool small_ok = blocks_d >= slots_d && p.td.tiles_per_seg >= 4 && (rem_d == 0 || rem_d >= slots_d * 5 / 8);
+    if (!(blocks_d >= 2 * slots_d || small_ok || (v.flags & TRX_FLAG_DEEP_TILE))) p.td = TileGeom{};
+    // GeomRD (GeomR's box under a 16 x 16 x 16 tile) joins under the same condition: rotations whose pre-image still fits that box
+    // tiny volumes (<= 64^3: at most 64 of these tiles) stay with GeomR's smaller tiles: measured +5 ... +14 % otherwise; and a launch
+    // of fewer than 1024 of these tiles (one pair up to 128^3) is a step of ~15 us, of which the five-body kernel's entry is 2-3
+    const bool big_rd = p.trd.ntiles >= 128 && (long)p.trd.ntiles * v.B >= 2l * slots;
+    if ((v.flags & TRX_FLAG_NO_ROT_DEEP_TILE) || !(big_rd || (v.flags & TRX_FLAG_DEEP_TILE))) p.trd = TileGeom{};
+    // the z-streaming body: pairs next to the identity (zs_fits on the device) in launches that fill the chip.  Sizes only here: the shape
+    // must tile (f1_candidates), and the launch must fill the chip with blocks of useful length (small problems stay with the tile kernels)
+    if (v.flags & TRX_FLAG_NO_ZSTREAM) p.zg = ZGeom{};
+    else if (p.zg.blocks_per_pair > 0 && !(v.flags & TRX_FLAG_ZSTREAM)) {
+        const long zb = (long)p.zg.blocks_per_pair * v.B;
+        if (zb < TRX_ZS_MIN_BLOCKS || p.zg.planes_per_seg < TRX_ZS_MIN_PLANES) p.zg = ZGeom{};
+        // between one block per CU and a full round the streaming blocks share CUs unevenly; where the tile kernels fit ONE round of block
+        // slots they win that case (3 x 192^3: 62 us against 69), everywhere else measured the streaming body is ahead
+        else if (zb > slots / 2 && zb < slots && (long)p.ta.blocks_per_pair * v.B <= slots) p.zg = ZGeom{};
+    }
+    if (p.zg.blocks_per_pair == 0) p.zgf = ZGeom{};   // (the flat tile belongs to the z-streaming kernel)
+    const TileGeom tef = p.tef;
+    p.tef = TileGeom{};
+    p.rows = f1_rows(p);
+    // big batches of the step kernels: a flat grid of persistent blocks over a pair-major work list (no surplus blocks; see the kernel)
+    // (B <= 64: the flat grid keeps one pair's state per lane)
+    p.flat = v.B <= 64 && (long)p.rows * v.B >= 2 * slots;
+    // the exact-footprint kernel (rotated pairs that GeomR would take) behind launches that fill the chip: columns of at most 64 of its tiles
+    // (sizes: its row / plane pitches are 24-bit multiplier operands, its byte offsets 32-bit)
+    const bool eft_sizes = (long)v.H * v.W * 4 < (1l << 24) && (size_t)v.D * v.H * v.W < ((size_t)1 << 29);
+    if (tef.tiles_per_seg <= 64 && eft_sizes && !(v.flags & TRX_FLAG_NO_EFT) && (p.flat || (v.flags & TRX_FLAG_EFT))) {
+        p.tef = tef;
+        p.eft = tef.blocks_per_pair;   // = the partial rows per pair of that kernel
+        p.rows = f1_rows(p);
+    }
+    // the row stride above counts the flat z-streaming tile wherever its shape fits; the tile handed to the kernels respects TRX_FLAG_NO_ZS_FLAT
+    if (v.flags & TRX_FLAG_NO_ZS_FLAT) p.zgf = ZGeom{};
+    // flat launches that offer the z-streaming body run it as a kernel of its own, FIRST (affine_zs_step_kernel): it alone evaluates the
+    // test, the kernels behind it skip its pairs and return at once when it has taken them all
+    p.zs_first = p.flat && p.zg.blocks_per_pair > 0 && !(v.flags & TRX_FLAG_ZS_FUSED);
+    // the one-kernel form of a step: the streaming kernel also runs the pairs outside its window (GeomR's body), nothing behind it
+    p.one_kernel = p.zs_first && (v.flags & TRX_FLAG_ONE_KERNEL);
+    // the two-body (GeomA / GeomR) instance for launches that offer nothing else - the five-body kernel's entry costs 2-3 us
+    // more (its arguments are fetched in front of the body that needs them), which is what a step of a small volume takes in all
+    // (and no exact-footprint kernel in front: the two-body instance does not read its marks and would run its pairs a second time - ADVICE r4)
+    const bool two_body = !p.flat && p.td.blocks_per_pair == 0 && p.trd.blocks_per_pair == 0 && p.zg.blocks_per_pair == 0 && p.eft == 0;
+    // (the carry form of a step is the two-body launch with theta from the block's own prologue: trx_affine_run)
+    p.dual = p.zs_first ? kBehindZs : !two_body ? kFiveBody : carry ? kCarry : kTwoBody;
+    return p;
 }
 
 // Workspace of the affine entry points: [B][rows][41] partial sums | coordinate tables (callers that pass none) | rows_used[B + 11]
@@ -2405,10 +2444,7 @@ static AffineWs affine_ws(const trx_volumes &v)
     AffineWs w;
     AffineGeom g = affine_geom(v, kTargetBlocks);
     w.rows = (size_t)g.nblk;
-    if (v.ndim == 3) {
-        const size_t t = tile_rows_per_pair(v);
-        if (t > w.rows) w.rows = t;
-    }
+    if (v.ndim == 3) w.rows = max(w.rows, (size_t)f1_rows(f1_candidates(v)));   // whatever a plan offers, its rows fit
     w.off_tab = ((size_t)v.B * w.rows * np_full(3) * sizeof(float) + 255) & ~(size_t)255;
     w.off_rows_used = w.off_tab + (((size_t)(v.W + v.H + v.D) * sizeof(float) + 255) & ~(size_t)255);
     const size_t notes = ((size_t)(v.B + 11) * sizeof(int) + 255) & ~(size_t)255;   // rows_used[B] | pairs left by the z-streaming kernel | its pair mask (2) | the exact-footprint kernel's work tickets, one per XCD (8)
@@ -2436,36 +2472,27 @@ extern "C" size_t trx_affine_workspace_rows_offset(const trx_volumes *vol)
 extern "C" int trx_affine_near_identity(const trx_volumes *vol, const float *theta_host)
 {
     if (check_vol(vol, false) != TRX_OK || !theta_host || vol->ndim != 3) return 0;
-    const ZGeom zg = zs_launch_geom(*vol);
-    if (zg.blocks_per_pair == 0) return 0;
-    const bool flat_ok = zs_shape_ok<ZSF>(*vol) && !(vol->flags & TRX_FLAG_NO_ZS_FLAT);
-    const ZGeom zgf = flat_ok ? zs_geom<ZSF>(*vol) : ZGeom{};
+    const F1Plan p = f1_plan(*vol, persistent_blocks(), true, false);
+    if (p.zg.blocks_per_pair == 0) return 0;
     const float fD = (float)vol->D, fH = (float)vol->H, fW = (float)vol->W;
     for (int b = 0; b < vol->B; b++) {
         const float *th = theta_host + (size_t)b * TRX_PSTRIDE;
-        if (zs_nsub<ZS64>(th, fD, fH, fW, zg.planes_per_seg) > 0) continue;
-        if (flat_ok && zs_nsub<ZSF>(th, fD, fH, fW, zgf.planes_per_seg) > 0) continue;
+        if (zs_nsub<ZS64>(th, fD, fH, fW, p.zg.planes_per_seg) > 0) continue;
+        if (p.zgf.blocks_per_pair > 0 && zs_nsub<ZSF>(th, fD, fH, fW, p.zgf.planes_per_seg) > 0) continue;
         return 0;
     }
     return 1;
 }
 
-static bool use_tile_path(const trx_volumes *vol)
-{
-    if (vol->ndim != 3) return false;
-    return !(vol->flags & TRX_FLAG_GATHER_PATH);   // the un-tiled kernel stays reachable so that the tests can compare the two
-}
+// (TRX_FLAG_GATHER_PATH: the un-tiled kernel stays reachable so that the tests can compare the two)
+static bool use_tile_path(const trx_volumes *vol) { return vol->ndim == 3 && !(vol->flags & TRX_FLAG_GATHER_PATH); }
 
-// MODE 0 / 1 dispatch: LDS-tiled kernel for 3-D, row-walking gather kernel otherwise.
-// Returns the number of partial rows per pair through *nblk.
 struct CarryLaunch {   // trx_affine_run's request for the carry form of a step launch: which parity buffers it writes, the kernel's carry arguments; `used` = it was launched
     int parity;
     CarryKArgs args;
     bool used;
     float *partials_out;   // where the launch wrote its rows (the parity buffer), whether or not the carry form was used
 };
-template <int MODE>
-static int launch_f1(const trx_volumes *vol, const float *theta, float *partials, int *nblk, hipStream_t s, bool dual, const int **rows_used = nullptr, CarryLaunch *cl = nullptr);
 
 template <int MODE>
 static int launch_accum(const trx_volumes *vol, const float *theta, const AffineGeom &g, int channels, size_t chan_stride,
@@ -2480,158 +2507,85 @@ static int launch_accum(const trx_volumes *vol, const float *theta, const Affine
     return TRX_OK;
 }
 
+// GeomA / GeomR (and the step kernels' extra bodies) per pair in one launch: the instance of affine_tile_dual_kernel that the plan names, on the
+// plan's grid.  rows_used == nullptr: the reader of `out` reads every row, so surplus blocks zero theirs.
+template <int MODE>
+static void launch_dual(const F1Plan &p, hipStream_t s, const trx_volumes &v, const float *theta, int channels, float *out, int *rows_used = nullptr,
+                        const CarryKArgs *carry = nullptr)
+{
+    const dim3 grid = p.flat ? dim3(p.slots, 1) : dim3(p.rows, v.B * channels);
+    const int zero_surplus = rows_used == nullptr, rows_stride = p.flat ? p.rows : 0;
+    auto launch = [&](auto which, auto... carry_args) {
+        hipLaunchKernelGGL((affine_tile_dual_kernel<MODE, decltype(which)::value>), grid, dim3(512), 0, s, v, theta, p.ta, p.tr, channels, out, zero_surplus, p.td, p.trd, p.zg,
+                           rows_used, rows_stride, p.eft, carry_args...);
+    };
+    if constexpr (MODE == 0 || MODE == 4)   // (the step kernels)
+        if (p.dual == kCarry) return launch(Which<kCarry>{}, *carry);
+    if constexpr (MODE == 0 || MODE == 1 || MODE == 4)   // (the F1 modes: the warp modes 2 / 3 never run behind a z-streaming kernel)
+        if (p.dual == kBehindZs) return launch(Which<kBehindZs>{});
+    p.dual == kTwoBody ? launch(Which<kTwoBody>{}) : launch(Which<kFiveBody>{});
+}
+
+// MODE 0 / 1 / 4 dispatch: LDS-tiled kernels for 3-D, row-walking gather kernel otherwise.  Returns the number of partial rows per pair through *nblk.
 // rows_used != nullptr: the caller's reduction reads the row count of every pair from the device array returned through it (the
 // step's finalise kernel): surplus blocks of the dual grid then write nothing, and the step kernels may offer their extra bodies.
 template <int MODE>
-static int launch_f1(const trx_volumes *vol, const float *theta, float *partials, int *nblk, hipStream_t s, bool dual, const int **rows_used, CarryLaunch *cl)
+static int launch_f1(const trx_volumes *vol, const float *theta, float *partials, int *nblk, hipStream_t s, const int **rows_used = nullptr, CarryLaunch *cl = nullptr)
 {
     if (rows_used) *rows_used = nullptr;
     if (cl) cl->used = false;
-    if (use_tile_path(vol)) {
-        TileGeom t = tile_geom(*vol);
-        trx_volumes v = *vol;
-        const AffineWs ws = affine_ws(*vol);
-        float *const ws_base = partials;   // (tables and notes sit at fixed offsets from the workspace's start; the rows go to the parity buffer)
-        const bool odd = cl != nullptr && cl->parity != 0;
-        if (odd) partials = (float *)((char *)ws_base + ws.off_part2);
-        if (cl) cl->partials_out = partials;
-        if (!v.xn || !v.yn || !v.zn) {
-            // tables live behind the partials (trx_affine_workspace_bytes reserves the room)
-            float *tab = (float *)((char *)ws_base + ws.off_tab);
-            const int n = max(v.W, max(v.H, v.D));
-            hipLaunchKernelGGL(fill_tables_kernel, dim3((n + 255) / 256), dim3(256), 0, s, tab, v.W, v.H, v.D);
-            TRX_CHECK_LAUNCH();
-            v.xn = tab; v.yn = tab + v.W; v.zn = tab + v.W + v.H;
+    if (!use_tile_path(vol)) {
+        if constexpr (MODE == 4) return TRX_ERR_ARG;   // (the MSE-only rows exist in the tile kernels only; trx_affine_step asks for them on the tile path)
+        else {
+            AffineGeom g = affine_geom(*vol, kTargetBlocks);
+            *nblk = g.nblk;
+            return launch_accum<MODE>(vol, theta, g, 1, 0, partials, s);
         }
-        if (dual && use_dual(vol)) {
-            const TileGeom ta = tile_geom<GeomA>(*vol), tr = tile_geom<GeomR>(*vol);
-            const int gx = ta.blocks_per_pair > tr.blocks_per_pair ? ta.blocks_per_pair : tr.blocks_per_pair;
-            const bool aware = rows_used != nullptr;
-            const bool step_kernel = aware && (MODE == 0 || MODE == 4);
-            // the deep tile joins the choice only where the reader of the partial rows knows which rows were written (the step's finalise
-            // kernel) and where its 128-row slabs still fill the chip (8192 voxels per tile: big batches)
-            TileGeom td = TileGeom{};
-            if (step_kernel) {
-                const TileGeom cand = tile_geom<GeomD>(*vol);
-                // big batches as before; smaller ones where the deep tiling still fills every block slot with blocks of at least four tiles
-                // (1 or 2 pairs of 256^3: -3 %; never where it would leave slots empty - 2 x 128^3 measured +29 % with it)
-                const long blocks_d = (long)cand.blocks_per_pair * vol->B;
-                const long slots_d = persistent_blocks();   // block slots of these 512-thread kernels (MI355X: 512) - the same number the flat grid and the z-streaming / exact-footprint rules use
-                const long rem_d = blocks_d % slots_d;  // a last round that is less than ~60 % full costs more than the deeper tile saves (6 x 256^3: +6 %)
-                const bool small_ok = blocks_d >= slots_d && cand.tiles_per_seg >= 4 && (rem_d == 0 || rem_d >= slots_d * 5 / 8);
-                if (blocks_d >= 2 * slots_d || small_ok || (vol->flags & TRX_FLAG_DEEP_TILE)) td = cand;
-            }
-            // GeomRD (GeomR's box under a 16 x 16 x 16 tile) joins under the same condition: rotations whose pre-image still fits that box
-            TileGeom trd = TileGeom{};
-            if (step_kernel && !(vol->flags & TRX_FLAG_NO_ROT_DEEP_TILE)) {
-                const TileGeom cand = tile_geom<GeomRD>(*vol);
-                // tiny volumes (<= 64^3: at most 64 of these tiles) stay with GeomR's smaller tiles: measured +5 ... +14 % otherwise; and a launch
-                // of fewer than 1024 of these tiles (one pair up to 128^3) is a step of ~15 us, of which the five-body kernel's entry is 2-3
-                if ((cand.ntiles >= 128 && (long)cand.ntiles * vol->B >= 2l * persistent_blocks()) || (vol->flags & TRX_FLAG_DEEP_TILE)) trd = cand;
-            }
-            // the z-streaming body: pairs next to the identity (zs_fits) in launches that fill the chip
-            ZGeom zg = ZGeom{};
-            if (step_kernel) zg = zs_launch_geom(*vol);
-            int gxx = gx;
-            if (td.blocks_per_pair > gxx) gxx = td.blocks_per_pair;
-            if (trd.blocks_per_pair > gxx) gxx = trd.blocks_per_pair;
-            if (zg.blocks_per_pair > gxx) gxx = zg.blocks_per_pair;
-            if (zg.blocks_per_pair > 0 && zs_shape_ok<ZSF>(*vol) && zs_geom<ZSF>(*vol).blocks_per_pair > gxx) gxx = zs_geom<ZSF>(*vol).blocks_per_pair;
-            int *ru = aware ? (int *)((char *)ws_base + (odd ? ws.off_rows_used2 : ws.off_rows_used)) : nullptr;
-            // big batches of the step kernels: a flat grid of persistent blocks over a pair-major work list (no surplus blocks; see the kernel)
-            const int slots = persistent_blocks();
-            // (B <= 64: the flat grid keeps one pair's state per lane)
-            const bool flat = step_kernel && vol->B <= 64 && (long)gxx * vol->B >= 2 * slots;
-            // the exact-footprint kernel (rotated pairs that GeomR would take) behind launches that fill the chip: columns of at most 64 of its tiles
-            const TileGeom tef = tile_geom<GeomRD>(*vol);   // (its 16^3 tiling is GeomRD's)
-            // (sizes: its row / plane pitches are 24-bit multiplier operands, its byte offsets 32-bit)
-            const bool eft_sizes = (long)vol->H * vol->W * 4 < (1l << 24) && (size_t)vol->D * vol->H * vol->W < ((size_t)1 << 29);
-            const int eft = (step_kernel && ru && tef.tiles_per_seg <= 64 && eft_sizes && !(vol->flags & TRX_FLAG_NO_EFT) &&
-                             (flat || (vol->flags & TRX_FLAG_EFT))) ? tef.blocks_per_pair : 0;   // = the partial rows per pair of that kernel
-            if (eft && tef.blocks_per_pair > gxx) gxx = tef.blocks_per_pair;
-            // flat launches that offer the z-streaming body run it as a kernel of its own, FIRST (affine_zs_step_kernel): it alone evaluates the
-            // test, the kernels behind it skip its pairs and return at once when it has taken them all
-            const bool zs_first = flat && zg.blocks_per_pair > 0 && ru != nullptr && !(vol->flags & TRX_FLAG_ZS_FUSED);
-            if constexpr (MODE == 0 || MODE == 4) {
-                if (zs_first) {
-                    const ZGeom zgf = (zs_shape_ok<ZSF>(*vol) && !(vol->flags & TRX_FLAG_NO_ZS_FLAT)) ? zs_geom<ZSF>(*vol) : ZGeom{};
-                    if (vol->flags & TRX_FLAG_ONE_KERNEL) {
-                        // the one-kernel form of a step: the streaming kernel also runs the pairs outside its window (GeomR's body), nothing behind it
-                        hipLaunchKernelGGL((affine_zs_one_kernel<MODE>), dim3(slots, 1), dim3(ZS64::Threads), 0, s, v, theta, zg, zgf, partials, ru, gxx, tr);
-                        TRX_CHECK_LAUNCH();
-                        *nblk = gxx;
-                        *rows_used = ru;
-                        return TRX_OK;
-                    }
-                    hipLaunchKernelGGL((affine_zs_step_kernel<MODE>), dim3(slots, 1), dim3(ZS64::Threads), 0, s, v, theta, zg, zgf, partials, ru, gxx);
-                    TRX_CHECK_LAUNCH();
-                }
-                if (eft) {   // in front of the tile kernel: takes its pairs and marks them rows_used < 0 (none - the usual case next to the identity - costs ~3 us, ~1.5 behind the z-streaming kernel)
-                    const int wd = td.blocks_per_pair > 0, wrd = trd.blocks_per_pair > 0, zp = zs_first ? -1 : (zg.blocks_per_pair > 0 ? zg.planes_per_seg : 0);   // (-1: the z-streaming kernel ran in front)
-                    if (flat) hipLaunchKernelGGL((affine_eft_step_kernel<MODE>), dim3(slots, 1), dim3(ECfg::Threads), 0, s, v, theta, tef, partials, ru, gxx, wd, wrd, zp);
-                    else hipLaunchKernelGGL((affine_eft_step_kernel<MODE>), dim3(tef.blocks_per_pair, vol->B), dim3(ECfg::Threads), 0, s, v, theta, tef, partials, ru, -gxx, wd, wrd, zp);
-                    TRX_CHECK_LAUNCH();
-                }
-            }
-            if (zs_first) hipLaunchKernelGGL((affine_tile_dual_kernel<MODE, 4>), dim3(slots, 1), dim3(512), 0, s, v, theta, ta, tr, 1, partials, 0, td, trd, zg, ru, gxx, eft);
-            else if (flat) launch_dual<MODE>(dim3(slots, 1), s, v, theta, ta, tr, 1, partials, 0, td, trd, zg, ru, gxx, eft);
-            else launch_dual<MODE>(dim3(gxx, vol->B), s, v, theta, ta, tr, 1, partials, aware ? 0 : 1, td, trd, zg, ru, 0, eft, cl ? &cl->args : nullptr, cl ? &cl->used : nullptr);
-            TRX_CHECK_LAUNCH();
-            *nblk = gxx;
-            if (aware) *rows_used = ru;
-            return TRX_OK;
-        }
+    }
+    trx_volumes v = *vol;
+    const AffineWs ws = affine_ws(*vol);
+    float *const ws_base = partials;   // (tables and notes sit at fixed offsets from the workspace's start; the rows go to the parity buffer)
+    const bool odd = cl != nullptr && cl->parity != 0;
+    if (odd) partials = (float *)((char *)ws_base + ws.off_part2);
+    if (cl) cl->partials_out = partials;
+    if (!v.xn || !v.yn || !v.zn) {
+        // tables live behind the partials (trx_affine_workspace_bytes reserves the room)
+        float *tab = (float *)((char *)ws_base + ws.off_tab);
+        const int n = max(v.W, max(v.H, v.D));
+        hipLaunchKernelGGL(fill_tables_kernel, dim3((n + 255) / 256), dim3(256), 0, s, tab, v.W, v.H, v.D);
+        TRX_CHECK_LAUNCH();
+        v.xn = tab; v.yn = tab + v.W; v.zn = tab + v.W + v.H;
+    }
+    if (!use_dual(vol)) {
+        const TileGeom t = tile_geom(*vol);
         hipLaunchKernelGGL((affine_tile_kernel<MODE>), dim3(t.blocks_per_pair, vol->B), dim3(kTileThreads), 0, s, v, theta, t, 1, partials);
         TRX_CHECK_LAUNCH();
         *nblk = t.blocks_per_pair;
         return TRX_OK;
     }
-    if constexpr (MODE == 4) {
-        return TRX_ERR_ARG;   // (the MSE-only rows exist in the tile kernels only; trx_affine_step asks for them on the tile path)
-    } else {
-        AffineGeom g = affine_geom(*vol, kTargetBlocks);
-        *nblk = g.nblk;
-        return launch_accum<MODE>(vol, theta, g, 1, 0, partials, s);
+    int *const ru = rows_used ? (int *)((char *)ws_base + (odd ? ws.off_rows_used2 : ws.off_rows_used)) : nullptr;
+    const F1Plan p = f1_plan(*vol, persistent_blocks(), ru != nullptr && (MODE == 0 || MODE == 4), cl != nullptr);
+    if constexpr (MODE == 0 || MODE == 4) {
+        if (p.one_kernel) hipLaunchKernelGGL((affine_zs_one_kernel<MODE>), dim3(p.slots, 1), dim3(ZS64::Threads), 0, s, v, theta, p.zg, p.zgf, partials, ru, p.rows, p.tr);
+        else {
+            if (p.zs_first) {
+                hipLaunchKernelGGL((affine_zs_step_kernel<MODE>), dim3(p.slots, 1), dim3(ZS64::Threads), 0, s, v, theta, p.zg, p.zgf, partials, ru, p.rows);
+                TRX_CHECK_LAUNCH();
+            }
+            if (p.eft) {   // in front of the tile kernel: takes its pairs and marks them rows_used < 0 (none - the usual case next to the identity - costs ~3 us, ~1.5 behind the z-streaming kernel)
+                const int wd = p.td.blocks_per_pair > 0, wrd = p.trd.blocks_per_pair > 0, zp = p.zs_first ? -1 : (p.zg.blocks_per_pair > 0 ? p.zg.planes_per_seg : 0);   // (-1: the z-streaming kernel ran in front)
+                if (p.flat) hipLaunchKernelGGL((affine_eft_step_kernel<MODE>), dim3(p.slots, 1), dim3(ECfg::Threads), 0, s, v, theta, p.tef, partials, ru, p.rows, wd, wrd, zp);
+                else hipLaunchKernelGGL((affine_eft_step_kernel<MODE>), dim3(p.tef.blocks_per_pair, vol->B), dim3(ECfg::Threads), 0, s, v, theta, p.tef, partials, ru, -p.rows, wd, wrd, zp);
+                TRX_CHECK_LAUNCH();
+            }
+        }
     }
-}
-
-static int launch_finalize(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt, const trx_affine_state *st, const float *partials, int nblk,
-                           const int *rows_used, bool mse_only, const float *state_in, hipStream_t s);
-
-extern "C" int trx_affine_step(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt,
-                               const trx_affine_state *st, void *workspace, size_t workspace_bytes, void *stream)
-{
-    int rc = check_vol(vol, true);
-    if (rc) return rc;
-    if (!loss || !opt || !st || !workspace) return TRX_ERR_ARG;
-    if (!st->param || !st->theta || !st->best_theta || !st->best_loss || !st->best_idx || !st->step) return TRX_ERR_ARG;
-    if (opt->kind != TRX_OPT_SGD && opt->kind != TRX_OPT_ADAM) return TRX_ERR_ARG;
-    if (opt->kind == TRX_OPT_ADAM && (!st->adam_m || !st->adam_v)) return TRX_ERR_ARG;
-    if (st->mode != TRX_PARAM_AFFINE && st->mode != TRX_PARAM_RIGID) return TRX_ERR_ARG;
-    if (workspace_bytes < trx_affine_workspace_bytes(vol)) return TRX_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    float *partials = (float *)workspace;
-    int nblk = 0;
-    // Every step picks GeomA / GeomR per pair in the kernel (TRX_FLAG_SINGLE_GEOM: the primary geometry only).  Rigid runs start from a
-    // random pose (reference: torch.rand, up to 1 rad) and live at large rotations; affine runs start at the identity, where the
-    // GeomA body is all that runs, but may rotate away from it: the single-geometry kernel then gathers from L2 at 3.2x the cost.
-    const int *rows_used = nullptr;
-    // without an NCC term only d = warped - target matters: the step kernel then keeps 13 sums instead of 41 (3-D tile path)
-    const bool mse_only = (loss->w_ncc == 0.f) && use_tile_path(vol);
-    rc = mse_only ? launch_f1<4>(vol, st->theta, partials, &nblk, s, true, &rows_used) : launch_f1<0>(vol, st->theta, partials, &nblk, s, true, &rows_used);
-    if (rc) return rc;
-    return launch_finalize(vol, loss, opt, st, partials, nblk, rows_used, mse_only, nullptr, s);
-}
-
-extern "C" int trx_affine_accumulate(const trx_volumes *vol, const float *theta, void *workspace, size_t workspace_bytes, void *stream)
-{
-    int rc = check_vol(vol, true);
-    if (rc) return rc;
-    if (!theta || !workspace) return TRX_ERR_ARG;
-    if (workspace_bytes < trx_affine_workspace_bytes(vol)) return TRX_ERR_WORKSPACE;
-    int nblk = 0;
-    const int *rows_used = nullptr;
-    return launch_f1<0>(vol, theta, (float *)workspace, &nblk, (hipStream_t)stream, true, &rows_used);   // exactly the launch of a step (profiling aid)
+    if (!p.one_kernel) launch_dual<MODE>(p, s, v, theta, 1, partials, ru, cl ? &cl->args : nullptr);
+    TRX_CHECK_LAUNCH();
+    if (cl) cl->used = p.dual == kCarry;
+    *nblk = p.rows;
+    if (rows_used) *rows_used = ru;
+    return TRX_OK;
 }
 
 // The finalise kernel behind a step launch (trx_affine_step, and the flush behind the last carry launch of trx_affine_run: state_in = its carry buffer)
@@ -2649,6 +2603,59 @@ static int launch_finalize(const trx_volumes *vol, const trx_loss_cfg *loss, con
     return TRX_OK;
 }
 
+// The arguments of a step: what trx_affine_step refuses, and what the carry form of trx_affine_run needs to hold before it launches anything
+static int check_step_args(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt, const trx_affine_state *st, const void *workspace, size_t workspace_bytes)
+{
+    int rc = check_vol(vol, true);
+    if (rc) return rc;
+    if (!loss || !opt || !st || !workspace) return TRX_ERR_ARG;
+    if (!st->param || !st->theta || !st->best_theta || !st->best_loss || !st->best_idx || !st->step) return TRX_ERR_ARG;
+    if (opt->kind != TRX_OPT_SGD && opt->kind != TRX_OPT_ADAM) return TRX_ERR_ARG;
+    if (opt->kind == TRX_OPT_ADAM && (!st->adam_m || !st->adam_v)) return TRX_ERR_ARG;
+    if (st->mode != TRX_PARAM_AFFINE && st->mode != TRX_PARAM_RIGID) return TRX_ERR_ARG;
+    if (workspace_bytes < trx_affine_workspace_bytes(vol)) return TRX_ERR_WORKSPACE;
+    return TRX_OK;
+}
+
+// without an NCC term only d = warped - target matters: the step kernel then keeps 13 sums instead of 41 (3-D tile path)
+static bool step_mse_only(const trx_volumes *vol, const trx_loss_cfg *loss) { return (loss->w_ncc == 0.f) && use_tile_path(vol); }
+
+// the F1 launch of a step (launch_f1's arguments): the MSE-only rows are MODE 4 of the same kernels
+template <class... Args>
+static int launch_step_f1(bool mse_only, Args... args) { return mse_only ? launch_f1<4>(args...) : launch_f1<0>(args...); }
+
+// odd iterations of a run walk the z-streaming columns downward: the tail of one pass is the head of the next (TRX_FLAG_WALK_DOWN)
+static unsigned iteration_flags(const trx_volumes *vol, int k) { return ((k & 1) && !(vol->flags & TRX_FLAG_NO_PINGPONG)) ? vol->flags ^ TRX_FLAG_WALK_DOWN : vol->flags; }
+
+extern "C" int trx_affine_step(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt,
+                               const trx_affine_state *st, void *workspace, size_t workspace_bytes, void *stream)
+{
+    int rc = check_step_args(vol, loss, opt, st, workspace, workspace_bytes);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    float *partials = (float *)workspace;
+    int nblk = 0;
+    // Every step picks GeomA / GeomR per pair in the kernel (TRX_FLAG_SINGLE_GEOM: the primary geometry only).  Rigid runs start from a
+    // random pose (reference: torch.rand, up to 1 rad) and live at large rotations; affine runs start at the identity, where the
+    // GeomA body is all that runs, but may rotate away from it: the single-geometry kernel then gathers from L2 at 3.2x the cost.
+    const int *rows_used = nullptr;
+    const bool mse_only = step_mse_only(vol, loss);
+    rc = launch_step_f1(mse_only, vol, st->theta, partials, &nblk, s, &rows_used);
+    if (rc) return rc;
+    return launch_finalize(vol, loss, opt, st, partials, nblk, rows_used, mse_only, nullptr, s);
+}
+
+extern "C" int trx_affine_accumulate(const trx_volumes *vol, const float *theta, void *workspace, size_t workspace_bytes, void *stream)
+{
+    int rc = check_vol(vol, true);
+    if (rc) return rc;
+    if (!theta || !workspace) return TRX_ERR_ARG;
+    if (workspace_bytes < trx_affine_workspace_bytes(vol)) return TRX_ERR_WORKSPACE;
+    int nblk = 0;
+    const int *rows_used = nullptr;
+    return launch_f1<0>(vol, theta, (float *)workspace, &nblk, (hipStream_t)stream, &rows_used);   // exactly the launch of a step (profiling aid)
+}
+
 extern "C" int trx_affine_run(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt,
                               const trx_affine_state *st, int iters, void *workspace, size_t workspace_bytes, void *stream)
 {
@@ -2660,29 +2667,24 @@ extern "C" int trx_affine_run(const trx_volumes *vol, const trx_loss_cfg *loss, 
     // CARRY (CarryKArgs): launch-bound 3-D steps - one (GeomA / GeomR) kernel and a finalise kernel behind it - run as ONE launch per iteration: the finalise
     // of iteration k rides in the prologue of iteration k + 1's kernel, and one finalise kernel behind the last launch flushes the run.  The launches alternate
     // between the workspace's two partial / note / carry buffers; the LAST one writes the primary set (what trx_affine_workspace_rows_offset describes).
-    if (iters >= 2 && !(vol->flags & TRX_FLAG_NO_CARRY) && check_vol(vol, true) == TRX_OK && vol->ndim == 3 && use_tile_path(vol) && loss && opt && workspace &&
-        st->param && st->theta && st->best_theta && st->best_loss && st->best_idx && st->step && (opt->kind == TRX_OPT_SGD || (opt->kind == TRX_OPT_ADAM && st->adam_m && st->adam_v)) &&
-        (st->mode == TRX_PARAM_AFFINE || st->mode == TRX_PARAM_RIGID) && workspace_bytes >= trx_affine_workspace_bytes(vol)) {
+    // (arguments a step would refuse: the loop below reports them)
+    if (iters >= 2 && !(vol->flags & TRX_FLAG_NO_CARRY) && use_tile_path(vol) && check_step_args(vol, loss, opt, st, workspace, workspace_bytes) == TRX_OK) {
         hipStream_t s = (hipStream_t)stream;
-        const AffineWs ws = affine_ws(*vol);
-        const bool mse_only = loss->w_ncc == 0.f;
+        const bool mse_only = step_mse_only(vol, loss);
         float *const base = (float *)workspace;
-        float *const carry_buf = (float *)((char *)workspace + ws.off_carry);
+        float *const carry_buf = (float *)((char *)workspace + affine_ws(*vol).off_carry);
         const float *prev_partials = nullptr;
         const int *prev_notes = nullptr;
         int prev_nblk = 0;
         for (int k = 0; k < iters; k++) {
-            CarryLaunch cl;
+            CarryLaunch cl = CarryLaunch{};
             cl.parity = (iters - 1 - k) & 1;
-            cl.used = false;
-            cl.partials_out = nullptr;
             cl.args = CarryKArgs{prev_partials, prev_notes, prev_nblk, mse_only ? 1 : 0, k > 0 ? carry_buf + (size_t)(cl.parity ^ 1) * vol->B * kCarryStride : nullptr,
                                  carry_buf + (size_t)cl.parity * vol->B * kCarryStride, (double)vol->D * vol->H * vol->W, *loss, *opt, *st};
-            v.flags = vol->flags;
-            if ((k & 1) && !(vol->flags & TRX_FLAG_NO_PINGPONG)) v.flags ^= TRX_FLAG_WALK_DOWN;
+            v.flags = iteration_flags(vol, k);
             int nblk = 0;
             const int *notes = nullptr;
-            int rc = mse_only ? launch_f1<4>(&v, st->theta, base, &nblk, s, true, &notes, &cl) : launch_f1<0>(&v, st->theta, base, &nblk, s, true, &notes, &cl);
+            int rc = launch_step_f1(mse_only, &v, st->theta, base, &nblk, s, &notes, &cl);
             if (rc) return rc;
             if (!cl.used) {
                 // not a launch the carry form exists for (only possible at k = 0: the choice depends on sizes and flags alone): the launch above was an
@@ -2699,9 +2701,7 @@ extern "C" int trx_affine_run(const trx_volumes *vol, const trx_loss_cfg *loss, 
             return launch_finalize(vol, loss, opt, st, prev_partials, prev_nblk, prev_notes, mse_only, carry_buf, s);
     }
     for (int i = first; i < iters; i++) {
-        // odd iterations walk the z-streaming columns downward: the tail of one pass is the head of the next (TRX_FLAG_WALK_DOWN)
-        v.flags = vol->flags;
-        if ((i & 1) && !(vol->flags & TRX_FLAG_NO_PINGPONG)) v.flags ^= TRX_FLAG_WALK_DOWN;
+        v.flags = iteration_flags(vol, i);
         int rc = trx_affine_step(&v, loss, opt, st, workspace, workspace_bytes, stream);
         if (rc) return rc;
     }
@@ -2718,7 +2718,7 @@ extern "C" int trx_affine_loss(const trx_volumes *vol, const trx_loss_cfg *loss,
     hipStream_t s = (hipStream_t)stream;
     float *partials = (float *)workspace;
     int nblk = 0;
-    rc = launch_f1<1>(vol, theta, partials, &nblk, s, true);
+    rc = launch_f1<1>(vol, theta, partials, &nblk, s);
     if (rc) return rc;
     const double nvox = (double)vol->D * vol->H * vol->W;
     hipLaunchKernelGGL(affine_loss_finalize_kernel, dim3(vol->B), dim3(TRX_FIN_THREADS), 0, s, partials, nblk, nvox, *loss, terms);
@@ -2740,10 +2740,9 @@ extern "C" int trx_affine_warp(const trx_volumes *vol, const float *theta, int c
         v.B = vol->B * channels;                       // geometry: every (pair, channel) is one slab of blocks
         TileGeom t = tile_geom(v);
         if (use_dual(vol)) {
-            const TileGeom ta = tile_geom<GeomA>(v), tr = tile_geom<GeomR>(v);
+            const F1Plan p = f1_plan(v, 0, false, false);   // (GeomA / GeomR on the classic grid)
             v.B = vol->B;
-            const int gx = ta.blocks_per_pair > tr.blocks_per_pair ? ta.blocks_per_pair : tr.blocks_per_pair;
-            launch_dual<3>(dim3(gx, vol->B * channels), s, v, theta, ta, tr, channels, out);
+            launch_dual<3>(p, s, v, theta, channels, out);
             TRX_CHECK_LAUNCH();
             return TRX_OK;
         }
@@ -2783,9 +2782,9 @@ extern "C" int trx_affine_warp_backward(const trx_volumes *vol, const float *the
         TileGeom t = tile_geom(*vol);
         int rows = t.blocks_per_pair;
         if (use_dual(vol)) {
-            const TileGeom ta = tile_geom<GeomA>(*vol), tr = tile_geom<GeomR>(*vol);
-            rows = ta.blocks_per_pair > tr.blocks_per_pair ? ta.blocks_per_pair : tr.blocks_per_pair;
-            launch_dual<2>(dim3(rows, vol->B), s, v, theta, ta, tr, 1, partials);
+            const F1Plan p = f1_plan(*vol, 0, false, false);   // (GeomA / GeomR on the classic grid)
+            rows = p.rows;
+            launch_dual<2>(p, s, v, theta, 1, partials);
         } else {
             hipLaunchKernelGGL((affine_tile_kernel<2>), dim3(t.blocks_per_pair, vol->B), dim3(kTileThreads), 0, s, v, theta, t, 1, partials);
         }
