@@ -100,6 +100,26 @@ def test_affine_warp_backward_vs_oracle(eng, single_step, case):
     assert np.max(np.abs(dth - d32)) <= bar(d32, d64, 1e-4 * np.max(np.abs(d64)))
 
 
+@pytest.mark.parametrize("case,shape", [("B2", (16, 16)), ("ROT3", (16, 16, 16))])
+def test_affine_warp_backward_two_channels_vs_c_oracle(eng, single_step, case, shape):
+    """trx_affine_warp_backward with two channels: the row-walking gather kernel in 2-D and in 3-D (the tile kernels take one channel) and
+    the backward finalise behind it.  grad_out = dMSE/dwarped of each channel, so dtheta is the sum over the channels of the C oracle's
+    dMSE/dtheta; the bar of test_affine_warp_backward_vs_oracle, with the oracle's own fp32-vs-fp64 gap.  Smooth phantoms and poses that keep
+    the samples off the cell faces: the oracle's own dtheta moves by 0.03 / 0.05 of the bar under 3e-7 nudges of theta (A3's pose at 16^3 puts
+    samples within rounding of a face, where the trilinear derivative jumps: 7 x the bar)."""
+    theta = np.asarray(single_step[f"{case}/theta"])
+    mov = torch.cat([ph.blobs(shape, 31), ph.blobs(shape, 32)], dim=1)
+    tgt = torch.cat([ph.blobs(shape, 41), ph.blobs(shape, 42)], dim=1)
+    th = torch.tensor(theta, dtype=torch.float32)[None]
+    w = eng.affine_warp(th.cuda(), mov.cuda())
+    go = 2.0 * (w - tgt.cuda()) / w[0, 0].numel()
+    dth = eng.affine_warp_backward(th.cuda(), mov.cuda(), go).cpu().numpy()[0]
+    d32, d64 = (sum(oracle.c_affine_loss_grad(mov[0, c].to(td).numpy(), tgt[0, c].to(td).numpy(), theta, oracle.wts(w_mse=1.0), oracle.base_tables(shape, nd_))[2]
+                    .astype(np.float64) for c in range(2)) for td, nd_ in ((torch.float32, np.float32), (torch.float64, np.float64)))
+    print(f"two channels {case}: err {np.max(np.abs(dth - d32)):.3e}, bar {bar(d32, d64, 1e-4 * np.max(np.abs(d64))):.3e}, max|d64| {np.max(np.abs(d64)):.3e}")
+    assert np.max(np.abs(dth - d32)) <= bar(d32, d64, 1e-4 * np.max(np.abs(d64)))
+
+
 def _mov_tgt(g, name):
     shape = tuple(g[f"{name}/shape"])
     seed = int(g[f"{name}/meta"][2])

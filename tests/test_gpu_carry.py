@@ -1,4 +1,4 @@
-"""Round 6: the CARRY form of trx_affine_run (csrc/affine.hip, CarryKArgs) - launch-bound 3-D steps (one pair up to ~128^3: the two-body GeomA / GeomR
+"""Round 6: the CARRY form of trx_affine_run (trx_affine_run in csrc/affine.hip; CarryKArgs and carry_prologue in csrc/affine_finalize.h) - launch-bound 3-D steps (one pair up to ~128^3: the two-body GeomA / GeomR
 kernel on the classic grid) as ONE launch per iteration: the finalise of iteration k rides in the prologue of iteration k + 1's kernel (every block of a
 pair reduces that pair's partial rows of the previous launch and computes the same theta; the pair's first block writes the state), one finalise kernel
 behind the last launch flushes the run.  TRX_FLAG_NO_CARRY keeps the two-launch form of rounds 1-5: every test runs both and compares - the folded finalise

@@ -2,10 +2,11 @@
 """Compare the gfx950 code of two builds kernel by kernel: a refactor that must not change the code that runs.
     python tools/isa_compare.py OLD_BUILD_DIR NEW_BUILD_DIR        (directories of `make`'s build/*.o)
 
-For every object present in both: the gfx950 code object out of the .hip_fatbin section, its disassembly split per kernel (addresses and
-encodings dropped) and the per-kernel metadata of its notes (register counts, spills, LDS / scratch / kernarg sizes, block size).  Prints the
-kernels compared, those present in one build only and the code-object sizes; the exit status is 1 when a kernel present in both differs or
-one appears only in the new build."""
+For every object: the gfx950 code object out of the .hip_fatbin section, its disassembly split per kernel (addresses and encodings
+dropped) and the per-kernel metadata of its notes (register counts, spills, LDS / scratch / kernarg sizes, block size).  Kernels are paired
+BY NAME over all objects of a build, so one that moved to another translation unit is compared like any other; the same name in two
+objects of one build is an error.  Prints kernel counts and code-object sizes per object, the kernels that changed object, those that
+differ and those present in one build only; the exit status is 1 when a kernel present in both differs or one appears only in the new build."""
 import os, re, subprocess, sys, tempfile
 
 LLVM = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
@@ -51,42 +52,57 @@ def kernels(co):
                 meta[item[".name"]] = item
     out = {}
     for name, it in meta.items():
-        out[name] = (code.get(name, []), {k: it.get(k) for k in META})
+        lines = code.get(name, [])
+        # Padding between a kernel and whatever follows it in the section (it depends on the neighbour, so a kernel that moved or became the
+        # last of its object would differ by it): dropped only where it follows the instruction that ends the code - nothing falls through there.
+        end = len(lines)
+        while end and lines[end - 1].strip() in ("s_nop 0", "s_code_end", "..."):
+            end -= 1
+        if end and lines[end - 1].split()[0] in ("s_endpgm", "s_branch", "s_setpc_b64"):
+            lines = lines[:end]
+        out[name] = (lines, {k: it.get(k) for k in META})
     return out
 
 
+def build(build_dir, tmp):
+    """every kernel of a build: ({symbol: (instruction lines, metadata dict, object)}, {object: code-object bytes})"""
+    os.mkdir(tmp)
+    found, sizes = {}, {}
+    for f in sorted(os.listdir(build_dir)):
+        co = code_object(os.path.join(build_dir, f), tmp) if f.endswith(".o") else None
+        if co is None:
+            continue
+        sizes[f] = os.path.getsize(co)
+        for k, (code, meta) in kernels(co).items():
+            if k in found:
+                sys.exit(f"{build_dir}: kernel {k} is in {found[k][2]} and in {f}")
+            found[k] = (code, meta, f)
+    return found, sizes
+
+
 def main(old_dir, new_dir):
-    bad = 0
-    tot = {"compared": 0, "removed": 0, "old_bytes": 0, "new_bytes": 0}
     with tempfile.TemporaryDirectory() as tmp:
-        os.mkdir(os.path.join(tmp, "old")); os.mkdir(os.path.join(tmp, "new"))
-        for f in sorted(os.listdir(old_dir)):
-            if not f.endswith(".o") or not os.path.exists(os.path.join(new_dir, f)):
-                continue
-            co_old, co_new = code_object(os.path.join(old_dir, f), os.path.join(tmp, "old")), code_object(os.path.join(new_dir, f), os.path.join(tmp, "new"))
-            if co_old is None and co_new is None:
-                continue
-            a, b = kernels(co_old) if co_old else {}, kernels(co_new) if co_new else {}
-            sa, sb = (os.path.getsize(c) if c else 0 for c in (co_old, co_new))
-            tot["old_bytes"] += sa; tot["new_bytes"] += sb
-            same = [k for k in a if k in b and a[k] == b[k]]
-            diff = [k for k in a if k in b and a[k] != b[k]]
-            gone = [k for k in a if k not in b]
-            new = [k for k in b if k not in a]
-            tot["compared"] += len(same) + len(diff); tot["removed"] += len(gone)
-            print(f"{f}: {len(same) + len(diff)} kernels compared, {len(same)} identical, {len(diff)} differ, {len(gone)} removed, {len(new)} new; "
-                  f"code object {sa} -> {sb} bytes")
-            for k in diff:
-                what = "metadata " + str({m: (a[k][1][m], b[k][1][m]) for m in META if a[k][1][m] != b[k][1][m]}) if a[k][0] == b[k][0] else \
-                    f"instructions ({len(a[k][0])} -> {len(b[k][0])} lines)"
-                print(f"  DIFFERS {k}: {what}")
-            for k in gone:
-                print(f"  removed {k}")
-            for k in new:
-                print(f"  NEW {k}")
-            bad += len(diff) + len(new)
-    print(f"total: {tot['compared']} kernels compared, {tot['removed']} removed, code objects {tot['old_bytes']} -> {tot['new_bytes']} bytes")
-    return 1 if bad else 0
+        (a, sa), (b, sb) = build(old_dir, os.path.join(tmp, "old")), build(new_dir, os.path.join(tmp, "new"))
+    for f in sorted(set(sa) | set(sb)):
+        print(f"{f}: {sum(v[2] == f for v in a.values())} -> {sum(v[2] == f for v in b.values())} kernels; code object {sa.get(f, 0)} -> {sb.get(f, 0)} bytes")
+    both = [k for k in a if k in b]
+    diff = [k for k in both if a[k][:2] != b[k][:2]]
+    moved = [k for k in both if a[k][2] != b[k][2]]
+    gone = [k for k in a if k not in b]
+    new = [k for k in b if k not in a]
+    for k in moved:
+        print(f"  moved {k}: {a[k][2]} -> {b[k][2]}")
+    for k in diff:
+        what = "metadata " + str({m: (a[k][1][m], b[k][1][m]) for m in META if a[k][1][m] != b[k][1][m]}) if a[k][0] == b[k][0] else \
+            f"instructions ({len(a[k][0])} -> {len(b[k][0])} lines)"
+        print(f"  DIFFERS {k} ({b[k][2]}): {what}")
+    for k in gone:
+        print(f"  removed {k} ({a[k][2]})")
+    for k in new:
+        print(f"  NEW {k} ({b[k][2]})")
+    print(f"total: {len(both)} kernels compared, {len(both) - len(diff)} identical, {len(diff)} differ, {len(moved)} changed object, {len(gone)} removed, {len(new)} new; "
+          f"code objects {sum(sa.values())} -> {sum(sb.values())} bytes")
+    return 1 if diff or new else 0
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Itemise the z-streaming F1 loop: static instruction counts of ONE pair of plane steps of affine_tile_dual_kernel<0,0>'s
-z-streaming body, by opcode and by what the opcode does in this loop.  Input: the device assembly of affine.hip
+z-streaming body, by opcode and by what the opcode does in this loop.  Input: the device assembly of affine.hip (the step kernels' unit; the body itself is affine_zstream.h)
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -fno-slp-vectorize -S --cuda-device-only torchregister_amd/csrc/affine.hip -o affine.s
     python3 tools/isa_zstream.py affine.s > profiles/r04_zstream_loop_isa.txt
 The loop body holds TWO plane steps (tvA / tvB register sets), each 4 rows per thread: per voxel-wave = counts / 8."""

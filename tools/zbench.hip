@@ -7,6 +7,7 @@
 #include <cstring>
 #include <vector>
 #include "../torchregister_amd/csrc/affine.hip"
+#include "../torchregister_amd/csrc/affine_finalize.hip"   // the loss / backward finalise launchers affine.hip's entry points call
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e), __FILE__, __LINE__); exit(1); } } while (0)
 

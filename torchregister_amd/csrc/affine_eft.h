@@ -1,4 +1,4 @@
-// EXACT-FOOTPRINT variant of the fused F1 pass (3-D) for ROTATED transforms.  Included by affine.hip inside namespace trx.
+// EXACT-FOOTPRINT variant of the fused F1 pass (3-D) for ROTATED transforms.  Included by affine.hip inside namespace trx, behind affine_tile.h and affine_zstream.h.
 //
 // Why a third kernel family.  Counters of the tile kernels at theta = R(0.5, 0.4, 0.3) diag(1.05, 0.95, 1.02), 8 x 256^3
 // (profiles/r04a_pose_pmc.txt): 620 us per launch, 46.5 M L2 requests of 128 B = 5.5 x the algorithmic bytes, 41 % of them misses

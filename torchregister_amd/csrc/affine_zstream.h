@@ -1,4 +1,4 @@
-// Z-STREAMING variant of the fused F1 pass (3-D) for transforms near the identity.  Included by affine.hip inside namespace trx.
+// Z-STREAMING variant of the fused F1 pass (3-D) for transforms near the identity.  Included by affine.hip inside namespace trx, behind affine_tile.h.
 //
 // Why a second kernel family: the tile kernels (tile_body) stage the whole pre-image box of a tile, wait for it, gather, and start
 // over; requests are in flight only while a block is in its burst phase, and every tile re-fetches its z / y halo.  Here a 512-thread

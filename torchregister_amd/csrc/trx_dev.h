@@ -2,7 +2,7 @@
 //  * TUNING CONSTANTS (first block): numbers, not code paths; the defaults ARE the product, and tools/build_variant.sh A/B runs override
 //    them with -D...  The code forms that lost their measurements are gone from the sources; DESIGN.md and profiles/ keep the numbers;
 //  * development INSTRUMENTATION (second block: TRX_DEV builds of tools/kbench.hip, -DTRX_TIMING=1 / -DTRX_LDS_PAD=n): in the product
-//    library every one of those expands to nothing, so the kernels in affine.hip read without #if blocks.
+//    library every one of those expands to nothing, so the kernels in affine.hip and affine_tile.h read without #if blocks.
 #pragma once
 
 // ---- tuning constants of the tile kernels
