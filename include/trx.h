@@ -41,7 +41,9 @@ extern "C" {
  *        trx_affine_run folds the finalise of an iteration into the next iteration's kernel for launch-bound 3-D steps (TRX_FLAG_NO_CARRY keeps two launches);
  *        trx_affine_workspace_bytes grows by a second partial / note buffer and two carry buffers (3-D).  No entry point changed its signature.
  *        Later addition under the same number: trx_resample / trx_resample_workspace_bytes (the levels of a coarse-to-fine pyramid and the flow
- *        hand-over between them) - new entry points only, no existing signature or struct changed. */
+ *        hand-over between them) - new entry points only, no existing signature or struct changed.
+ *        Later addition under the same number: trx_bspline_* and trx_bspline_state (cubic B-spline free-form deformation: control lattice <-> dense
+ *        flow, its adjoint, and the device-side loop over them) - new entry points and one new struct only. */
 #define TRX_VERSION 240
 #define TRX_PSTRIDE 12  /* floats per pair in theta / param / adam / best_theta arrays */
 
@@ -399,6 +401,62 @@ int trx_nmi_loop_update(int ndim, float *theta, float *pose, const float *grad_a
 size_t trx_resample_workspace_bytes(int ndim, int N, int D, int H, int W, int Do, int Ho, int Wo);
 int trx_resample(const float *in, float *out, int ndim, int N, int D, int H, int W, int Do, int Ho, int Wo, int align_corners, int channels,
                  const float *channel_scale /*[host]*/, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- Cubic B-spline free-form deformation (Rueckert et al. 1999; extension, the reference has dense flows only: ref:warpings.py:178-242).
+ * A control lattice with an integer spacing of d voxels per axis parameterises the displacement field.  Per spatial axis of S voxels:
+ *   G = (S - 1) / d + 4 control points (integer division), point i at voxel coordinate (i - 1) d;
+ *   at voxel x: i0 = x / d, t = (x % d) / d, weights B0 = (1-t)^3/6, B1 = (3t^3 - 6t^2 + 4)/6, B2 = (-3t^3 + 3t^2 + 3t + 1)/6, B3 = t^3/6
+ *   (formed in fp64, stored in fp32: there are only d distinct quadruples per axis).
+ * ctrl [B][ndim][Gz][Gy][Gx] fp32 contiguous (2-D: [B][2][Gy][Gx], D = 1, sz ignored), units and channel convention of `flow` above.
+ *   expand: flow_c(z,y,x) = base_c(z,y,x) + sum_{l,m,n=0..3} B_l(tz) B_m(ty) B_n(tx) ctrl_c[iz0+l][iy0+m][ix0+n]   (base: nullable, shape of flow)
+ *   reduce: dctrl_c[k] = sum over voxels of w_k(voxel) dflow_c(voxel), the same weights - the exact adjoint; base receives no gradient.
+ * Spacings: 1 .. 1024 per axis (sz, sy, sx; they may differ).  Separable 1-D passes, no atomics, every sum in a fixed order: the same bits on
+ * every call, and a pair's result does not depend on the batch around it.  CPU restatement: tests/bspline_ref.py. */
+
+/* [host] (Gz, Gy, Gx) of a geometry and spacing into grid[3] (2-D: Gz = 1).  No device work.  Extension; restatement: tests/bspline_ref.py::grid. */
+int trx_bspline_grid(int ndim, int D, int H, int W, int sz, int sy, int sx, int *grid /*[host]*/);
+
+/* Bytes of workspace that trx_bspline_expand, trx_bspline_reduce and trx_bspline_run / _step each accept for this geometry (one size serves all:
+ * the intermediates of the separable passes, and for the loop dL/dctrl, the loss terms and trx_flow_loss_grad's workspace).  0 = arguments
+ * rejected, as trx_resample_workspace_bytes.  Extension. */
+size_t trx_bspline_workspace_bytes(int ndim, int B, int D, int H, int W, int sz, int sy, int sx);
+
+/* Control lattice -> dense flow (+ base).  Passes z, y, x: only the last touches a full-size array (12 B/voxel written in 3-D, 24 B/voxel moved
+ * with a base).  Extension; restatement: tests/bspline_ref.py::expand. */
+int trx_bspline_expand(const float *ctrl, const float *base /*nullable*/, float *flow, int ndim, int B, int D, int H, int W, int sz, int sy, int sx,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
+/* The adjoint: dL/dflow [B][ndim][D][H][W] -> dL/dctrl [B][ndim][Gz][Gy][Gx].  Passes x, y, z: dflow is read exactly once (12 B/voxel in 3-D).
+ * Extension; restatement: tests/bspline_ref.py::reduce. */
+int trx_bspline_reduce(const float *dflow, float *dctrl, int ndim, int B, int D, int H, int W, int sz, int sy, int sx, void *workspace,
+                       size_t workspace_bytes, void *stream);
+
+/* State of the free-form-deformation loop, all device memory.  Early stop, step and flow_last as in trx_flow_state: the iteration whose recorded
+ * loss is <= stop_crit still applies its update, every later iteration is a no-op for that pair, step[b] = number of recorded losses,
+ * flow_last = the expanded flow of the pair's last forward.  Extension (no counterpart in the reference). */
+typedef struct {
+    float *ctrl;        /* [B][ndim][Gz][Gy][Gx] in/out: the parameters */
+    float *adam_m;      /* same size, Adam only (may be NULL for SGD) */
+    float *adam_v;
+    const float *base;  /* [B][ndim][D][H][W] or NULL: a fixed dense flow the lattice adds to (coarse-to-fine hand-over); no gradient */
+    float *flow;        /* [B][ndim][D][H][W] scratch the caller owns: the expanded flow of the last forward of the call */
+    float *dflow;       /* same size, scratch: dL/dflow of that forward */
+    float *losses;      /* [B][losses_capacity] */
+    int losses_capacity;
+    int *step;          /* [B] in/out, 0 before the run */
+    float stop_crit;
+    int *stopped;       /* [B] in/out, 0 before the run; NULL disables the early stop */
+    float *flow_last;   /* optional [B][ndim][D][H][W]: kept for a pair when it stops and on the last iteration of every call */
+} trx_bspline_state;
+
+/* One iteration / `iters` iterations back to back, no host sync, no allocation: expand -> trx_flow_loss_grad on the expanded flow (the fused
+ * MSE / NCC / SSD loss of trx_loss_cfg and its dL/dflow) -> reduce -> per pair: losses[b][t] = terms[b][0], early stop, SGD or Adam on ctrl
+ * (trx_opt_cfg's constants and bias correction).  spacing [host]: (sz, sy, sx).  Status codes before any HIP call; iters > losses_capacity:
+ * TRX_ERR_CAPACITY.  Extension: arbiter = tests/bspline_ref.py::expand + oracle/compose.py (flow_warp, weighted_loss) under torch autograd. */
+int trx_bspline_step(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt, const trx_bspline_state *st,
+                     const int *spacing /*[host]*/, void *workspace, size_t workspace_bytes, void *stream);
+int trx_bspline_run(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt, const trx_bspline_state *st,
+                    const int *spacing /*[host]*/, int iters, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

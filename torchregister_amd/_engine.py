@@ -402,6 +402,165 @@ class FlowSolver:
         _lib.check(rc, "trx_flow_run")
 
 
+def _spacing3(spacing, nd):
+    """An int or a per-axis sequence -> the (sz, sy, sx) of the C ABI (2-D: sz = 1) as a tuple of ints >= 1."""
+    if isinstance(spacing, bool):
+        raise ValueError(f"spacing must be an int >= 1 or {nd} of them, got {spacing!r}")
+    sp = list(spacing) if isinstance(spacing, (list, tuple)) else [spacing] * nd
+    if len(sp) != nd or any(isinstance(s, bool) or not isinstance(s, int) or s < 1 for s in sp):
+        raise ValueError(f"spacing must be an int >= 1 or {nd} of them, got {spacing!r}")
+    if max(sp) > 1024:
+        raise ValueError(f"spacing {spacing!r}: at most 1024 voxels per axis")
+    return (1,) * (3 - nd) + tuple(sp)
+
+
+def _dhw(spatial):
+    return (1,) * (3 - len(spatial)) + tuple(int(s) for s in spatial)
+
+
+def bspline_grid(spatial, spacing):
+    """Control-lattice size of a cubic B-spline free-form deformation: per axis G = (S - 1) // spacing + 4 (trx_bspline_grid; host only)."""
+    spatial = tuple(int(s) for s in spatial)
+    nd = len(spatial)
+    if nd not in (2, 3):
+        raise ValueError(f"expected 2 or 3 spatial sizes, got {spatial}")
+    grid = (ctypes.c_int * 3)()
+    rc = _lib.load().trx_bspline_grid(nd, *_dhw(spatial), *_spacing3(spacing, nd), grid)
+    _lib.check(rc, "trx_bspline_grid")
+    return tuple(grid)[3 - nd:]
+
+
+def _bspline_workspace(lib, nd, B, spatial, sp3, device):
+    ws_bytes = lib.trx_bspline_workspace_bytes(nd, B, *_dhw(spatial), *sp3)
+    if ws_bytes == 0:
+        raise _lib.TrxError(f"trx_bspline_workspace_bytes rejected {B} x {tuple(spatial)} with spacing {sp3[3 - nd:]}")
+    return torch.empty(ws_bytes, dtype=torch.uint8, device=device), ws_bytes
+
+
+def bspline_expand(ctrl, spatial, spacing, base=None):
+    """trx_bspline_expand: control tensor [B, nd, *grid] (fp32, GPU) -> dense flow [B, nd, *spatial] (+ base, a dense flow of that shape)."""
+    _require_gpu(ctrl, "ctrl")
+    spatial = tuple(int(s) for s in spatial)
+    nd = len(spatial)
+    sp3 = _spacing3(spacing, nd)
+    B = ctrl.shape[0]
+    if tuple(ctrl.shape) != (B, nd) + bspline_grid(spatial, spacing):
+        raise ValueError(f"ctrl shape {tuple(ctrl.shape)} is not [B, {nd}, *{bspline_grid(spatial, spacing)}]")
+    lib = _lib.load()
+    ctrl = ctrl.detach().contiguous()
+    flow = torch.empty((B, nd) + spatial, dtype=torch.float32, device=ctrl.device)
+    if base is not None:
+        _require_gpu(base, "base")
+        if base.shape != flow.shape:
+            raise ValueError(f"base shape {tuple(base.shape)} does not match the flow {tuple(flow.shape)}")
+        base = base.detach().contiguous()
+    ws, ws_bytes = _bspline_workspace(lib, nd, B, spatial, sp3, ctrl.device)
+    with torch.cuda.device(ctrl.device):
+        rc = lib.trx_bspline_expand(_lib.ptr(ctrl), _lib.ptr(base), _lib.ptr(flow), nd, B, *_dhw(spatial), *sp3, _lib.ptr(ws), ws_bytes,
+                                    _lib.current_stream(ctrl.device))
+    _lib.check(rc, "trx_bspline_expand")
+    return flow
+
+
+def bspline_reduce(dflow, spacing):
+    """trx_bspline_reduce, the adjoint of bspline_expand: dL/dflow [B, nd, *spatial] (fp32, GPU) -> dL/dctrl [B, nd, *grid]."""
+    _require_gpu(dflow, "dflow")
+    nd = dflow.dim() - 2
+    if nd not in (2, 3) or dflow.shape[1] != nd:
+        raise ValueError(f"expected a dense flow gradient [B,nd,*spatial], got {tuple(dflow.shape)}")
+    spatial = tuple(dflow.shape[2:])
+    sp3 = _spacing3(spacing, nd)
+    B = dflow.shape[0]
+    lib = _lib.load()
+    dflow = dflow.detach().contiguous()
+    dctrl = torch.empty((B, nd) + bspline_grid(spatial, spacing), dtype=torch.float32, device=dflow.device)
+    ws, ws_bytes = _bspline_workspace(lib, nd, B, spatial, sp3, dflow.device)
+    with torch.cuda.device(dflow.device):
+        rc = lib.trx_bspline_reduce(_lib.ptr(dflow), _lib.ptr(dctrl), nd, B, *_dhw(spatial), *sp3, _lib.ptr(ws), ws_bytes,
+                                    _lib.current_stream(dflow.device))
+    _lib.check(rc, "trx_bspline_reduce")
+    return dctrl
+
+
+class BSplineSolver:
+    """Cubic B-spline free-form deformation (extension): the control lattice `ctrl` [B, nd, *grid] is the parameter, the displacement field
+    is base + expand(ctrl); the whole loop (expand, fused loss and dL/dflow, reduce, SGD / Adam, early stop) runs in trx_bspline_run.
+    After run(): `flow` = expand of the current ctrl (+ base), `flow_last` (keep_last or stop_crit) = the flow of the last forward."""
+
+    def __init__(self, moving, target, spacing, loss=None, optimizer="sgd", lr=1e-3, init=None, base=None, capacity=1000, stop_crit=None,
+                 keep_last=False, betas=(0.9, 0.999), eps=1e-8):
+        self.lib = _lib.load()
+        self.batch = _Batch(moving, target, tables=False)
+        if self.batch.C != 1:
+            raise ValueError("the optimiser path takes single-channel volumes [B,1,...]")
+        b, nd, dev = self.batch.B, self.batch.nd, self.batch.device
+        self.nd = nd
+        self.spacing = _spacing3(spacing, nd)[3 - nd:]
+        self.sp3 = (ctypes.c_int * 3)(*_spacing3(spacing, nd))
+        self.grid = bspline_grid(self.batch.spatial, self.spacing)
+        self.loss = loss or LossSpec(w_mse=1.0)
+        self.loss_c = self.loss.c()
+        self.opt = opt_cfg(optimizer, lr, betas, eps)
+        cshape, fshape = (b, nd) + self.grid, (b, nd) + self.batch.spatial
+        if init is None:
+            self.ctrl = torch.zeros(cshape, device=dev)
+        else:
+            if tuple(init.shape) != cshape:
+                raise ValueError(f"init shape {tuple(init.shape)} is not the control tensor's {cshape}")
+            self.ctrl = init.to(device=dev, dtype=torch.float32).contiguous().clone()
+        self.base = None
+        if base is not None:
+            _require_gpu(base, "base")
+            if tuple(base.shape) != fshape:
+                raise ValueError(f"base shape {tuple(base.shape)} is not the flow's {fshape}")
+            self.base = base.detach().contiguous()
+        adam = self.opt.kind == _lib.OPT_ADAM
+        self.adam_m = torch.zeros(cshape, device=dev) if adam else None
+        self.adam_v = torch.zeros(cshape, device=dev) if adam else None
+        self.flow = torch.empty(fshape, device=dev)
+        self.dflow = torch.empty(fshape, device=dev)
+        self.capacity = int(capacity)
+        self.losses = torch.full((b, self.capacity), float("nan"), device=dev)
+        self.step = torch.zeros(b, dtype=torch.int32, device=dev)
+        self.stopped = torch.zeros(b, dtype=torch.int32, device=dev) if stop_crit is not None else None
+        self.flow_last = torch.empty(fshape, device=dev) if (keep_last or stop_crit is not None) else None
+        self.vol = self.batch.vol()
+        self.workspace, self.ws_bytes = _bspline_workspace(self.lib, nd, b, self.batch.spatial, tuple(self.sp3), dev)
+        st = _lib.BSplineState()
+        st.ctrl = self.ctrl.data_ptr()
+        st.adam_m = self.adam_m.data_ptr() if adam else None
+        st.adam_v = self.adam_v.data_ptr() if adam else None
+        st.base = self.base.data_ptr() if self.base is not None else None
+        st.flow, st.dflow = self.flow.data_ptr(), self.dflow.data_ptr()
+        st.losses, st.losses_capacity, st.step = self.losses.data_ptr(), self.capacity, self.step.data_ptr()
+        st.stop_crit = float(stop_crit) if stop_crit is not None else 0.0
+        st.stopped = self.stopped.data_ptr() if self.stopped is not None else None
+        st.flow_last = self.flow_last.data_ptr() if self.flow_last is not None else None
+        self.state = st
+        self.enqueued = 0
+        self._expand()
+
+    def _expand(self):
+        """flow = base + expand(ctrl): the same call the loop makes, so the bits are those of a forward at the current ctrl."""
+        D, H, W = _dhw(self.batch.spatial)
+        with torch.cuda.device(self.batch.device):
+            rc = self.lib.trx_bspline_expand(_lib.ptr(self.ctrl), _lib.ptr(self.base), _lib.ptr(self.flow), self.nd, self.batch.B, D, H, W, *self.sp3,
+                                             _lib.ptr(self.workspace), self.ws_bytes, _lib.current_stream(self.batch.device))
+        _lib.check(rc, "trx_bspline_expand")
+
+    def run(self, iters):
+        iters = int(iters)
+        if self.enqueued + iters > self.capacity:
+            raise _lib.TrxError(f"loss-curve capacity exceeded: {self.enqueued} iterations enqueued + {iters} requested > capacity "
+                                f"{self.capacity} (create the solver with a larger `capacity`)")
+        self.enqueued += iters
+        with torch.cuda.device(self.batch.device):
+            rc = self.lib.trx_bspline_run(ctypes.byref(self.vol), ctypes.byref(self.loss_c), ctypes.byref(self.opt), ctypes.byref(self.state),
+                                          self.sp3, iters, _lib.ptr(self.workspace), self.ws_bytes, _lib.current_stream(self.batch.device))
+        _lib.check(rc, "trx_bspline_run")
+        self._expand()
+
+
 def flow_warp(moving, flow, nearest=False):
     """SpatialTransformer forward: moving [B,C,*sp], flow [B,nd,*sp] -> [B,C,*sp]; nearest: mode='nearest' (round half to even, zeros outside)."""
     lib = _lib.load()

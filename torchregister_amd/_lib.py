@@ -64,6 +64,12 @@ class FlowState(ctypes.Structure):
                 ("stopped", ctypes.c_void_p), ("flow_last", ctypes.c_void_p)]
 
 
+class BSplineState(ctypes.Structure):
+    _fields_ = [("ctrl", ctypes.c_void_p), ("adam_m", ctypes.c_void_p), ("adam_v", ctypes.c_void_p), ("base", ctypes.c_void_p),
+                ("flow", ctypes.c_void_p), ("dflow", ctypes.c_void_p), ("losses", ctypes.c_void_p), ("losses_capacity", ctypes.c_int),
+                ("step", ctypes.c_void_p), ("stop_crit", ctypes.c_float), ("stopped", ctypes.c_void_p), ("flow_last", ctypes.c_void_p)]
+
+
 # name -> (restype, argtypes); must list every symbol include/trx.h declares (tests check this)
 _P = ctypes.c_void_p
 SIGNATURES = {
@@ -128,6 +134,14 @@ SIGNATURES = {
     "trx_lncc_loss_grad": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_float, _P, _P, _P, ctypes.c_size_t, _P]),
     "trx_resample_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 8),
     "trx_resample": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 10 + [_P, _P, ctypes.c_size_t, _P]),
+    "trx_bspline_grid": (ctypes.c_int, [ctypes.c_int] * 7 + [c_int_p]),
+    "trx_bspline_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 8),
+    "trx_bspline_expand": (ctypes.c_int, [_P, _P, _P] + [ctypes.c_int] * 8 + [_P, ctypes.c_size_t, _P]),
+    "trx_bspline_reduce": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 8 + [_P, ctypes.c_size_t, _P]),
+    "trx_bspline_step": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(LossCfg), ctypes.POINTER(OptCfg), ctypes.POINTER(BSplineState), c_int_p,
+                                        _P, ctypes.c_size_t, _P]),
+    "trx_bspline_run": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(LossCfg), ctypes.POINTER(OptCfg), ctypes.POINTER(BSplineState), c_int_p,
+                                       ctypes.c_int, _P, ctypes.c_size_t, _P]),
 }
 
 _lib = None

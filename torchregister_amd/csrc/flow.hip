@@ -870,11 +870,19 @@ static unsigned flow_grid_x(const trx_volumes &v)
 
 using namespace trx;
 
+// The flow workspace depends on the sizes alone (trx_common.h: csrc/bspline.hip reserves one inside its own workspace)
+size_t trx::flow_workspace_size(int ndim, int B, int D, int H, int W)
+{
+    trx_volumes v{};
+    v.ndim = ndim; v.B = B; v.D = D; v.H = H; v.W = W;
+    return (size_t)B * flow_grid_x(v) * kFlowNP * sizeof(float) + (size_t)B * sizeof(FlowCoef) + 256 +
+           (size_t)B * sizeof(double) + 256;   // + the fp64 data part of the last recorded loss (lagged regulariser term)
+}
+
 extern "C" size_t trx_flow_workspace_bytes(const trx_volumes *vol)
 {
     if (check_vol_flow(vol, false) != TRX_OK) return 0;
-    return (size_t)vol->B * flow_grid_x(*vol) * kFlowNP * sizeof(float) + (size_t)vol->B * sizeof(FlowCoef) + 256 +
-           (size_t)vol->B * sizeof(double) + 256;   // + the fp64 data part of the last recorded loss (lagged regulariser term)
+    return flow_workspace_size(vol->ndim, vol->B, vol->D, vol->H, vol->W);
 }
 
 static FlowCoef *coef_ptr(const trx_volumes *vol, void *workspace)

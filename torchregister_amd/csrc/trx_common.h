@@ -14,6 +14,9 @@
 
 namespace trx {
 
+// [host] bytes behind trx_flow_workspace_bytes for a geometry that has already been validated (csrc/flow.hip)
+size_t flow_workspace_size(int ndim, int B, int D, int H, int W);
+
 // ------------------------------------------------------------------------------------------
 // Trilinear / bilinear sample with zero padding (grid_sample 'bilinear', padding_mode='zeros').
 // Returns the value and the derivative wrt the (un-normalised) voxel coordinates.

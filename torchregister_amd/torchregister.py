@@ -24,7 +24,7 @@ def _per_level(value, levels, name):
 
 class Register():
     def __init__(self, mode='rigid', device='cpu', criterion=None, weight=None, grad_edges=False, debug=False, *,
-                 optimizer='sgd', honor_criterion=False, init=None, smooth_weight=0.0, flow_model='unet', levels=1):
+                 optimizer='sgd', honor_criterion=False, init=None, smooth_weight=0.0, flow_model='unet', levels=1, spacing=None):
         '''
         Numerical registration on an AMD GPU (MI355X) behind the TorchRegister API.
 
@@ -42,13 +42,25 @@ class Register():
         levels : (keyword-only extension) coarse-to-fine registration over a pyramid of this many levels (pyramid_shapes: each level
             halves every axis that stays >= 8 voxels).  Rigid / affine hand the final parameters of a level to the next unchanged (theta is
             in normalised coordinates); flow_model='direct' hands its final flow up through upsample_flow.  1 = single resolution.
+        flow_model : (keyword-only extension) 'unet', 'direct' or 'bspline' - a cubic B-spline free-form deformation whose control lattice has
+            `spacing` voxels between control points (an int or one per axis, default 8).  After optim, `.control` is the final control tensor
+            (the finest level's).  With levels > 1 the spacing in voxels is the same at every level, every level starts from a zero control
+            tensor and adds to base = upsample_flow(the previous level's final dense flow): multi-level FFD as a sum of levels.
         '''
         if mode not in ('rigid', 'affine', 'flow'):
             raise ValueError("mode must be 'rigid', 'affine' or 'flow'")
         if not isinstance(levels, int) or isinstance(levels, bool) or levels < 1:
             raise ValueError(f"levels must be an int >= 1, got {levels!r}")
-        if levels > 1 and mode == 'flow' and flow_model == 'unet':
+        if levels > 1 and mode == 'flow' and flow_model not in ('direct', 'bspline'):
             raise ValueError("levels > 1 needs flow_model='direct': the U-Net is built for one image size")
+        if spacing is not None and not (mode == 'flow' and flow_model == 'bspline'):
+            raise ValueError("spacing is the control-point spacing of mode='flow' with flow_model='bspline'")
+        if mode == 'flow' and flow_model == 'bspline':
+            each = [] if spacing is None else list(spacing) if isinstance(spacing, (list, tuple)) else [spacing]
+            if any(isinstance(v, bool) or not isinstance(v, int) or v < 1 for v in each) or len(each) > 3:
+                raise ValueError(f"spacing must be an int >= 1 or one per axis, got {spacing!r}")
+            if smooth_weight != 0:
+                raise ValueError("flow_model='bspline' takes no smooth_weight: the control lattice is the regulariser")
         self.criterion = criterion
         self.weight = weight
         self.mode = mode
@@ -62,12 +74,25 @@ class Register():
         self.init = init
         self.smooth_weight = smooth_weight
         self.flow_model = flow_model
+        self.spacing = spacing
         self.levels = levels
+        self.control = None
         self.losses = None
         self.final_theta = None
         self.best_idx = None
         self.level_losses = None
         self.level_shapes = None
+
+    def _flow_kw(self, n, lr, max_epochs):
+        kw = dict(mode='bilinear', n=n, lr=lr, max_epochs=max_epochs, optimizer=self.optimizer, smooth_weight=self.smooth_weight,
+                  flow_model=self.flow_model)
+        if self.flow_model == 'bspline':
+            kw.update(spacing=self.spacing)
+        if self.criterion is not None and self.weight is not None:           # ref:torchregister.py:71-73
+            kw.update(criterions=self.criterion, weights=self.weight)
+        elif self.weight is not None:                                         # ref:torchregister.py:74-76
+            kw.update(weights=self.weight)
+        return kw
 
     def optim(self, moving, target, lr=1E-5, max_epochs=1000, n=32, per=0.1):
         '''
@@ -81,18 +106,13 @@ class Register():
         if self.levels > 1:
             return self._optim_levels(moving, target, lr, max_epochs, n, per)
         if self.mode == 'flow':
-            kw = dict(mode='bilinear', n=n, lr=lr, max_epochs=max_epochs, optimizer=self.optimizer, smooth_weight=self.smooth_weight,
-                      flow_model=self.flow_model)
-            if self.criterion is not None and self.weight is not None:       # ref:torchregister.py:71-73
-                kw.update(criterions=self.criterion, weights=self.weight)
-            elif self.weight is not None:                                     # ref:torchregister.py:74-76
-                kw.update(weights=self.weight)
-            flowreg = flow_register(target.shape[2:], **kw).to(moving.device)
+            flowreg = flow_register(target.shape[2:], **self._flow_kw(n, lr, max_epochs)).to(moving.device)
             flowreg.optimize(moving, target, self.device, self.debug)
             self.theta = flowreg.flow
             self.warp = flowreg.deform
             self.losses = flowreg.losses
             self.final_theta = flowreg.final_flow
+            self.control = flowreg.control
             return
 
         fn = affine_register if self.mode == 'affine' else rigid_register
@@ -125,17 +145,16 @@ class Register():
         self.level_losses, self.level_shapes = [], shapes
         for k in range(L):
             if flow:
-                kw = dict(mode='bilinear', n=n, lr=lrs[k], max_epochs=epochs[k], optimizer=self.optimizer, smooth_weight=self.smooth_weight,
-                          flow_model=self.flow_model)
-                if self.criterion is not None and self.weight is not None:
-                    kw.update(criterions=self.criterion, weights=self.weight)
-                elif self.weight is not None:
-                    kw.update(weights=self.weight)
-                reg = flow_register(shapes[k], **kw).to(moving.device)
-                reg.init_flow = None if init is None else upsample_flow(init, shapes[k])
+                reg = flow_register(shapes[k], **self._flow_kw(n, lrs[k], epochs[k])).to(moving.device)
+                up = None if init is None else upsample_flow(init, shapes[k])
+                if self.flow_model == 'bspline':
+                    reg.base_flow = up       # the level's lattice starts from zero and adds to what the coarser levels found
+                else:
+                    reg.init_flow = up
                 reg.optimize(movs[k], tgts[k], self.device, False)
                 init = reg.final_flow
                 self.theta, self.warp, self.final_theta = reg.flow, reg.deform, reg.final_flow
+                self.control = reg.control
                 self.losses = reg.losses
             else:
                 fn = affine_register if self.mode == 'affine' else rigid_register

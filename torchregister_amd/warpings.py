@@ -374,14 +374,29 @@ class flow_register(nn.Module):
     reference's), `.warp` (SpatialTransformer), `.deform(x)` and the stop_crit early stop follow the reference.
     Deviation (flow_model='direct' with a batch): the reference is batch-1 and stops on its one scalar loss
     (ref:warpings.py:231-233); here a batch is B independent registrations, each pair stops on its OWN loss, and
-    `optimize` reports 'Converged' only when every pair has stopped (`.iterations` holds the per-pair counts)."""
+    `optimize` reports 'Converged' only when every pair has stopped (`.iterations` holds the per-pair counts).
+    flow_model='bspline' (extension): cubic B-spline free-form deformation - a control lattice with `spacing` voxels between control
+    points (an int or one per axis) parameterises the flow, flow = base_flow + expand(control), optimised by trx_bspline_run like
+    'direct' (fused MSE / NCC / SSD criteria only; smooth by construction, so smooth_weight must stay 0).  `.control` is the final
+    control tensor [B, nd, *grid]; `.init_control` (None = zero) and `.base_flow` (None = none) set the start."""
 
     def __init__(self, img_size, mode="bilinear", in_c=1, n=1, criterions=None, weights=[0.33, 0.33, 0.33], lr=1E-3,
-                 max_epochs=2000, stop_crit=1E-4, *, flow_model="unet", optimizer="sgd", smooth_weight=0.0):
+                 max_epochs=2000, stop_crit=1E-4, *, flow_model="unet", optimizer="sgd", smooth_weight=0.0, spacing=None):
         super().__init__()
-        if flow_model not in ("unet", "direct"):
-            raise ValueError("flow_model must be 'unet' or 'direct'")
+        if flow_model not in ("unet", "direct", "bspline"):
+            raise ValueError("flow_model must be 'unet', 'direct' or 'bspline'")
         self.img_size = tuple(int(s) for s in img_size)
+        if flow_model != "bspline" and spacing is not None:
+            raise ValueError(f"spacing is the control-point spacing of flow_model='bspline'; flow_model={flow_model!r} has none")
+        self.spacing = None
+        if flow_model == "bspline":
+            self.spacing = _engine._spacing3(8 if spacing is None else spacing, len(self.img_size))[3 - len(self.img_size):]
+            if smooth_weight != 0:
+                raise ValueError("flow_model='bspline' takes no smooth_weight: the control lattice is the regulariser (choose a larger spacing)")
+            used = [nn.MSELoss(), NCCLoss(), NMILoss()] if criterions is None else criterions
+            if loss_spec_from(used, weights[: len(used)]) is None:
+                raise ValueError("flow_model='bspline' runs the fused criteria only: nn.MSELoss (mean), NCCLoss and SSDLoss, "
+                                 f"got {[type(c).__name__ for c in used]}")
         self.flow_model = flow_model
         self.criterions = [nn.MSELoss(), NCCLoss(), NMILoss()] if criterions is None else criterions
         if len(weights) < len(self.criterions):
@@ -400,6 +415,9 @@ class flow_register(nn.Module):
         self.final_flow = None
         self.losses = None
         self.init_flow = None      # flow_model='direct': the flow the optimisation starts from (None = zero; set by Register's coarse-to-fine loop)
+        self.control = None        # flow_model='bspline': the final control tensor
+        self.init_control = None   # flow_model='bspline': the control tensor the optimisation starts from (None = zero)
+        self.base_flow = None      # flow_model='bspline': a fixed dense flow the lattice adds to (None = none; Register's coarse-to-fine loop)
 
     def forward(self, x, device=None):
         if self.model is not None:
@@ -421,6 +439,8 @@ class flow_register(nn.Module):
                 with torch.backends.cudnn.flags(enabled=True, benchmark=True):
                     return self._optimize_unet(moving, target, spec, debug)
             return self._optimize_unet(moving, target, spec, debug)
+        if self.flow_model == "bspline":
+            return self._optimize_bspline(moving, target, spec, debug)
         lncc = None
         if spec is None and moving.dim() == 5 and len(self.criterions) == 1 and isinstance(self.criterions[0], LocalNCCLoss):
             # direct flow + local-window NCC (+ smoothness): the VoxelMorph-style objective as ONE device-side loop (trx_flow_lncc_run) -
@@ -440,6 +460,24 @@ class flow_register(nn.Module):
         self.flow = solver.flow_last if self.max_epochs > 0 else solver.flow
         self.final_flow = solver.flow
         self.losses = solver.losses[:, :n]             # pairs that stopped earlier are NaN-padded behind their own `iterations`
+        self.iterations = done
+        self.solver = solver
+        message = "Converged to %f" % self.stop_crit if bool((solver.stopped != 0).all()) else "Reached max epochs"
+        if debug:
+            print("Optimization ended with status: %s" % message)
+
+    def _optimize_bspline(self, moving, target, spec, debug):
+        """The 'direct' loop with a control lattice as the parameter: one trx_bspline_run call, per-pair early stop on the device, one host sync."""
+        from ._engine import BSplineSolver
+        solver = BSplineSolver(moving, target, self.spacing, loss=spec, optimizer=self.optimizer_kind, lr=self.lr, init=self.init_control,
+                               base=self.base_flow, capacity=max(1, self.max_epochs), stop_crit=self.stop_crit, keep_last=True)
+        solver.run(self.max_epochs)
+        done = solver.step.cpu()
+        n = int(done.max()) if self.max_epochs > 0 else 0
+        self.flow = solver.flow_last if self.max_epochs > 0 else solver.flow
+        self.final_flow = solver.flow
+        self.control = solver.ctrl
+        self.losses = solver.losses[:, :n]
         self.iterations = done
         self.solver = solver
         message = "Converged to %f" % self.stop_crit if bool((solver.stopped != 0).all()) else "Reached max epochs"
