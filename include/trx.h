@@ -416,8 +416,9 @@ int trx_resample(const float *in, float *out, int ndim, int N, int D, int H, int
 /* [host] (Gz, Gy, Gx) of a geometry and spacing into grid[3] (2-D: Gz = 1).  No device work.  Extension; restatement: tests/bspline_ref.py::grid. */
 int trx_bspline_grid(int ndim, int D, int H, int W, int sz, int sy, int sx, int *grid /*[host]*/);
 
-/* Bytes of workspace that trx_bspline_expand, trx_bspline_reduce and trx_bspline_run / _step each accept for this geometry (one size serves all:
- * the intermediates of the separable passes, and for the loop dL/dctrl, the loss terms and trx_flow_loss_grad's workspace).  0 = arguments
+/* Bytes of workspace that trx_bspline_expand, trx_bspline_reduce, trx_bspline_bending and trx_bspline_run / _step each accept for this geometry
+ * (one size serves all: the intermediates of the separable passes, for the loop dL/dctrl, the loss terms and trx_flow_loss_grad's workspace,
+ * and for the bending energy its Gram bands and one partial sum per lattice tile).  0 = arguments
  * rejected, as trx_resample_workspace_bytes.  Extension. */
 size_t trx_bspline_workspace_bytes(int ndim, int B, int D, int H, int W, int sz, int sy, int sx);
 
@@ -430,6 +431,24 @@ int trx_bspline_expand(const float *ctrl, const float *base /*nullable*/, float 
  * Extension; restatement: tests/bspline_ref.py::reduce. */
 int trx_bspline_reduce(const float *dflow, float *dctrl, int ndim, int B, int D, int H, int W, int sz, int sy, int sx, void *workspace,
                        size_t workspace_bytes, void *stream);
+
+/* Bending energy of the control lattice (the regulariser of Rueckert et al. 1999) and its gradient.  Extension.
+ * Per axis, the k-th-derivative weights with respect to the voxel coordinate, on control points i0 .. i0 + 3 at voxel x (i0, t as above):
+ *   k = 0: B0 .. B3;   k = 1: (1/d) [ -(1-t)^2/2, (3t^2 - 4t)/2, (-3t^2 + 2t + 1)/2, t^2/2 ];   k = 2: (1/d^2) [ 1-t, 3t-2, 1-3t, t ]
+ * (formed in fp64, stored in fp32).  M_a^(k) [S][G] holds them in row x, columns i0 .. i0 + 3.  With N = D H W:
+ *   E_b = (1/N) sum_c sum_{kz+ky+kx = 2} (2! / (kz! ky! kx!)) sum_voxels [ (ctrl_{b,c} x_z M_z^(kz) x_y M_y^(ky) x_x M_x^(kx))(voxel) ]^2
+ * - 3-D: zz, yy, xx once and zy, zx, yx twice; 2-D: yy, xx and 2 yx - exact second derivatives of the B-spline displacement (no `base`), in
+ * `flow`'s units, sampled at the voxel centres; an axis of one voxel has its one sample at t = 0.
+ * The kernels use the Gram form: R_a^(k) = M_a^(k)^T M_a^(k) ([G][G], banded: |i - j| <= 3; each entry summed in fp64 over its voxels in
+ * ascending x, stored in fp32), dE_b/dctrl_{b,c} = (2/N) sum_k mult_k (R_z^(kz) (x) R_y^(ky) (x) R_x^(kx)) ctrl_{b,c},
+ * E_b = 1/2 sum_c <ctrl_{b,c}, dE_b/dctrl_{b,c}>.  E is not clamped: for a lattice whose energy is zero (affine), rounding can leave a
+ * slightly negative value.
+ *   energy[b] = E_b (unweighted);   dctrl (nullable) = (accumulate ? dctrl : 0) + weight dE/dctrl.
+ * Three launches (the bands, the lattice tiles, the per-pair sum), no atomics, every sum in a fixed order: the same bits on every call, and a
+ * pair's result does not depend on the batch around it.  Status codes before any HIP call.  Workspace: trx_bspline_workspace_bytes.
+ * CPU restatement: tests/bspline_bending_ref.py. */
+int trx_bspline_bending(const float *ctrl, float *energy /*[B]*/, float *dctrl /*nullable*/, float weight, int accumulate, int ndim, int B, int D, int H,
+                        int W, int sz, int sy, int sx, void *workspace, size_t workspace_bytes, void *stream);
 
 /* State of the free-form-deformation loop, all device memory.  Early stop, step and flow_last as in trx_flow_state: the iteration whose recorded
  * loss is <= stop_crit still applies its update, every later iteration is a no-op for that pair, step[b] = number of recorded losses,
@@ -447,12 +466,16 @@ typedef struct {
     float stop_crit;
     int *stopped;       /* [B] in/out, 0 before the run; NULL disables the early stop */
     float *flow_last;   /* optional [B][ndim][D][H][W]: kept for a pair when it stops and on the last iteration of every call */
+    float bending_weight; /* lambda >= 0 of the bending-energy penalty (trx_bspline_bending); 0 = none: today's launches and bits.  Later addition
+                           * under TRX_VERSION 240: a caller built against the shorter struct must zero this field */
 } trx_bspline_state;
 
 /* One iteration / `iters` iterations back to back, no host sync, no allocation: expand -> trx_flow_loss_grad on the expanded flow (the fused
  * MSE / NCC / SSD loss of trx_loss_cfg and its dL/dflow) -> reduce -> per pair: losses[b][t] = terms[b][0], early stop, SGD or Adam on ctrl
  * (trx_opt_cfg's constants and bias correction).  spacing [host]: (sz, sy, sx).  Status codes before any HIP call; iters > losses_capacity:
- * TRX_ERR_CAPACITY.  Extension: arbiter = tests/bspline_ref.py::expand + oracle/compose.py (flow_warp, weighted_loss) under torch autograd. */
+ * TRX_ERR_CAPACITY.  With st->bending_weight = lambda > 0 the objective of pair b is L = data term + lambda E_b (trx_bspline_bending): the
+ * Gram bands are formed once per call, each iteration has one more launch (after reduce: dctrl += lambda dE/dctrl, the tiles' energies), and
+ * losses[b][t] and the early stop see the total; `base` receives nothing.  lambda < 0 or not finite: TRX_ERR_ARG.  Extension: arbiter = tests/bspline_ref.py::expand + oracle/compose.py (flow_warp, weighted_loss) under torch autograd. */
 int trx_bspline_step(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt, const trx_bspline_state *st,
                      const int *spacing /*[host]*/, void *workspace, size_t workspace_bytes, void *stream);
 int trx_bspline_run(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt, const trx_bspline_state *st,

@@ -482,14 +482,49 @@ def bspline_reduce(dflow, spacing):
     return dctrl
 
 
+def _bending_weight(value):
+    """A finite float >= 0, or ValueError."""
+    try:
+        w = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"bending_weight must be a finite number >= 0, got {value!r}") from None
+    if isinstance(value, bool) or not (w >= 0.0) or w == float("inf"):
+        raise ValueError(f"bending_weight must be a finite number >= 0, got {value!r}")
+    return w
+
+
+def bspline_bending(ctrl, spatial, spacing, grad=False):
+    """trx_bspline_bending: the bending energy E [B] of a control tensor [B, nd, *grid] (fp32, GPU) - per voxel, the squared second
+    derivatives of the B-spline displacement, mixed ones twice - and with grad=True (E, dE/dctrl)."""
+    _require_gpu(ctrl, "ctrl")
+    spatial = tuple(int(s) for s in spatial)
+    nd = len(spatial)
+    sp3 = _spacing3(spacing, nd)
+    B = ctrl.shape[0]
+    if tuple(ctrl.shape) != (B, nd) + bspline_grid(spatial, spacing):
+        raise ValueError(f"ctrl shape {tuple(ctrl.shape)} is not [B, {nd}, *{bspline_grid(spatial, spacing)}]")
+    lib = _lib.load()
+    ctrl = ctrl.detach().contiguous()
+    energy = torch.empty(B, dtype=torch.float32, device=ctrl.device)
+    dctrl = torch.empty_like(ctrl) if grad else None
+    ws, ws_bytes = _bspline_workspace(lib, nd, B, spatial, sp3, ctrl.device)
+    with torch.cuda.device(ctrl.device):
+        rc = lib.trx_bspline_bending(_lib.ptr(ctrl), _lib.ptr(energy), _lib.ptr(dctrl), 1.0, 0, nd, B, *_dhw(spatial), *sp3, _lib.ptr(ws), ws_bytes,
+                                     _lib.current_stream(ctrl.device))
+    _lib.check(rc, "trx_bspline_bending")
+    return (energy, dctrl) if grad else energy
+
+
 class BSplineSolver:
     """Cubic B-spline free-form deformation (extension): the control lattice `ctrl` [B, nd, *grid] is the parameter, the displacement field
     is base + expand(ctrl); the whole loop (expand, fused loss and dL/dflow, reduce, SGD / Adam, early stop) runs in trx_bspline_run.
-    After run(): `flow` = expand of the current ctrl (+ base), `flow_last` (keep_last or stop_crit) = the flow of the last forward."""
+    bending_weight = lambda > 0 adds lambda * (bending energy of ctrl, bspline_bending) to each pair's loss: `losses` and the early stop see
+    the total; `base` is not penalised.  After run(): `flow` = expand of the current ctrl (+ base), `flow_last` (keep_last or stop_crit) = the flow of the last forward."""
 
     def __init__(self, moving, target, spacing, loss=None, optimizer="sgd", lr=1e-3, init=None, base=None, capacity=1000, stop_crit=None,
-                 keep_last=False, betas=(0.9, 0.999), eps=1e-8):
+                 keep_last=False, betas=(0.9, 0.999), eps=1e-8, bending_weight=0.0):
         self.lib = _lib.load()
+        self.bending_weight = _bending_weight(bending_weight)
         self.batch = _Batch(moving, target, tables=False)
         if self.batch.C != 1:
             raise ValueError("the optimiser path takes single-channel volumes [B,1,...]")
@@ -536,6 +571,7 @@ class BSplineSolver:
         st.stop_crit = float(stop_crit) if stop_crit is not None else 0.0
         st.stopped = self.stopped.data_ptr() if self.stopped is not None else None
         st.flow_last = self.flow_last.data_ptr() if self.flow_last is not None else None
+        st.bending_weight = self.bending_weight
         self.state = st
         self.enqueued = 0
         self._expand()

@@ -67,7 +67,8 @@ class FlowState(ctypes.Structure):
 class BSplineState(ctypes.Structure):
     _fields_ = [("ctrl", ctypes.c_void_p), ("adam_m", ctypes.c_void_p), ("adam_v", ctypes.c_void_p), ("base", ctypes.c_void_p),
                 ("flow", ctypes.c_void_p), ("dflow", ctypes.c_void_p), ("losses", ctypes.c_void_p), ("losses_capacity", ctypes.c_int),
-                ("step", ctypes.c_void_p), ("stop_crit", ctypes.c_float), ("stopped", ctypes.c_void_p), ("flow_last", ctypes.c_void_p)]
+                ("step", ctypes.c_void_p), ("stop_crit", ctypes.c_float), ("stopped", ctypes.c_void_p), ("flow_last", ctypes.c_void_p),
+                ("bending_weight", ctypes.c_float)]
 
 
 # name -> (restype, argtypes); must list every symbol include/trx.h declares (tests check this)
@@ -138,6 +139,7 @@ SIGNATURES = {
     "trx_bspline_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 8),
     "trx_bspline_expand": (ctypes.c_int, [_P, _P, _P] + [ctypes.c_int] * 8 + [_P, ctypes.c_size_t, _P]),
     "trx_bspline_reduce": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 8 + [_P, ctypes.c_size_t, _P]),
+    "trx_bspline_bending": (ctypes.c_int, [_P, _P, _P, ctypes.c_float, ctypes.c_int] + [ctypes.c_int] * 8 + [_P, ctypes.c_size_t, _P]),
     "trx_bspline_step": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(LossCfg), ctypes.POINTER(OptCfg), ctypes.POINTER(BSplineState), c_int_p,
                                         _P, ctypes.c_size_t, _P]),
     "trx_bspline_run": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(LossCfg), ctypes.POINTER(OptCfg), ctypes.POINTER(BSplineState), c_int_p,

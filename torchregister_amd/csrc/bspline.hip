@@ -1,6 +1,7 @@
 // Cubic B-spline free-form deformation (Rueckert et al. 1999; extension, the reference has no such model): the operator between a control
 // lattice and a dense flow (trx_bspline_expand), its exact adjoint (trx_bspline_reduce) and a device-side optimisation loop over them
-// (trx_bspline_run).  CPU restatement: tests/bspline_ref.py.
+// (trx_bspline_run), and the bending energy of the lattice with its gradient (trx_bspline_bending; in the loop: trx_bspline_state.bending_weight).
+// CPU restatements: tests/bspline_ref.py, tests/bspline_bending_ref.py.
 //
 // Definition (include/trx.h): an axis of S voxels with spacing d has G = (S - 1) / d + 4 control points, point i at voxel (i - 1) d; at
 // voxel x, i0 = x / d, t = (x % d) / d and the four weights B0..B3(t) of the uniform cubic B-spline act on points i0 .. i0 + 3 (always
@@ -21,6 +22,7 @@
 #include "trx_common.h"
 
 #include <algorithm>
+#include <cmath>
 
 namespace trx {
 
@@ -225,13 +227,14 @@ struct BsCoef {
 };
 constexpr int kBsNormal = 0, kBsHit = 1, kBsSkip = 2;
 
-// One thread per pair: the loss curve, the step counter, the early stop (trx_flow_state's semantics: the iteration that meets stop_crit
-// still applies its update, later ones are no-ops) and the Adam scalars of this iteration.
-__global__ void bspline_decide_kernel(const float *__restrict__ terms, int B, trx_opt_cfg oc, float *__restrict__ losses, int losses_capacity,
-                                      int *__restrict__ step, float stop_crit, int *__restrict__ stopped, BsCoef *__restrict__ coef)
+// One pair: the loss curve, the step counter, the early stop (trx_flow_state's semantics: the iteration that meets stop_crit still applies
+// its update, later ones are no-ops) and the Adam scalars of this iteration.  `penalty` = lambda E_b joins the data term before the
+// early stop and the record (BEND only).
+template <bool BEND>
+__device__ __forceinline__ void bspline_decide_pair(int b, float penalty, const float *__restrict__ terms, const trx_opt_cfg &oc, float *__restrict__ losses,
+                                                    int losses_capacity, int *__restrict__ step, float stop_crit, int *__restrict__ stopped,
+                                                    BsCoef *__restrict__ coef)
 {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
     BsCoef c;
     if (stopped && stopped[b] != 0) {
         c.step_size = 0.f; c.inv_sqrt_bc2 = 1.f; c.mode = kBsSkip;
@@ -239,7 +242,8 @@ __global__ void bspline_decide_kernel(const float *__restrict__ terms, int B, tr
         return;
     }
     const int t = step[b];
-    const float total = terms[b * 4];
+    float total = terms[b * 4];
+    if constexpr (BEND) total += penalty;
     if (oc.kind == TRX_OPT_ADAM) {
         const double bc1 = 1.0 - ipow((double)oc.beta1, t + 1), bc2 = 1.0 - ipow((double)oc.beta2, t + 1);
         c.step_size = (float)((double)oc.lr / bc1);
@@ -256,6 +260,15 @@ __global__ void bspline_decide_kernel(const float *__restrict__ terms, int B, tr
     coef[b] = c;
     if (losses && t < losses_capacity) losses[(size_t)b * losses_capacity + t] = total;
     step[b] = t + 1;
+}
+
+// One thread per pair (bending_weight = 0)
+__global__ void bspline_decide_kernel(const float *__restrict__ terms, int B, trx_opt_cfg oc, float *__restrict__ losses, int losses_capacity,
+                                      int *__restrict__ step, float stop_crit, int *__restrict__ stopped, BsCoef *__restrict__ coef)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    bspline_decide_pair<false>(b, 0.f, terms, oc, losses, losses_capacity, step, stop_crit, stopped, coef);
 }
 
 // SGD / Adam on the control points of pair blockIdx.y (the arithmetic of flow_update_kernel, csrc/flow.hip), and - when the caller keeps
@@ -291,12 +304,232 @@ __global__ __launch_bounds__(TRX_BLOCK) void bspline_update_kernel(float *__rest
     }
 }
 
+// ---- Bending energy (include/trx.h: trx_bspline_bending; CPU restatement: tests/bspline_bending_ref.py) ----------------------------------
+// Gram form: with R_a^(k) = M_a^(k)^T M_a^(k) ([G][G], non-zero only for |i - j| <= 3),
+//   g = dE/dctrl_c = (2 / N) sum_{kz + ky + kx = 2} mult_k (R_z^(kz) (x) R_y^(ky) (x) R_x^(kx)) ctrl_c,   E = 1/2 sum_c <ctrl_c, g>.
+// bspline_gram_kernel writes the bands R[a][k][G_a][7] once per call; bspline_bending_kernel applies them to lattice tiles in LDS.
+
+// weight l of the k-th derivative (with respect to the voxel coordinate) of the cubic B-spline at t, fp64
+__device__ __forceinline__ double bspline_dweight(int k, int l, double t, double d)
+{
+    const double u = 1.0 - t, t2 = t * t;
+    double w;
+    if (k == 0) {
+        const double t3 = t2 * t;
+        w = l == 0 ? u * u * u / 6.0 : l == 1 ? (3.0 * t3 - 6.0 * t2 + 4.0) / 6.0 : l == 2 ? (-3.0 * t3 + 3.0 * t2 + 3.0 * t + 1.0) / 6.0 : t3 / 6.0;
+        return w;
+    }
+    if (k == 1) {
+        w = l == 0 ? -u * u / 2.0 : l == 1 ? (3.0 * t2 - 4.0 * t) / 2.0 : l == 2 ? (-3.0 * t2 + 2.0 * t + 1.0) / 2.0 : t2 / 2.0;
+        return w / d;
+    }
+    w = l == 0 ? u : l == 1 ? 3.0 * t - 2.0 : l == 2 ? 1.0 - 3.0 * t : t;
+    return w / (d * d);
+}
+
+struct BendAxes {
+    int S[3], d[3], G[3];
+};
+
+// R[a][k][i][m] = sum_x M_a^(k)[x][i] M_a^(k)[x][i + m - 3] (0 where i + m - 3 is outside the lattice): one thread per entry, the at most
+// 4 d voxels that both control points see in ascending x, the fp32 weights multiplied and summed in fp64, stored as fp32.
+__global__ __launch_bounds__(TRX_BLOCK) void bspline_gram_kernel(float *__restrict__ R, BendAxes ax)
+{
+    const int n0 = 21 * ax.G[0], n1 = 21 * ax.G[1], n = n0 + n1 + 21 * ax.G[2];
+    for (int e = blockIdx.x * TRX_BLOCK + threadIdx.x; e < n; e += gridDim.x * TRX_BLOCK) {
+        const int a = e < n0 ? 0 : e < n0 + n1 ? 1 : 2;
+        const int r = e - (a == 0 ? 0 : a == 1 ? n0 : n0 + n1);
+        const int S = ax.S[a], d = ax.d[a], G = ax.G[a];
+        const int k = r / (7 * G), i = r / 7 % G, j = i + r % 7 - 3;
+        double s = 0.0;
+        if (j >= 0 && j < G) {
+            for (int c = max(max(i, j) - 3, 0); c <= min(i, j); c++) {      // the cells (i0) whose four points hold both i and j
+                const long x0 = (long)c * d;
+                if (x0 >= S) break;
+                const int nx = (int)min((long)d, (long)S - x0);
+                for (int rr = 0; rr < nx; rr++) {
+                    const double t = (double)rr / (double)d;
+                    s += (double)(float)bspline_dweight(k, i - c, t, (double)d) * (double)(float)bspline_dweight(k, j - c, t, (double)d);
+                }
+            }
+        }
+        R[e] = (float)s;
+    }
+}
+
+// Output tile of the bending kernel and its input tile (a halo of 3 points on every axis that has a band); 2-D has no z axis.
+template <int ND> struct BendTile {
+    static constexpr int TZ = ND == 3 ? 8 : 1, TY = ND == 3 ? 8 : 16, TX = ND == 3 ? 8 : 32, HZ = ND == 3 ? 3 : 0;
+    static constexpr int IZ = TZ + 2 * HZ, IY = TY + 6, IX = TX + 6;
+    static constexpr int NA = ND == 3 ? 3 : 1;     // arrays behind the y pass: one per kz
+    static constexpr int TMAX = TX;                // the longest tile edge
+    static constexpr int PL = TY * TX;             // outputs per z plane
+};
+
+// One lattice tile of one volume (pair and channel) per step of a block:
+//   load   the tile with its halo (zeros outside the lattice) and the bands' rows of the tile into LDS;
+//   x pass X_k = R_x^(k) tile, k = 0, 1, 2                                       [IZ][IY][TX] each;
+//   y pass the six products R_y^(ky) X_kx with kx + ky <= 2, summed by the kz = 2 - kx - ky they meet in the z pass, with their
+//          multiplicities: A_0 = Y_20 + Y_02 + 2 Y_11, A_1 = 2 (Y_10 + Y_01), A_2 = Y_00   [IZ][TY][TX] each (2-D: A_0 is the result);
+//   z pass g = (2 / N) sum_kz R_z^(kz) A_kz, dctrl (+)= weight g, and 1/2 sum c g over the tile -> partials[volume][tile].
+// A thread keeps its x (x pass) or its (y, x) (y pass) and with it its 21 band coefficients in registers.  No atomics; the tile's energy is
+// summed in fp64 by a fixed tree.
+template <int ND>
+__global__ __launch_bounds__(TRX_BLOCK) void bspline_bending_kernel(const float *__restrict__ ctrl, const float *__restrict__ R, float *__restrict__ dctrl,
+                                                                      float *__restrict__ partials, int nvol, int Gz, int Gy, int Gx, int nty, int ntx,
+                                                                      unsigned ntile, float scale, float weight, int accumulate)
+{
+    using T = BendTile<ND>;
+    __shared__ float s_in[T::IZ * T::IY * T::IX];
+    __shared__ float s_x[3][T::IZ * T::IY * T::TX];
+    __shared__ float s_a[T::NA][T::IZ * T::PL];
+    __shared__ float s_r[3][3][T::TMAX][7];        // [axis][k][row of the tile][tap]
+    __shared__ double s_red[TRX_WAVES];
+    const int tid = threadIdx.x;
+    const float *Rax[3] = {R, R + 21 * Gz, R + 21 * (Gz + Gy)};
+    const int G[3] = {Gz, Gy, Gx}, TT[3] = {T::TZ, T::TY, T::TX};
+    const size_t nlat = (size_t)Gz * Gy * Gx;
+    for (int v = blockIdx.y; v < nvol; v += gridDim.y) {
+        const float *src = ctrl + (size_t)v * nlat;
+        float *dst = dctrl ? dctrl + (size_t)v * nlat : nullptr;
+        for (unsigned t = blockIdx.x; t < ntile; t += gridDim.x) {
+            const int tx = (int)(t % (unsigned)ntx), ty = (int)(t / (unsigned)ntx % (unsigned)nty), tz = (int)(t / (unsigned)ntx / (unsigned)nty);
+            const int o[3] = {tz * T::TZ, ty * T::TY, tx * T::TX};
+            for (int e = tid; e < 3 * 3 * T::TMAX * 7; e += TRX_BLOCK) {
+                const int tap = e % 7, row = e / 7 % T::TMAX, k = e / (7 * T::TMAX) % 3, a = e / (21 * T::TMAX);
+                const int i = o[a] + row;
+                const bool live = (ND == 3 || a > 0) && row < TT[a] && i < G[a];
+                s_r[a][k][row][tap] = live ? Rax[a][((size_t)k * G[a] + i) * 7 + tap] : 0.f;
+            }
+            for (int e = tid; e < T::IZ * T::IY * T::IX; e += TRX_BLOCK) {
+                const int gx = o[2] + e % T::IX - 3, gy = o[1] + e / T::IX % T::IY - 3, gz = o[0] + e / (T::IX * T::IY) - T::HZ;
+                const bool inside = gx >= 0 && gx < Gx && gy >= 0 && gy < Gy && gz >= 0 && gz < Gz;
+                s_in[e] = inside ? src[((size_t)gz * Gy + gy) * Gx + gx] : 0.f;
+            }
+            __syncthreads();
+            {   // x pass
+                const int xo = tid % T::TX;
+                float r[3][7];
+#pragma unroll
+                for (int k = 0; k < 3; k++)
+#pragma unroll
+                    for (int m = 0; m < 7; m++) r[k][m] = s_r[2][k][xo][m];
+                for (int row = tid / T::TX; row < T::IZ * T::IY; row += TRX_BLOCK / T::TX) {
+                    const float *p = s_in + row * T::IX + xo;
+                    float c[7];
+#pragma unroll
+                    for (int m = 0; m < 7; m++) c[m] = p[m];
+#pragma unroll
+                    for (int k = 0; k < 3; k++) {
+                        float acc = r[k][0] * c[0];
+#pragma unroll
+                        for (int m = 1; m < 7; m++) acc = fmaf(r[k][m], c[m], acc);
+                        s_x[k][row * T::TX + xo] = acc;
+                    }
+                }
+            }
+            __syncthreads();
+            for (int q = tid % T::PL; q < T::PL; q += TRX_BLOCK) {   // y pass
+                const int xo = q % T::TX, yo = q / T::TX;
+                float r[3][7];
+#pragma unroll
+                for (int k = 0; k < 3; k++)
+#pragma unroll
+                    for (int m = 0; m < 7; m++) r[k][m] = s_r[1][k][yo][m];
+                for (int iz = T::PL < TRX_BLOCK ? tid / T::PL : 0; iz < T::IZ; iz += T::PL < TRX_BLOCK ? TRX_BLOCK / T::PL : 1) {
+                    const int base = (iz * T::IY + yo) * T::TX + xo;
+                    float y00 = 0.f, y10 = 0.f, y20 = 0.f, y01 = 0.f, y11 = 0.f, y02 = 0.f;
+#pragma unroll
+                    for (int m = 0; m < 7; m++) {
+                        const float x0 = s_x[0][base + m * T::TX], x1 = s_x[1][base + m * T::TX], x2 = s_x[2][base + m * T::TX];
+                        y00 = fmaf(r[0][m], x0, y00); y10 = fmaf(r[0][m], x1, y10); y20 = fmaf(r[0][m], x2, y20);
+                        y01 = fmaf(r[1][m], x0, y01); y11 = fmaf(r[1][m], x1, y11);
+                        y02 = fmaf(r[2][m], x0, y02);
+                    }
+                    s_a[0][iz * T::PL + q] = (y20 + y02) + 2.f * y11;
+                    if constexpr (ND == 3) {
+                        s_a[1][iz * T::PL + q] = 2.f * (y10 + y01);
+                        s_a[2][iz * T::PL + q] = y00;
+                    }
+                }
+            }
+            __syncthreads();
+            double part = 0.0;
+            for (int e = tid; e < T::TZ * T::PL; e += TRX_BLOCK) {   // z pass, the gradient and the tile's energy
+                const int q = e % T::PL, zo = e / T::PL, xo = q % T::TX, yo = q / T::TX;
+                float g;
+                if constexpr (ND == 3) {
+                    g = 0.f;
+#pragma unroll
+                    for (int k = 0; k < 3; k++)
+#pragma unroll
+                        for (int m = 0; m < 7; m++) g = fmaf(s_r[0][k][zo][m], s_a[k][(zo + m) * T::PL + q], g);
+                } else {
+                    g = s_a[0][q];
+                }
+                g *= scale;
+                const int gz = o[0] + zo, gy = o[1] + yo, gx = o[2] + xo;
+                if (gz < Gz && gy < Gy && gx < Gx) {
+                    part += (double)(s_in[((zo + T::HZ) * T::IY + yo + 3) * T::IX + xo + 3] * g);
+                    if (dst) {
+                        const size_t i = ((size_t)gz * Gy + gy) * Gx + gx;
+                        dst[i] = accumulate ? fmaf(weight, g, dst[i]) : weight * g;
+                    }
+                }
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) part += __shfl_down(part, off, 64);
+            if ((tid & 63) == 0) s_red[tid >> 6] = part;
+            __syncthreads();
+            if (tid == 0) partials[(size_t)v * ntile + t] = (float)(0.5 * (((s_red[0] + s_red[1]) + s_red[2]) + s_red[3]));
+            __syncthreads();
+        }
+    }
+}
+
+// Sum of n partials by the 64 threads of a block, in ascending order: thread l sums the l-th of 64 contiguous runs, then the 64 run sums are
+// added in ascending l; fp64 throughout.  Every thread gets the total.
+__device__ __forceinline__ double bspline_sum_partials(const float *__restrict__ p, int n)
+{
+    __shared__ double s_run[64];
+    const int run = (n + 63) / 64, lo = min(n, (int)threadIdx.x * run), hi = min(n, lo + run);
+    double s = 0.0;
+    for (int i = lo; i < hi; i++) s += (double)p[i];
+    s_run[threadIdx.x] = s;
+    __syncthreads();
+    double total = 0.0;
+    for (int l = 0; l < 64; l++) total += s_run[l];
+    return total;
+}
+
+// energy[b] = sum of the pair's partials (its ndim volumes, tiles in ascending order); one block of 64 threads per pair
+__global__ __launch_bounds__(64) void bspline_energy_kernel(const float *__restrict__ partials, int per_pair, float *__restrict__ energy)
+{
+    const double e = bspline_sum_partials(partials + (size_t)blockIdx.x * per_pair, per_pair);
+    if (threadIdx.x == 0) energy[blockIdx.x] = (float)e;
+}
+
+// bspline_decide_kernel with the penalty: one block of 64 threads per pair sums the pair's partials, thread 0 decides on
+// terms[b][0] + lambda E_b
+__global__ __launch_bounds__(64) void bspline_decide_bending_kernel(const float *__restrict__ terms, const float *__restrict__ partials, int per_pair,
+                                                                      float lambda, trx_opt_cfg oc, float *__restrict__ losses, int losses_capacity,
+                                                                      int *__restrict__ step, float stop_crit, int *__restrict__ stopped,
+                                                                      BsCoef *__restrict__ coef)
+{
+    const int b = blockIdx.x;
+    const double e = bspline_sum_partials(partials + (size_t)b * per_pair, per_pair);
+    if (threadIdx.x == 0) bspline_decide_pair<true>(b, lambda * (float)e, terms, oc, losses, losses_capacity, step, stop_crit, stopped, coef);
+}
+
 struct BsGeom {
     int ndim, B, S[3], d[3], G[3];   // axes z, y, x (2-D: S[0] = G[0] = d[0] = 1, no z pass)
     size_t t1, t2;                   // floats per volume (pair and channel) of [D][Gy][Gx] and [D][H][Gx]
     size_t t2_offset;                // floats from the workspace's start to the [D][H][Gx] intermediates
     size_t lattice_bytes;            // both intermediates of all volumes
     size_t terms_offset, coef_offset, dctrl_offset, flow_offset, flow_bytes, ws_bytes;   // the loop's part: terms[B][4], BsCoef[B], dL/dctrl, trx_flow_loss_grad's workspace
+    int bend_nt[3];                  // tiles of the bending kernel per axis
+    size_t bend_ntile;               // per volume
+    size_t gram_offset, part_offset; // the bending energy's part: the bands R[a][k][G_a][7], partials[B ndim][bend_ntile]
 };
 
 static int bspline_geom(int ndim, int B, int D, int H, int W, int sz, int sy, int sx, BsGeom *g)
@@ -324,7 +557,12 @@ static int bspline_geom(int ndim, int B, int D, int H, int W, int sz, int sy, in
     g->coef_offset = g->terms_offset + (((size_t)B * 4 * sizeof(float) + 255) & ~(size_t)255);
     g->dctrl_offset = g->coef_offset + (((size_t)B * sizeof(BsCoef) + 255) & ~(size_t)255);
     g->flow_offset = g->dctrl_offset + ((nvol * g->G[0] * g->G[1] * g->G[2] * sizeof(float) + 255) & ~(size_t)255);
-    g->ws_bytes = g->flow_offset + g->flow_bytes;
+    const int tile[3] = {ndim == 3 ? BendTile<3>::TZ : BendTile<2>::TZ, ndim == 3 ? BendTile<3>::TY : BendTile<2>::TY, ndim == 3 ? BendTile<3>::TX : BendTile<2>::TX};
+    for (int a = 0; a < 3; a++) g->bend_nt[a] = (g->G[a] + tile[a] - 1) / tile[a];
+    g->bend_ntile = (size_t)g->bend_nt[0] * g->bend_nt[1] * g->bend_nt[2];
+    g->gram_offset = (g->flow_offset + g->flow_bytes + 255) & ~(size_t)255;
+    g->part_offset = g->gram_offset + (((size_t)21 * ((size_t)g->G[0] + g->G[1] + g->G[2]) * sizeof(float) + 255) & ~(size_t)255);
+    g->ws_bytes = g->part_offset + ((nvol * g->bend_ntile * sizeof(float) + 255) & ~(size_t)255);
     return TRX_OK;
 }
 
@@ -397,6 +635,35 @@ static int bspline_reduce_impl(const BsGeom &g, const float *dflow, float *dctrl
     return TRX_OK;
 }
 
+static int bspline_gram_impl(const BsGeom &g, void *workspace, hipStream_t s)
+{
+    BendAxes ax;
+    for (int a = 0; a < 3; a++) { ax.S[a] = g.S[a]; ax.d[a] = g.d[a]; ax.G[a] = g.G[a]; }
+    const int n = 21 * (g.G[0] + g.G[1] + g.G[2]);
+    hipLaunchKernelGGL(bspline_gram_kernel, dim3((unsigned)std::min(1024, (n + TRX_BLOCK - 1) / TRX_BLOCK)), dim3(TRX_BLOCK), 0, s,
+                       (float *)((char *)workspace + g.gram_offset), ax);
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
+
+// dctrl (nullable) = (accumulate ? dctrl : 0) + weight dE/dctrl, and the tiles' energies into the workspace; the bands must be there
+static int bspline_bending_impl(const BsGeom &g, const float *ctrl, float *dctrl, float weight, int accumulate, void *workspace, hipStream_t s)
+{
+    const int nvol = g.B * g.ndim;
+    const float *R = (const float *)((char *)workspace + g.gram_offset);
+    float *partials = (float *)((char *)workspace + g.part_offset);
+    const float scale = (float)(2.0 / ((double)g.S[0] * g.S[1] * g.S[2]));
+    const dim3 grid = bs_grid(g.bend_ntile, nvol);
+    if (g.ndim == 3)
+        hipLaunchKernelGGL(bspline_bending_kernel<3>, grid, dim3(TRX_BLOCK), 0, s, ctrl, R, dctrl, partials, nvol, g.G[0], g.G[1], g.G[2], g.bend_nt[1],
+                           g.bend_nt[2], (unsigned)g.bend_ntile, scale, weight, accumulate);
+    else
+        hipLaunchKernelGGL(bspline_bending_kernel<2>, grid, dim3(TRX_BLOCK), 0, s, ctrl, R, dctrl, partials, nvol, g.G[0], g.G[1], g.G[2], g.bend_nt[1],
+                           g.bend_nt[2], (unsigned)g.bend_ntile, scale, weight, accumulate);
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
+
 }  // namespace trx
 
 using namespace trx;
@@ -440,6 +707,23 @@ extern "C" int trx_bspline_reduce(const float *dflow, float *dctrl, int ndim, in
     return bspline_reduce_impl(g, dflow, dctrl, workspace, (hipStream_t)stream);
 }
 
+extern "C" int trx_bspline_bending(const float *ctrl, float *energy, float *dctrl, float weight, int accumulate, int ndim, int B, int D, int H, int W,
+                                   int sz, int sy, int sx, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!ctrl || !energy || !workspace) return TRX_ERR_ARG;
+    BsGeom g;
+    int rc = bspline_geom(ndim, B, D, H, W, sz, sy, sx, &g);
+    if (rc != TRX_OK) return rc;
+    if (workspace_bytes < g.ws_bytes) return TRX_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    if ((rc = bspline_gram_impl(g, workspace, s)) != TRX_OK) return rc;
+    if ((rc = bspline_bending_impl(g, ctrl, dctrl, weight, accumulate, workspace, s)) != TRX_OK) return rc;
+    hipLaunchKernelGGL(bspline_energy_kernel, dim3((unsigned)B), dim3(64), 0, s, (const float *)((char *)workspace + g.part_offset),
+                       (int)(g.ndim * g.bend_ntile), energy);
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
+
 extern "C" int trx_bspline_run(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt, const trx_bspline_state *st, const int *spacing,
                                int iters, void *workspace, size_t workspace_bytes, void *stream)
 {
@@ -451,6 +735,8 @@ extern "C" int trx_bspline_run(const trx_volumes *vol, const trx_loss_cfg *loss,
     if (opt->kind != TRX_OPT_SGD && opt->kind != TRX_OPT_ADAM) return TRX_ERR_ARG;
     if (opt->kind == TRX_OPT_ADAM && (!st->adam_m || !st->adam_v)) return TRX_ERR_ARG;
     if (iters < 0 || (st->losses && st->losses_capacity < 0)) return TRX_ERR_ARG;
+    const float lambda = st->bending_weight;
+    if (!(lambda >= 0.f) || !std::isfinite(lambda)) return TRX_ERR_ARG;
     if (workspace_bytes < g.ws_bytes) return TRX_ERR_WORKSPACE;
     if (st->losses && iters > st->losses_capacity) return TRX_ERR_CAPACITY;
     hipStream_t s = (hipStream_t)stream;
@@ -461,12 +747,20 @@ extern "C" int trx_bspline_run(const trx_volumes *vol, const trx_loss_cfg *loss,
     const size_t nctrl = (size_t)g.ndim * g.G[0] * g.G[1] * g.G[2], nflow = (size_t)g.ndim * vol->D * vol->H * vol->W;
     const size_t work = std::max(nctrl, st->flow_last ? nflow : (size_t)0);
     const dim3 ugrid((unsigned)std::max<size_t>(1, std::min<size_t>((work + TRX_BLOCK - 1) / TRX_BLOCK, std::max(1, 2048 / vol->B))), (unsigned)vol->B);
+    const bool bend = lambda > 0.f;
+    if (bend && iters > 0 && (rc = bspline_gram_impl(g, workspace, s)) != TRX_OK) return rc;   // once per call: the bands depend on the geometry alone
     for (int i = 0; i < iters; i++) {
         if ((rc = bspline_expand_impl(g, st->ctrl, st->base, st->flow, workspace, s)) != TRX_OK) return rc;
         if ((rc = trx_flow_loss_grad(vol, loss, st->flow, terms, st->dflow, ws + g.flow_offset, g.flow_bytes, stream)) != TRX_OK) return rc;
         if ((rc = bspline_reduce_impl(g, st->dflow, dctrl, workspace, s)) != TRX_OK) return rc;
-        hipLaunchKernelGGL(bspline_decide_kernel, dim3((vol->B + 63) / 64), dim3(64), 0, s, (const float *)terms, vol->B, *opt, st->losses, st->losses_capacity,
-                           st->step, st->stop_crit, st->stopped, coef);
+        if (bend) {
+            if ((rc = bspline_bending_impl(g, st->ctrl, dctrl, lambda, 1, workspace, s)) != TRX_OK) return rc;
+            hipLaunchKernelGGL(bspline_decide_bending_kernel, dim3((unsigned)vol->B), dim3(64), 0, s, (const float *)terms, (const float *)(ws + g.part_offset),
+                               (int)(g.ndim * g.bend_ntile), lambda, *opt, st->losses, st->losses_capacity, st->step, st->stop_crit, st->stopped, coef);
+        } else {
+            hipLaunchKernelGGL(bspline_decide_kernel, dim3((vol->B + 63) / 64), dim3(64), 0, s, (const float *)terms, vol->B, *opt, st->losses,
+                               st->losses_capacity, st->step, st->stop_crit, st->stopped, coef);
+        }
         TRX_CHECK_LAUNCH();
         hipLaunchKernelGGL(bspline_update_kernel, ugrid, dim3(TRX_BLOCK), 0, s, st->ctrl, (const float *)dctrl, st->adam_m, st->adam_v, nctrl,
                            (const BsCoef *)coef, *opt, (const float *)st->flow, st->flow_last, nflow, i + 1 == iters ? 1 : 0);

@@ -9,6 +9,7 @@ U-Net-generated flow, 'direct' = the flow field itself is the parameter), levels
 import torch
 from torch import cat
 
+from ._engine import _bending_weight
 from .pyramid import pyramid, pyramid_shapes, upsample_flow
 from .warpings import affine_register, flow_register, get_affine_warp, rigid_register
 
@@ -24,7 +25,8 @@ def _per_level(value, levels, name):
 
 class Register():
     def __init__(self, mode='rigid', device='cpu', criterion=None, weight=None, grad_edges=False, debug=False, *,
-                 optimizer='sgd', honor_criterion=False, init=None, smooth_weight=0.0, flow_model='unet', levels=1, spacing=None):
+                 optimizer='sgd', honor_criterion=False, init=None, smooth_weight=0.0, flow_model='unet', levels=1, spacing=None,
+                 bending_weight=0.0):
         '''
         Numerical registration on an AMD GPU (MI355X) behind the TorchRegister API.
 
@@ -46,6 +48,10 @@ class Register():
             `spacing` voxels between control points (an int or one per axis, default 8).  After optim, `.control` is the final control tensor
             (the finest level's).  With levels > 1 the spacing in voxels is the same at every level, every level starts from a zero control
             tensor and adds to base = upsample_flow(the previous level's final dense flow): multi-level FFD as a sum of levels.
+        bending_weight : (keyword-only extension, flow_model='bspline' only) lambda >= 0: lambda * (bending energy of the control lattice,
+            bspline_bending) joins each pair's loss; `.losses` and the early stop see the total.  With levels > 1 the same lambda applies to
+            each level's own lattice: the energy is per voxel of that level, in that level's voxel coordinates, nothing is rescaled between
+            levels, and the base handed up from the coarser levels is not penalised.
         '''
         if mode not in ('rigid', 'affine', 'flow'):
             raise ValueError("mode must be 'rigid', 'affine' or 'flow'")
@@ -60,7 +66,10 @@ class Register():
             if any(isinstance(v, bool) or not isinstance(v, int) or v < 1 for v in each) or len(each) > 3:
                 raise ValueError(f"spacing must be an int >= 1 or one per axis, got {spacing!r}")
             if smooth_weight != 0:
-                raise ValueError("flow_model='bspline' takes no smooth_weight: the control lattice is the regulariser")
+                raise ValueError("flow_model='bspline' takes no smooth_weight: its regularisers are the control-point spacing and bending_weight")
+        bending_weight = _bending_weight(bending_weight)
+        if bending_weight != 0 and not (mode == 'flow' and flow_model == 'bspline'):
+            raise ValueError("bending_weight is the bending-energy penalty of mode='flow' with flow_model='bspline'")
         self.criterion = criterion
         self.weight = weight
         self.mode = mode
@@ -75,6 +84,7 @@ class Register():
         self.smooth_weight = smooth_weight
         self.flow_model = flow_model
         self.spacing = spacing
+        self.bending_weight = bending_weight
         self.levels = levels
         self.control = None
         self.losses = None
@@ -87,7 +97,7 @@ class Register():
         kw = dict(mode='bilinear', n=n, lr=lr, max_epochs=max_epochs, optimizer=self.optimizer, smooth_weight=self.smooth_weight,
                   flow_model=self.flow_model)
         if self.flow_model == 'bspline':
-            kw.update(spacing=self.spacing)
+            kw.update(spacing=self.spacing, bending_weight=self.bending_weight)
         if self.criterion is not None and self.weight is not None:           # ref:torchregister.py:71-73
             kw.update(criterions=self.criterion, weights=self.weight)
         elif self.weight is not None:                                         # ref:torchregister.py:74-76

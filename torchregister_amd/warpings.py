@@ -377,22 +377,28 @@ class flow_register(nn.Module):
     `optimize` reports 'Converged' only when every pair has stopped (`.iterations` holds the per-pair counts).
     flow_model='bspline' (extension): cubic B-spline free-form deformation - a control lattice with `spacing` voxels between control
     points (an int or one per axis) parameterises the flow, flow = base_flow + expand(control), optimised by trx_bspline_run like
-    'direct' (fused MSE / NCC / SSD criteria only; smooth by construction, so smooth_weight must stay 0).  `.control` is the final
+    'direct' (fused MSE / NCC / SSD criteria only; smooth_weight must stay 0).  bending_weight = lambda > 0 adds lambda * (bending energy of
+    the control lattice, bspline_bending: per voxel of this image size, in its voxel coordinates) to each pair's loss - `.losses` and
+    stop_crit see the total, `base_flow` is not penalised; the other flow models raise for it.  `.control` is the final
     control tensor [B, nd, *grid]; `.init_control` (None = zero) and `.base_flow` (None = none) set the start."""
 
     def __init__(self, img_size, mode="bilinear", in_c=1, n=1, criterions=None, weights=[0.33, 0.33, 0.33], lr=1E-3,
-                 max_epochs=2000, stop_crit=1E-4, *, flow_model="unet", optimizer="sgd", smooth_weight=0.0, spacing=None):
+                 max_epochs=2000, stop_crit=1E-4, *, flow_model="unet", optimizer="sgd", smooth_weight=0.0, spacing=None,
+                 bending_weight=0.0):
         super().__init__()
         if flow_model not in ("unet", "direct", "bspline"):
             raise ValueError("flow_model must be 'unet', 'direct' or 'bspline'")
         self.img_size = tuple(int(s) for s in img_size)
         if flow_model != "bspline" and spacing is not None:
             raise ValueError(f"spacing is the control-point spacing of flow_model='bspline'; flow_model={flow_model!r} has none")
+        self.bending_weight = _engine._bending_weight(bending_weight)
+        if flow_model != "bspline" and self.bending_weight != 0:
+            raise ValueError(f"bending_weight is the bending-energy penalty of flow_model='bspline'; flow_model={flow_model!r} has no control lattice")
         self.spacing = None
         if flow_model == "bspline":
             self.spacing = _engine._spacing3(8 if spacing is None else spacing, len(self.img_size))[3 - len(self.img_size):]
             if smooth_weight != 0:
-                raise ValueError("flow_model='bspline' takes no smooth_weight: the control lattice is the regulariser (choose a larger spacing)")
+                raise ValueError("flow_model='bspline' takes no smooth_weight: its regularisers are the control-point spacing and bending_weight")
             used = [nn.MSELoss(), NCCLoss(), NMILoss()] if criterions is None else criterions
             if loss_spec_from(used, weights[: len(used)]) is None:
                 raise ValueError("flow_model='bspline' runs the fused criteria only: nn.MSELoss (mean), NCCLoss and SSDLoss, "
@@ -470,7 +476,8 @@ class flow_register(nn.Module):
         """The 'direct' loop with a control lattice as the parameter: one trx_bspline_run call, per-pair early stop on the device, one host sync."""
         from ._engine import BSplineSolver
         solver = BSplineSolver(moving, target, self.spacing, loss=spec, optimizer=self.optimizer_kind, lr=self.lr, init=self.init_control,
-                               base=self.base_flow, capacity=max(1, self.max_epochs), stop_crit=self.stop_crit, keep_last=True)
+                               base=self.base_flow, capacity=max(1, self.max_epochs), stop_crit=self.stop_crit, keep_last=True,
+                               bending_weight=self.bending_weight)
         solver.run(self.max_epochs)
         done = solver.step.cpu()
         n = int(done.max()) if self.max_epochs > 0 else 0
