@@ -43,7 +43,9 @@ extern "C" {
  *        Later addition under the same number: trx_resample / trx_resample_workspace_bytes (the levels of a coarse-to-fine pyramid and the flow
  *        hand-over between them) - new entry points only, no existing signature or struct changed.
  *        Later addition under the same number: trx_bspline_* and trx_bspline_state (cubic B-spline free-form deformation: control lattice <-> dense
- *        flow, its adjoint, and the device-side loop over them) - new entry points and one new struct only. */
+ *        flow, its adjoint, and the device-side loop over them) - new entry points and one new struct only.
+ *        Later addition under the same number: trx_mi_* , trx_flow_mi_* , trx_bspline_mi_* and trx_mi_cfg (Parzen joint-histogram mutual information
+ *        and the two device-side loops over it) - new entry points and one new struct only. */
 #define TRX_VERSION 240
 #define TRX_PSTRIDE 12  /* floats per pair in theta / param / adam / best_theta arrays */
 
@@ -480,6 +482,60 @@ int trx_bspline_step(const trx_volumes *vol, const trx_loss_cfg *loss, const trx
                      const int *spacing /*[host]*/, void *workspace, size_t workspace_bytes, void *stream);
 int trx_bspline_run(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt, const trx_bspline_state *st,
                     const int *spacing /*[host]*/, int iters, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- Mutual information from a Parzen joint histogram (Mattes et al. 2003; extension: the reference's NMILoss, ref:utils.py:224-259, is a Gaussian
+ * KDE on a nearest-resampled lattice that its own README rules out in 3-D).  target / warped: [B][D][H][W] fp32 contiguous (D = 1 for ndim 2),
+ * N = D H W voxels per pair, K = cfg->bins in 8 .. 64, range [B][4] = (lo_t, hi_t, lo_w, hi_w) per pair.
+ *   target bin (box window):   a = clamp((int)floorf((t - lo_t) * s_t), 0, K - 1),  s_t = hi_t > lo_t ? K / (hi_t - lo_t) : 0 - one fp32 subtract, one
+ *                              fp32 multiply, never contracted;
+ *   warped (cubic B-spline):   x = (w - lo_w) * s_w,  s_w = hi_w > lo_w ? (K - 3) / (hi_w - lo_w) : 0 (fp32 as above),  u = 1 + clamp(x, 0, K - 3),
+ *                              c = min((int)floorf(u), K - 3),  r = u - c in [0, 1]; bins c - 1 .. c + 2 receive
+ *                              ((1 - r)^3, 3r^3 - 6r^2 + 4, -3r^3 + 3r^2 + 3r + 1, r^3) / 6 (they sum to 1; every index lies in [0, K - 1]);
+ *   P[a][k] = (1 / N) sum_v [a_v = a] beta_k(u_v),  p_T = sum_k P,  p_W = sum_a P,  H_T, H_W, H_TW their entropies (natural logarithm, 0 log 0 = 0);
+ *   loss[b] = alpha (H_TW - H_W)  [= alpha (H_T - MI): the gradient of -alpha MI]   or, cfg->normalized != 0,   alpha (2 - (H_T + H_W) / H_TW)
+ *             (loss and gradient 0 when H_TW = 0).  Both are >= 0 up to rounding, so the loops' `loss <= stop_crit` keeps its meaning;
+ *   grad_warped[v] = (s_w / N) [0 <= x_v <= K - 3] sum_{j = 0..3} G[a_v][c_v - 1 + j] beta'_j(r_v),  G = d loss / d P (0 where P = 0),
+ *             beta' = (-(1 - r)^2, 3r^2 - 4r, -3r^2 + 2r + 1, r^2) / 2.  The mask is inclusive (torch's clamp backward); at a voxel exactly on an
+ *             end of the range the function is only one-sidedly differentiable.  The target receives no gradient.
+ * Ranges are the caller's: the hot paths take the target's min / max and the moving image's min / max widened to contain 0 (the value of the
+ * zero-padded warp outside the field of view) once per optimisation.  Values outside the range fall into the end bins with a zero gradient.
+ * The histogram is accumulated in fixed point (2^31 units per voxel, the fp32 weights converted to units, the largest of the four as the remainder so
+ * that every voxel adds exactly one) with 64-bit integer adds, LDS and global: beyond the fp32 rounding of the weights,
+ * |P[a][k] - exact| <= 1.5 * 2^-31 n[a][k] / N for the n[a][k] voxels that touch the cell, at most 3 * 2^-31 summed over the table.  No float atomics; entropies in fp64 in a fixed order: the same bits on every call, and a pair's result does not depend on
+ * the batch around it.  One memset and three launches (histogram 8 B/voxel, the K x K table, gradient 12 B/voxel; grad_warped == NULL: two), no host
+ * sync, no allocation; status codes (TRX_ERR_ARG: null pointer, bins outside 8 .. 64, alpha not finite; TRX_ERR_NDIM; TRX_ERR_WORKSPACE) before any
+ * HIP call.  CPU restatement: tests/mi_ref.py. */
+typedef struct {
+    int bins;            /* K: 8 .. 64 */
+    float alpha;
+    int normalized;      /* 0: alpha (H_TW - H_W);  otherwise: alpha (2 - (H_T + H_W) / H_TW) */
+    const float *range;  /* device [B][4]: lo_t, hi_t, lo_w, hi_w */
+} trx_mi_cfg;
+size_t trx_mi_workspace_bytes(int ndim, int B, int D, int H, int W, int bins);   /* 0 = arguments rejected */
+int trx_mi_loss_grad(const float *target, const float *warped, int ndim, int B, int D, int H, int W, const trx_mi_cfg *cfg, float *loss /*[B]*/,
+                     float *grad_warped /*nullable, [B][D][H][W]*/, void *workspace, size_t workspace_bytes, void *stream);
+/* The histogram pass of trx_mi_loss_grad alone: uint64 counts[B][K][K] (target bin, warped bin; 2^31 units per voxel, so a pair's counts sum to
+ * N * 2^31 exactly and P = counts / (N * 2^31)) at the start of the workspace.  Exposed so that the pass can be timed in isolation
+ * (tools/bench_mi.py) and its table checked on its own.  Same arguments, checks and workspace. */
+int trx_mi_histogram(const float *target, const float *warped, int ndim, int B, int D, int H, int W, const trx_mi_cfg *cfg, void *workspace,
+                     size_t workspace_bytes, void *stream);
+
+/* Direct flow field + mutual information (+ smoothness regulariser st->smooth_weight) as one device-side loop: trx_flow_lncc_run with
+ * trx_mi_loss_grad in the middle - warp at the current flow -> histogram, loss, dL/dwarped -> loss curve / early stop / optimiser scalars -> dL/dflow
+ * through the trilinear derivative + smoothness gradient + SGD / Adam in place.  3-D only (TRX_ERR_NDIM otherwise).  State, early stop and flow_last as
+ * for trx_flow_run; vol->target: dense [B][D][H][W]; cfg->range is read on the device, once per iteration, and must outlive the run.
+ * Extension: arbiter = oracle/compose.py::flow_warp + tests/mi_ref.py under torch autograd. */
+size_t trx_flow_mi_workspace_bytes(const trx_volumes *vol, int bins);
+int trx_flow_mi_run(const trx_volumes *vol, const trx_mi_cfg *cfg, const trx_opt_cfg *opt, const trx_flow_state *st, int iters, void *workspace,
+                    size_t workspace_bytes, void *stream);
+
+/* Free-form deformation + mutual information: trx_bspline_run with another data term, 2-D and 3-D.  Per iteration: expand -> trx_flow_warp ->
+ * trx_mi_loss_grad -> trx_flow_warp_backward -> reduce -> the bending / decide / update launches of trx_bspline_run.  trx_bspline_state keeps its
+ * whole meaning (base, bending_weight, stop_crit, stopped, flow_last, losses = data term + lambda E).  vol->target: dense [B][D][H][W].
+ * Extension: arbiter = tests/bspline_ref.py::expand + oracle/compose.py::flow_warp + tests/mi_ref.py (+ tests/bspline_bending_ref.py) under torch autograd. */
+size_t trx_bspline_mi_workspace_bytes(int ndim, int B, int D, int H, int W, int sz, int sy, int sx, int bins);
+int trx_bspline_mi_run(const trx_volumes *vol, const trx_mi_cfg *cfg, const trx_opt_cfg *opt, const trx_bspline_state *st,
+                       const int *spacing /*[host]*/, int iters, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,6 @@ from ._engine import (AffineSolver, BSplineSolver, FlowSolver, LossSpec, SlabFlo
 from .pyramid import pyramid, pyramid_shapes, upsample_flow  # noqa: F401
 from .sharding import register_sharded  # noqa: F401
 from .torchregister import Register  # noqa: F401
-from .utils import (EPSILON, Attention_UNet, K_gauss, LocalNCCLoss, NCCLoss, NMI, NMILoss, PDF, PDF_xis, Regressor, SpatialTransformer, SSDLoss,  # noqa: F401
+from .utils import (EPSILON, Attention_UNet, K_gauss, LocalNCCLoss, MILoss, NCCLoss, NMI, NMILoss, PDF, PDF_xis, Regressor, SpatialTransformer, SSDLoss,  # noqa: F401
                     Theta, attention_grid, get_pdf, norm, padNd)
 from .warpings import affine_register, compose_theta, flow_register, get_affine_warp, rigid_register  # noqa: F401

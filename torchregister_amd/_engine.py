@@ -332,12 +332,17 @@ class FlowSolver:
     """Direct dense flow-field optimisation (the flow itself is the parameter), batched."""
 
     def __init__(self, moving, target, loss=None, optimizer="sgd", lr=1e-3, init=None, capacity=1000, smooth_weight=0.0,
-                 betas=(0.9, 0.999), eps=1e-8, stop_crit=None, keep_last=False, flags=0, lncc=None):
+                 betas=(0.9, 0.999), eps=1e-8, stop_crit=None, keep_last=False, flags=0, lncc=None, mi=None):
         """stop_crit: the reference's early stop (ref:warpings.py:231-233), tested on the device per pair - a pair whose recorded loss
         is <= stop_crit keeps that iteration's update and ignores every later iteration; `step[b]` = number of recorded losses.
         keep_last: also keep `flow_last`, the flow of the last forward (what the reference's flow_register.flow holds).
         lncc: dict(window=9, alpha=1.0, eps=1e-5) - the data term is the LOCAL-window NCC (extension) instead of `loss`: the whole loop
-        (warp, window sums, gradient, smoothness, SGD / Adam) runs in trx_flow_lncc_run, 3-D only."""
+        (warp, window sums, gradient, smoothness, SGD / Adam) runs in trx_flow_lncc_run, 3-D only.
+        mi: dict(bins=32, alpha=1.0, normalized=False, target_range=None, moving_range=None) - the data term is the Parzen joint-histogram
+        mutual information (extension, mi_loss_grad) instead of `loss`: the whole loop runs in trx_flow_mi_run, 3-D only.  A range of None
+        is fitted once, here, to (target, moving)."""
+        if mi is not None and (lncc is not None or loss is not None):
+            raise ValueError("mi is a data term of its own: give it without `loss` and without `lncc`")
         self.lib = _lib.load()
         self.batch = _Batch(moving, target, tables=False, flags=flags)
         if self.batch.C != 1:
@@ -357,12 +362,17 @@ class FlowSolver:
         self.losses = torch.full((b, self.capacity), float("nan"), device=dev)
         self.step = torch.zeros(b, dtype=torch.int32, device=dev)
         self.vol = self.batch.vol()
-        self.lncc = None
+        self.lncc = self.mi = None
         if lncc is not None:
             if nd != 3:
                 raise ValueError("the fused local-NCC loop is 3-D only (2-D: LocalNCCLoss through the generic autograd path)")
             self.lncc = (int(lncc.get("window", 9)), float(lncc.get("alpha", 1.0)), float(lncc.get("eps", 1e-5)))
             self.ws_bytes = self.lib.trx_flow_lncc_workspace_bytes(ctypes.byref(self.vol))
+        elif mi is not None:
+            if nd != 3:
+                raise ValueError("the fused mutual-information flow loop is 3-D only (2-D: MILoss through the generic autograd path, or BSplineSolver)")
+            self.mi, self.mi_range = _mi_cfg(mi, self.batch.target, self.batch.moving)
+            self.ws_bytes = self.lib.trx_flow_mi_workspace_bytes(ctypes.byref(self.vol), self.mi.bins)
         else:
             self.ws_bytes = self.lib.trx_flow_workspace_bytes(ctypes.byref(self.vol))
         if self.ws_bytes == 0:
@@ -395,6 +405,11 @@ class FlowSolver:
                                                 ctypes.byref(self.state), int(iters), _lib.ptr(self.workspace), self.ws_bytes,
                                                 _lib.current_stream(self.batch.device))
                 _lib.check(rc, "trx_flow_lncc_run")
+                return
+            if self.mi is not None:
+                rc = self.lib.trx_flow_mi_run(ctypes.byref(self.vol), ctypes.byref(self.mi), ctypes.byref(self.opt), ctypes.byref(self.state), int(iters),
+                                              _lib.ptr(self.workspace), self.ws_bytes, _lib.current_stream(self.batch.device))
+                _lib.check(rc, "trx_flow_mi_run")
                 return
             rc = self.lib.trx_flow_run(ctypes.byref(self.vol), ctypes.byref(self.loss_c), ctypes.byref(self.opt),
                                        ctypes.byref(self.state), int(iters), _lib.ptr(self.workspace), self.ws_bytes,
@@ -519,10 +534,14 @@ class BSplineSolver:
     """Cubic B-spline free-form deformation (extension): the control lattice `ctrl` [B, nd, *grid] is the parameter, the displacement field
     is base + expand(ctrl); the whole loop (expand, fused loss and dL/dflow, reduce, SGD / Adam, early stop) runs in trx_bspline_run.
     bending_weight = lambda > 0 adds lambda * (bending energy of ctrl, bspline_bending) to each pair's loss: `losses` and the early stop see
-    the total; `base` is not penalised.  After run(): `flow` = expand of the current ctrl (+ base), `flow_last` (keep_last or stop_crit) = the flow of the last forward."""
+    the total; `base` is not penalised.  After run(): `flow` = expand of the current ctrl (+ base), `flow_last` (keep_last or stop_crit) = the flow of the last forward.
+    mi = dict(bins=32, alpha=1.0, normalized=False, target_range=None, moving_range=None): the data term is the Parzen joint-histogram mutual
+    information (mi_loss_grad) instead of `loss`, and the loop runs in trx_bspline_mi_run; a range of None is fitted once, here, to (target, moving)."""
 
     def __init__(self, moving, target, spacing, loss=None, optimizer="sgd", lr=1e-3, init=None, base=None, capacity=1000, stop_crit=None,
-                 keep_last=False, betas=(0.9, 0.999), eps=1e-8, bending_weight=0.0):
+                 keep_last=False, betas=(0.9, 0.999), eps=1e-8, bending_weight=0.0, mi=None):
+        if mi is not None and loss is not None:
+            raise ValueError("mi is a data term of its own: give it without `loss`")
         self.lib = _lib.load()
         self.bending_weight = _bending_weight(bending_weight)
         self.batch = _Batch(moving, target, tables=False)
@@ -560,7 +579,15 @@ class BSplineSolver:
         self.stopped = torch.zeros(b, dtype=torch.int32, device=dev) if stop_crit is not None else None
         self.flow_last = torch.empty(fshape, device=dev) if (keep_last or stop_crit is not None) else None
         self.vol = self.batch.vol()
-        self.workspace, self.ws_bytes = _bspline_workspace(self.lib, nd, b, self.batch.spatial, tuple(self.sp3), dev)
+        self.mi = None
+        if mi is not None:
+            self.mi, self.mi_range = _mi_cfg(mi, self.batch.target, self.batch.moving)
+            self.ws_bytes = self.lib.trx_bspline_mi_workspace_bytes(nd, b, *_dhw(self.batch.spatial), *self.sp3, self.mi.bins)
+            if self.ws_bytes == 0:
+                raise _lib.TrxError(f"trx_bspline_mi_workspace_bytes rejected {b} x {tuple(self.batch.spatial)} with spacing {self.spacing}")
+            self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+        else:
+            self.workspace, self.ws_bytes = _bspline_workspace(self.lib, nd, b, self.batch.spatial, tuple(self.sp3), dev)
         st = _lib.BSplineState()
         st.ctrl = self.ctrl.data_ptr()
         st.adam_m = self.adam_m.data_ptr() if adam else None
@@ -591,9 +618,13 @@ class BSplineSolver:
                                 f"{self.capacity} (create the solver with a larger `capacity`)")
         self.enqueued += iters
         with torch.cuda.device(self.batch.device):
-            rc = self.lib.trx_bspline_run(ctypes.byref(self.vol), ctypes.byref(self.loss_c), ctypes.byref(self.opt), ctypes.byref(self.state),
-                                          self.sp3, iters, _lib.ptr(self.workspace), self.ws_bytes, _lib.current_stream(self.batch.device))
-        _lib.check(rc, "trx_bspline_run")
+            if self.mi is not None:
+                rc = self.lib.trx_bspline_mi_run(ctypes.byref(self.vol), ctypes.byref(self.mi), ctypes.byref(self.opt), ctypes.byref(self.state),
+                                                 self.sp3, iters, _lib.ptr(self.workspace), self.ws_bytes, _lib.current_stream(self.batch.device))
+            else:
+                rc = self.lib.trx_bspline_run(ctypes.byref(self.vol), ctypes.byref(self.loss_c), ctypes.byref(self.opt), ctypes.byref(self.state),
+                                              self.sp3, iters, _lib.ptr(self.workspace), self.ws_bytes, _lib.current_stream(self.batch.device))
+        _lib.check(rc, "trx_bspline_mi_run" if self.mi is not None else "trx_bspline_run")
         self._expand()
 
 
@@ -1210,6 +1241,71 @@ def run_slabs_lockstep(solvers, iters):
                 s.peer_finish()
     for s in solvers:
         s.peers.check()
+
+
+def _mi_bins(bins):
+    if isinstance(bins, bool) or not isinstance(bins, int) or not 8 <= bins <= 64:
+        raise ValueError(f"bins must be an int in 8 .. 64, got {bins!r}")
+    return bins
+
+
+def mi_range(target, moving, target_range=None, moving_range=None):
+    """[B,4] fp32 on the tensors' device: (lo_t, hi_t, lo_w, hi_w) per pair.  None: the target's min / max, the moving (or warped) image's min /
+    max widened to contain 0 - the value of a zero-padded warp outside the field of view.  A (lo, hi) pair of numbers serves every pair of the
+    batch.  No host sync."""
+    B = target.shape[0]
+    cols = []
+    for x, r, widen in ((target, target_range, False), (moving, moving_range, True)):
+        if r is None:
+            flat = x.detach().float().reshape(B, -1)
+            lo, hi = flat.amin(1), flat.amax(1)
+            if widen:
+                lo, hi = lo.clamp(max=0.0), hi.clamp(min=0.0)
+        else:
+            lo, hi = (torch.full((B,), float(v), dtype=torch.float32, device=target.device) for v in r)
+        cols += [lo, hi]
+    return torch.stack(cols, dim=1).contiguous()
+
+
+def _mi_cfg(mi, target, moving):
+    """dict -> (trx_mi_cfg, the range tensor it points to: the caller keeps it alive)."""
+    unknown = set(mi) - {"bins", "alpha", "normalized", "target_range", "moving_range"}
+    if unknown:
+        raise ValueError(f"unknown mutual-information settings {sorted(unknown)}")
+    rng = mi_range(target, moving, mi.get("target_range"), mi.get("moving_range"))
+    cfg = _lib.MICfg()
+    cfg.bins, cfg.alpha, cfg.normalized, cfg.range = _mi_bins(mi.get("bins", 32)), float(mi.get("alpha", 1.0)), int(bool(mi.get("normalized", False))), rng.data_ptr()
+    return cfg, rng
+
+
+def mi_loss_grad(target, warped, rng, bins=32, alpha=1.0, normalized=False, need_grad=True):
+    """Parzen joint-histogram mutual information (extension, include/trx.h: trx_mi_loss_grad): target / warped [B,1,*spatial] fp32 on the GPU,
+    rng [B,4] (mi_range).  Returns (loss [B], d loss / d warped (same shape as warped) or None)."""
+    lib = _lib.load()
+    if not (target.is_cuda and warped.is_cuda):
+        raise _lib.TrxError("mi_loss_grad needs CUDA (HIP) tensors: there is no CPU fallback")
+    if target.shape != warped.shape or target.dim() not in (4, 5) or target.shape[1] != 1:
+        raise ValueError(f"expected two [B,1,*spatial] tensors of equal shape, got {tuple(target.shape)} and {tuple(warped.shape)}")
+    nd = target.dim() - 2
+    y, w = target.detach().contiguous().float(), warped.detach().contiguous().float()
+    B = y.shape[0]
+    if tuple(rng.shape) != (B, 4):
+        raise ValueError(f"expected a range tensor [{B}, 4], got {tuple(rng.shape)}")
+    rng = rng.detach().to(device=y.device, dtype=torch.float32).contiguous()
+    D, H, W = (1, *y.shape[2:]) if nd == 2 else y.shape[2:]
+    cfg = _lib.MICfg()
+    cfg.bins, cfg.alpha, cfg.normalized, cfg.range = _mi_bins(bins), float(alpha), int(bool(normalized)), rng.data_ptr()
+    loss = torch.empty(B, device=y.device)
+    grad = torch.empty_like(w) if need_grad else None
+    ws_bytes = lib.trx_mi_workspace_bytes(nd, B, D, H, W, cfg.bins)
+    if ws_bytes == 0:
+        raise _lib.TrxError(f"trx_mi_workspace_bytes rejected {B} x {tuple(y.shape[2:])} with {bins} bins")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=y.device)
+    with torch.cuda.device(y.device):
+        rc = lib.trx_mi_loss_grad(_lib.ptr(y), _lib.ptr(w), nd, B, D, H, W, ctypes.byref(cfg), _lib.ptr(loss), _lib.ptr(grad), _lib.ptr(ws), ws_bytes,
+                                  _lib.current_stream(y.device))
+    _lib.check(rc, "trx_mi_loss_grad")
+    return loss, grad
 
 
 def local_ncc_loss_grad(target, warped, window=9, alpha=1.0, eps=1e-5, need_grad=True):

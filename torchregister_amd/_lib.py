@@ -71,6 +71,10 @@ class BSplineState(ctypes.Structure):
                 ("bending_weight", ctypes.c_float)]
 
 
+class MICfg(ctypes.Structure):
+    _fields_ = [("bins", ctypes.c_int), ("alpha", ctypes.c_float), ("normalized", ctypes.c_int), ("range", ctypes.c_void_p)]
+
+
 # name -> (restype, argtypes); must list every symbol include/trx.h declares (tests check this)
 _P = ctypes.c_void_p
 SIGNATURES = {
@@ -144,6 +148,15 @@ SIGNATURES = {
                                         _P, ctypes.c_size_t, _P]),
     "trx_bspline_run": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(LossCfg), ctypes.POINTER(OptCfg), ctypes.POINTER(BSplineState), c_int_p,
                                        ctypes.c_int, _P, ctypes.c_size_t, _P]),
+    "trx_mi_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
+    "trx_mi_loss_grad": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 5 + [ctypes.POINTER(MICfg), _P, _P, _P, ctypes.c_size_t, _P]),
+    "trx_mi_histogram": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 5 + [ctypes.POINTER(MICfg), _P, ctypes.c_size_t, _P]),
+    "trx_flow_mi_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Volumes), ctypes.c_int]),
+    "trx_flow_mi_run": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MICfg), ctypes.POINTER(OptCfg), ctypes.POINTER(FlowState), ctypes.c_int, _P,
+                                       ctypes.c_size_t, _P]),
+    "trx_bspline_mi_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 9),
+    "trx_bspline_mi_run": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MICfg), ctypes.POINTER(OptCfg), ctypes.POINTER(BSplineState), c_int_p,
+                                          ctypes.c_int, _P, ctypes.c_size_t, _P]),
 }
 
 _lib = None

@@ -229,9 +229,9 @@ constexpr int kBsNormal = 0, kBsHit = 1, kBsSkip = 2;
 
 // One pair: the loss curve, the step counter, the early stop (trx_flow_state's semantics: the iteration that meets stop_crit still applies
 // its update, later ones are no-ops) and the Adam scalars of this iteration.  `penalty` = lambda E_b joins the data term before the
-// early stop and the record (BEND only).
+// early stop and the record (BEND only).  The data term of pair b is terms[b * tstride] (trx_flow_loss_grad: 4, trx_mi_loss_grad: 1).
 template <bool BEND>
-__device__ __forceinline__ void bspline_decide_pair(int b, float penalty, const float *__restrict__ terms, const trx_opt_cfg &oc, float *__restrict__ losses,
+__device__ __forceinline__ void bspline_decide_pair(int b, float penalty, const float *__restrict__ terms, int tstride, const trx_opt_cfg &oc, float *__restrict__ losses,
                                                     int losses_capacity, int *__restrict__ step, float stop_crit, int *__restrict__ stopped,
                                                     BsCoef *__restrict__ coef)
 {
@@ -242,7 +242,7 @@ __device__ __forceinline__ void bspline_decide_pair(int b, float penalty, const 
         return;
     }
     const int t = step[b];
-    float total = terms[b * 4];
+    float total = terms[b * tstride];
     if constexpr (BEND) total += penalty;
     if (oc.kind == TRX_OPT_ADAM) {
         const double bc1 = 1.0 - ipow((double)oc.beta1, t + 1), bc2 = 1.0 - ipow((double)oc.beta2, t + 1);
@@ -263,12 +263,12 @@ __device__ __forceinline__ void bspline_decide_pair(int b, float penalty, const 
 }
 
 // One thread per pair (bending_weight = 0)
-__global__ void bspline_decide_kernel(const float *__restrict__ terms, int B, trx_opt_cfg oc, float *__restrict__ losses, int losses_capacity,
+__global__ void bspline_decide_kernel(const float *__restrict__ terms, int tstride, int B, trx_opt_cfg oc, float *__restrict__ losses, int losses_capacity,
                                       int *__restrict__ step, float stop_crit, int *__restrict__ stopped, BsCoef *__restrict__ coef)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    bspline_decide_pair<false>(b, 0.f, terms, oc, losses, losses_capacity, step, stop_crit, stopped, coef);
+    bspline_decide_pair<false>(b, 0.f, terms, tstride, oc, losses, losses_capacity, step, stop_crit, stopped, coef);
 }
 
 // SGD / Adam on the control points of pair blockIdx.y (the arithmetic of flow_update_kernel, csrc/flow.hip), and - when the caller keeps
@@ -511,14 +511,14 @@ __global__ __launch_bounds__(64) void bspline_energy_kernel(const float *__restr
 
 // bspline_decide_kernel with the penalty: one block of 64 threads per pair sums the pair's partials, thread 0 decides on
 // terms[b][0] + lambda E_b
-__global__ __launch_bounds__(64) void bspline_decide_bending_kernel(const float *__restrict__ terms, const float *__restrict__ partials, int per_pair,
+__global__ __launch_bounds__(64) void bspline_decide_bending_kernel(const float *__restrict__ terms, int tstride, const float *__restrict__ partials, int per_pair,
                                                                       float lambda, trx_opt_cfg oc, float *__restrict__ losses, int losses_capacity,
                                                                       int *__restrict__ step, float stop_crit, int *__restrict__ stopped,
                                                                       BsCoef *__restrict__ coef)
 {
     const int b = blockIdx.x;
     const double e = bspline_sum_partials(partials + (size_t)b * per_pair, per_pair);
-    if (threadIdx.x == 0) bspline_decide_pair<true>(b, lambda * (float)e, terms, oc, losses, losses_capacity, step, stop_crit, stopped, coef);
+    if (threadIdx.x == 0) bspline_decide_pair<true>(b, lambda * (float)e, terms, tstride, oc, losses, losses_capacity, step, stop_crit, stopped, coef);
 }
 
 struct BsGeom {
@@ -724,26 +724,31 @@ extern "C" int trx_bspline_bending(const float *ctrl, float *energy, float *dctr
     return TRX_OK;
 }
 
-extern "C" int trx_bspline_run(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt, const trx_bspline_state *st, const int *spacing,
-                               int iters, void *workspace, size_t workspace_bytes, void *stream)
+// The checks trx_bspline_run and trx_bspline_mi_run share (everything but the data term's own arguments and the workspace size)
+static int bspline_run_checks(const trx_volumes *vol, const trx_opt_cfg *opt, const trx_bspline_state *st, const int *spacing, int iters, void *workspace,
+                              BsGeom *g)
 {
-    if (!vol || !vol->moving || !vol->target || !loss || !opt || !st || !spacing || !workspace) return TRX_ERR_ARG;
+    if (!vol || !vol->moving || !vol->target || !opt || !st || !spacing || !workspace) return TRX_ERR_ARG;
     if (!st->ctrl || !st->flow || !st->dflow || !st->step) return TRX_ERR_ARG;
-    BsGeom g;
-    int rc = bspline_geom(vol->ndim, vol->B, vol->D, vol->H, vol->W, spacing[0], spacing[1], spacing[2], &g);
+    const int rc = bspline_geom(vol->ndim, vol->B, vol->D, vol->H, vol->W, spacing[0], spacing[1], spacing[2], g);
     if (rc != TRX_OK) return rc;
     if (opt->kind != TRX_OPT_SGD && opt->kind != TRX_OPT_ADAM) return TRX_ERR_ARG;
     if (opt->kind == TRX_OPT_ADAM && (!st->adam_m || !st->adam_v)) return TRX_ERR_ARG;
     if (iters < 0 || (st->losses && st->losses_capacity < 0)) return TRX_ERR_ARG;
-    const float lambda = st->bending_weight;
-    if (!(lambda >= 0.f) || !std::isfinite(lambda)) return TRX_ERR_ARG;
-    if (workspace_bytes < g.ws_bytes) return TRX_ERR_WORKSPACE;
-    if (st->losses && iters > st->losses_capacity) return TRX_ERR_CAPACITY;
-    hipStream_t s = (hipStream_t)stream;
+    if (!(st->bending_weight >= 0.f) || !std::isfinite(st->bending_weight)) return TRX_ERR_ARG;
+    return TRX_OK;
+}
+
+// The loop both data terms share.  data_term(): the launches that turn st->flow into the pairs' data terms (terms[b * tstride]) and st->dflow.
+template <typename DataTerm>
+static int bspline_loop(const BsGeom &g, const trx_volumes *vol, const trx_opt_cfg *opt, const trx_bspline_state *st, int iters, const float *terms,
+                        int tstride, void *workspace, hipStream_t s, DataTerm data_term)
+{
+    int rc;
     char *ws = (char *)workspace;
-    float *terms = (float *)(ws + g.terms_offset);
     BsCoef *coef = (BsCoef *)(ws + g.coef_offset);
     float *dctrl = (float *)(ws + g.dctrl_offset);
+    const float lambda = st->bending_weight;
     const size_t nctrl = (size_t)g.ndim * g.G[0] * g.G[1] * g.G[2], nflow = (size_t)g.ndim * vol->D * vol->H * vol->W;
     const size_t work = std::max(nctrl, st->flow_last ? nflow : (size_t)0);
     const dim3 ugrid((unsigned)std::max<size_t>(1, std::min<size_t>((work + TRX_BLOCK - 1) / TRX_BLOCK, std::max(1, 2048 / vol->B))), (unsigned)vol->B);
@@ -751,14 +756,14 @@ extern "C" int trx_bspline_run(const trx_volumes *vol, const trx_loss_cfg *loss,
     if (bend && iters > 0 && (rc = bspline_gram_impl(g, workspace, s)) != TRX_OK) return rc;   // once per call: the bands depend on the geometry alone
     for (int i = 0; i < iters; i++) {
         if ((rc = bspline_expand_impl(g, st->ctrl, st->base, st->flow, workspace, s)) != TRX_OK) return rc;
-        if ((rc = trx_flow_loss_grad(vol, loss, st->flow, terms, st->dflow, ws + g.flow_offset, g.flow_bytes, stream)) != TRX_OK) return rc;
+        if ((rc = data_term()) != TRX_OK) return rc;
         if ((rc = bspline_reduce_impl(g, st->dflow, dctrl, workspace, s)) != TRX_OK) return rc;
         if (bend) {
             if ((rc = bspline_bending_impl(g, st->ctrl, dctrl, lambda, 1, workspace, s)) != TRX_OK) return rc;
-            hipLaunchKernelGGL(bspline_decide_bending_kernel, dim3((unsigned)vol->B), dim3(64), 0, s, (const float *)terms, (const float *)(ws + g.part_offset),
+            hipLaunchKernelGGL(bspline_decide_bending_kernel, dim3((unsigned)vol->B), dim3(64), 0, s, terms, tstride, (const float *)(ws + g.part_offset),
                                (int)(g.ndim * g.bend_ntile), lambda, *opt, st->losses, st->losses_capacity, st->step, st->stop_crit, st->stopped, coef);
         } else {
-            hipLaunchKernelGGL(bspline_decide_kernel, dim3((vol->B + 63) / 64), dim3(64), 0, s, (const float *)terms, vol->B, *opt, st->losses,
+            hipLaunchKernelGGL(bspline_decide_kernel, dim3((vol->B + 63) / 64), dim3(64), 0, s, terms, tstride, vol->B, *opt, st->losses,
                                st->losses_capacity, st->step, st->stop_crit, st->stopped, coef);
         }
         TRX_CHECK_LAUNCH();
@@ -767,6 +772,73 @@ extern "C" int trx_bspline_run(const trx_volumes *vol, const trx_loss_cfg *loss,
         TRX_CHECK_LAUNCH();
     }
     return TRX_OK;
+}
+
+extern "C" int trx_bspline_run(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt, const trx_bspline_state *st, const int *spacing,
+                               int iters, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!loss) return TRX_ERR_ARG;
+    BsGeom g;
+    const int rc = bspline_run_checks(vol, opt, st, spacing, iters, workspace, &g);
+    if (rc != TRX_OK) return rc;
+    if (workspace_bytes < g.ws_bytes) return TRX_ERR_WORKSPACE;
+    if (st->losses && iters > st->losses_capacity) return TRX_ERR_CAPACITY;
+    char *ws = (char *)workspace;
+    float *terms = (float *)(ws + g.terms_offset);
+    return bspline_loop(g, vol, opt, st, iters, terms, 4, workspace, (hipStream_t)stream, [&]() {
+        return trx_flow_loss_grad(vol, loss, st->flow, terms, st->dflow, ws + g.flow_offset, g.flow_bytes, stream);
+    });
+}
+
+// Free-form deformation + mutual information (csrc/mi.hip): behind the loop's workspace lie the warped volumes, dL/dwarped and trx_mi_loss_grad's
+// workspace; the pairs' losses take the place of terms[B][4] (stride 1).
+struct BsMiLayout {
+    size_t o_warped, o_go, o_mi, mi_bytes, ws_bytes;
+};
+
+static int bspline_mi_layout(const BsGeom &g, int bins, BsMiLayout *l)
+{
+    l->mi_bytes = trx_mi_workspace_bytes(g.ndim, g.B, g.S[0], g.S[1], g.S[2], bins);
+    if (l->mi_bytes == 0) return TRX_ERR_ARG;
+    const size_t vols = (((size_t)g.B * g.S[0] * g.S[1] * g.S[2] * sizeof(float)) + 255) & ~(size_t)255;
+    l->o_warped = (g.ws_bytes + 255) & ~(size_t)255;
+    l->o_go = l->o_warped + vols;
+    l->o_mi = l->o_go + vols;
+    l->ws_bytes = l->o_mi + l->mi_bytes;
+    return TRX_OK;
+}
+
+extern "C" size_t trx_bspline_mi_workspace_bytes(int ndim, int B, int D, int H, int W, int sz, int sy, int sx, int bins)
+{
+    BsGeom g;
+    BsMiLayout l;
+    if (bspline_geom(ndim, B, D, H, W, sz, sy, sx, &g) != TRX_OK || bspline_mi_layout(g, bins, &l) != TRX_OK) return 0;
+    return l.ws_bytes;
+}
+
+extern "C" int trx_bspline_mi_run(const trx_volumes *vol, const trx_mi_cfg *cfg, const trx_opt_cfg *opt, const trx_bspline_state *st, const int *spacing,
+                                  int iters, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!cfg || !cfg->range) return TRX_ERR_ARG;
+    BsGeom g;
+    int rc = bspline_run_checks(vol, opt, st, spacing, iters, workspace, &g);
+    if (rc != TRX_OK) return rc;
+    BsMiLayout l;
+    if ((rc = bspline_mi_layout(g, cfg->bins, &l)) != TRX_OK) return rc;
+    if (!std::isfinite(cfg->alpha)) return TRX_ERR_ARG;
+    const size_t nvox = (size_t)vol->D * vol->H * vol->W;
+    if (vol->B > 1 && vol->target_stride != nvox) return TRX_ERR_ARG;   // the histogram kernels take a dense [B][D][H][W] target
+    if (workspace_bytes < l.ws_bytes) return TRX_ERR_WORKSPACE;
+    if (st->losses && iters > st->losses_capacity) return TRX_ERR_CAPACITY;
+    char *ws = (char *)workspace;
+    float *mloss = (float *)(ws + g.terms_offset), *warped = (float *)(ws + l.o_warped), *go = (float *)(ws + l.o_go);
+    return bspline_loop(g, vol, opt, st, iters, mloss, 1, workspace, (hipStream_t)stream, [&]() {
+        int r = trx_flow_warp(vol, st->flow, 1, warped, stream);
+        if (r != TRX_OK) return r;
+        r = trx_mi_loss_grad(vol->target, warped, vol->ndim, vol->B, vol->D, vol->H, vol->W, cfg, mloss, go, ws + l.o_mi, l.mi_bytes, stream);
+        if (r != TRX_OK) return r;
+        return trx_flow_warp_backward(vol, st->flow, 1, go, st->dflow, stream);
+    });
 }
 
 extern "C" int trx_bspline_step(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt, const trx_bspline_state *st, const int *spacing,

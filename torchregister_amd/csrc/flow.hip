@@ -11,6 +11,8 @@
 // ref:warpings.py:208-220 when the parameter is the flow itself.
 #include "trx_common.h"
 
+#include <cmath>
+
 namespace trx {
 
 struct FlowCoef {   // per pair, written by flow_coef_kernel, read by pass B (wave-uniform)
@@ -1038,42 +1040,35 @@ extern "C" int trx_flow_run(const trx_volumes *vol, const trx_loss_cfg *loss, co
 //   flow_update3_kernel<2> dL/dflow = dL/dwarped * (trilinear derivative) + smoothness gradient; SGD / Adam in place
 // No autograd, no host sync, no torch optimiser.
 // ---------------------------------------------------------------------------------------------------
-static size_t lncc_loop_offsets(const trx_volumes *vol, size_t *o_warped, size_t *o_go, size_t *o_loss, size_t *o_lncc)
+// Workspace of a loop whose criterion runs between the warp and the update: behind trx_flow_workspace_bytes lie the warped volumes, dL/dwarped,
+// the pairs' losses and `crit_bytes` for the criterion itself.
+struct CritLoopOffsets {
+    size_t warped, go, loss, crit, total;
+};
+
+static CritLoopOffsets crit_loop_offsets(const trx_volumes *vol, size_t crit_bytes)
 {
     const size_t nvox = (size_t)vol->D * vol->H * vol->W;
+    CritLoopOffsets o;
     size_t off = (trx_flow_workspace_bytes(vol) + 255) & ~(size_t)255;
-    *o_warped = off; off += ((size_t)vol->B * nvox * sizeof(float) + 255) & ~(size_t)255;
-    *o_go = off;     off += ((size_t)vol->B * nvox * sizeof(float) + 255) & ~(size_t)255;
-    *o_loss = off;   off += ((size_t)vol->B * sizeof(float) + 255) & ~(size_t)255;
-    *o_lncc = off;   off += trx_lncc_workspace_bytes(vol->ndim, vol->B, vol->D, vol->H, vol->W);
-    return off;
+    o.warped = off; off += ((size_t)vol->B * nvox * sizeof(float) + 255) & ~(size_t)255;
+    o.go = off;     off += ((size_t)vol->B * nvox * sizeof(float) + 255) & ~(size_t)255;
+    o.loss = off;   off += ((size_t)vol->B * sizeof(float) + 255) & ~(size_t)255;
+    o.crit = off;   off += crit_bytes;
+    o.total = off;
+    return o;
 }
 
-extern "C" size_t trx_flow_lncc_workspace_bytes(const trx_volumes *vol)
-{
-    if (check_vol_flow(vol, false) != TRX_OK || vol->ndim != 3) return 0;
-    size_t a, b, c, d;
-    return lncc_loop_offsets(vol, &a, &b, &c, &d);
-}
-
-extern "C" int trx_flow_lncc_run(const trx_volumes *vol, int window, float lncc_alpha, float lncc_eps, const trx_opt_cfg *opt, const trx_flow_state *st,
-                                 int iters, void *workspace, size_t workspace_bytes, void *stream)
+// The iterations both criteria share (arguments already checked).  criterion(warped, loss [B], dL/dwarped, its workspace): the launches that turn
+// the warped volumes into the pairs' data terms and their gradient.
+template <typename Criterion>
+static int flow_criterion_loop(const trx_volumes *vol, const trx_opt_cfg *opt, const trx_flow_state *st, int iters, void *workspace, const CritLoopOffsets &o,
+                               hipStream_t s, Criterion criterion)
 {
     const trx_loss_cfg none = {0.f, 0.f, 0.f, 0.f, 0.f};
-    int rc = check_flow_args(vol, &none, opt, st, workspace, workspace_bytes);
-    if (rc) return rc;
-    if (vol->ndim != 3) return TRX_ERR_NDIM;
     const size_t nvox = (size_t)vol->D * vol->H * vol->W;
-    if (iters < 0 || (window != 3 && window != 5 && window != 7 && window != 9)) return TRX_ERR_ARG;
-    if (vol->B > 1 && vol->target_stride != nvox) return TRX_ERR_ARG;   // the window kernels take a dense [B][D][H][W] target
-    if (workspace_bytes < trx_flow_lncc_workspace_bytes(vol)) return TRX_ERR_WORKSPACE;
-    if (st->losses && iters > st->losses_capacity) return TRX_ERR_CAPACITY;
-    hipStream_t s = (hipStream_t)stream;
-    size_t o_warped, o_go, o_loss, o_lncc;
-    lncc_loop_offsets(vol, &o_warped, &o_go, &o_loss, &o_lncc);
     char *ws = (char *)workspace;
-    float *partials = (float *)workspace, *warped = (float *)(ws + o_warped), *go = (float *)(ws + o_go), *lloss = (float *)(ws + o_loss);
-    const size_t lncc_bytes = trx_lncc_workspace_bytes(3, vol->B, vol->D, vol->H, vol->W);
+    float *partials = (float *)workspace, *warped = (float *)(ws + o.warped), *go = (float *)(ws + o.go), *closs = (float *)(ws + o.loss);
     FlowCoef *coef = coef_ptr(vol, workspace);
     const bool smooth = st->smooth_weight != 0.f, adam = opt->kind == TRX_OPT_ADAM;
     float *cur = st->flow, *nxt = smooth ? st->flow_tmp : st->flow;
@@ -1084,11 +1079,11 @@ extern "C" int trx_flow_lncc_run(const trx_volumes *vol, int window, float lncc_
         if (smooth) hipLaunchKernelGGL((flow_moments3_kernel<true>), grid, block, 0, s, *vol, cur, partials, slab, cg, warped);
         else hipLaunchKernelGGL((flow_moments3_kernel<false>), grid, block, 0, s, *vol, cur, partials, slab, cg, warped);
         TRX_CHECK_LAUNCH();
-        rc = trx_lncc_loss_grad(vol->target, warped, 3, vol->B, vol->D, vol->H, vol->W, window, lncc_alpha, lncc_eps, lloss, go, ws + o_lncc, lncc_bytes, stream);
+        const int rc = criterion((const float *)warped, closs, go, (void *)(ws + o.crit));
         if (rc) return rc;
         hipLaunchKernelGGL(flow_coef_kernel, dim3(vol->B), dim3(1024), 0, s, partials, cg.nblk, 3, vol->D, vol->H, vol->W, none, *opt, st->smooth_weight,
                            st->losses, st->losses_capacity, st->step, (float *)nullptr, coef, (double *)nullptr, (const double *)nullptr, vol->D, 0,
-                           stash_ptr(vol, workspace), st->stop_crit, st->stopped, (int)(cur != nxt), lloss);
+                           stash_ptr(vol, workspace), st->stop_crit, st->stopped, (int)(cur != nxt), closs);
         TRX_CHECK_LAUNCH();
         const int save_last = (i + 1 == iters) ? 1 : 0;
 #define TRX_LAUNCH_L(SM, AD) hipLaunchKernelGGL((flow_update3_kernel<2, SM, false, AD>), grid, block, 0, s, *vol, cur, nxt, st->adam_m, st->adam_v, coef, *opt, slab, cg, \
@@ -1103,6 +1098,67 @@ extern "C" int trx_flow_lncc_run(const trx_volumes *vol, int window, float lncc_
         if (hipMemcpyAsync(st->flow, cur, (size_t)vol->B * 3 * nvox * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return TRX_ERR_HIP;
     }
     return TRX_OK;
+}
+
+// the checks the two loops share; `none`: no fused term
+static int check_criterion_loop(const trx_volumes *vol, const trx_opt_cfg *opt, const trx_flow_state *st, int iters, void *workspace, size_t workspace_bytes)
+{
+    const trx_loss_cfg none = {0.f, 0.f, 0.f, 0.f, 0.f};
+    const int rc = check_flow_args(vol, &none, opt, st, workspace, workspace_bytes);
+    if (rc) return rc;
+    if (vol->ndim != 3) return TRX_ERR_NDIM;
+    if (iters < 0) return TRX_ERR_ARG;
+    if (vol->B > 1 && vol->target_stride != (size_t)vol->D * vol->H * vol->W) return TRX_ERR_ARG;   // the criteria take a dense [B][D][H][W] target
+    return TRX_OK;
+}
+
+extern "C" size_t trx_flow_lncc_workspace_bytes(const trx_volumes *vol)
+{
+    if (check_vol_flow(vol, false) != TRX_OK || vol->ndim != 3) return 0;
+    return crit_loop_offsets(vol, trx_lncc_workspace_bytes(vol->ndim, vol->B, vol->D, vol->H, vol->W)).total;
+}
+
+extern "C" int trx_flow_lncc_run(const trx_volumes *vol, int window, float lncc_alpha, float lncc_eps, const trx_opt_cfg *opt, const trx_flow_state *st,
+                                 int iters, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const int rc = check_criterion_loop(vol, opt, st, iters, workspace, workspace_bytes);
+    if (rc) return rc;
+    if (window != 3 && window != 5 && window != 7 && window != 9) return TRX_ERR_ARG;
+    if (workspace_bytes < trx_flow_lncc_workspace_bytes(vol)) return TRX_ERR_WORKSPACE;
+    if (st->losses && iters > st->losses_capacity) return TRX_ERR_CAPACITY;
+    const size_t lncc_bytes = trx_lncc_workspace_bytes(3, vol->B, vol->D, vol->H, vol->W);
+    return flow_criterion_loop(vol, opt, st, iters, workspace, crit_loop_offsets(vol, lncc_bytes), (hipStream_t)stream,
+                               [&](const float *warped, float *loss, float *go, void *cws) {
+                                   return trx_lncc_loss_grad(vol->target, warped, 3, vol->B, vol->D, vol->H, vol->W, window, lncc_alpha, lncc_eps, loss, go, cws,
+                                                             lncc_bytes, stream);
+                               });
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Direct flow + mutual information (+ smoothness): the loop above with trx_mi_loss_grad (csrc/mi.hip) as the criterion.  Arbiter:
+// oracle/compose.py::flow_warp + tests/mi_ref.py + smooth_regulariser under torch autograd.
+// ---------------------------------------------------------------------------------------------------
+extern "C" size_t trx_flow_mi_workspace_bytes(const trx_volumes *vol, int bins)
+{
+    if (check_vol_flow(vol, false) != TRX_OK || vol->ndim != 3) return 0;
+    const size_t mi_bytes = trx_mi_workspace_bytes(3, vol->B, vol->D, vol->H, vol->W, bins);
+    if (mi_bytes == 0) return 0;
+    return crit_loop_offsets(vol, mi_bytes).total;
+}
+
+extern "C" int trx_flow_mi_run(const trx_volumes *vol, const trx_mi_cfg *cfg, const trx_opt_cfg *opt, const trx_flow_state *st, int iters,
+                               void *workspace, size_t workspace_bytes, void *stream)
+{
+    const int rc = check_criterion_loop(vol, opt, st, iters, workspace, workspace_bytes);
+    if (rc) return rc;
+    if (!cfg || !cfg->range || cfg->bins < 8 || cfg->bins > 64 || !std::isfinite(cfg->alpha)) return TRX_ERR_ARG;
+    if (workspace_bytes < trx_flow_mi_workspace_bytes(vol, cfg->bins)) return TRX_ERR_WORKSPACE;
+    if (st->losses && iters > st->losses_capacity) return TRX_ERR_CAPACITY;
+    const size_t mi_bytes = trx_mi_workspace_bytes(3, vol->B, vol->D, vol->H, vol->W, cfg->bins);
+    return flow_criterion_loop(vol, opt, st, iters, workspace, crit_loop_offsets(vol, mi_bytes), (hipStream_t)stream,
+                               [&](const float *warped, float *loss, float *go, void *cws) {
+                                   return trx_mi_loss_grad(vol->target, warped, 3, vol->B, vol->D, vol->H, vol->W, cfg, loss, go, cws, mi_bytes, stream);
+                               });
 }
 
 extern "C" int trx_flow_step(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt, const trx_flow_state *st,

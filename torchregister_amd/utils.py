@@ -86,6 +86,54 @@ class LocalNCCLoss(nn.Module):
         return _LocalNCCFn.apply(y, yp, self.window, self.alpha, self.eps).mean()
 
 
+class _MIFn(torch.autograd.Function):
+    """loss [B] = Parzen joint-histogram mutual-information loss of (target, warped) through the HIP kernels; gradient wrt warped only."""
+
+    @staticmethod
+    def forward(ctx, y, yp, rng, bins, alpha, normalized):
+        from . import _engine
+        loss, grad = _engine.mi_loss_grad(y, yp, rng, bins, alpha, normalized, need_grad=yp.requires_grad)
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        (grad,) = ctx.saved_tensors
+        if grad is None:
+            return None, None, None, None, None, None
+        return None, grad * gl.view(-1, *([1] * (grad.dim() - 1))), None, None, None, None
+
+
+class MILoss(nn.Module):
+    """alpha * (H(target, warped) - H(warped)) - the joint entropy minus the warped image's, which has the gradient of -alpha * (mutual
+    information) - from a Parzen joint histogram with `bins` bins per image (Mattes-style: box window on the target, cubic B-spline window
+    on the warped image); normalized=True: alpha * (2 - (H(target) + H(warped)) / H(target, warped)).  Both are >= 0 and fall as the
+    images align, whatever (non-linear, non-monotone) map relates their intensities.  EXTENSION: the reference's NMILoss is a Gaussian KDE
+    on a re-sampled lattice; this criterion exists only here and is defined by include/trx.h (trx_mi_loss_grad; CPU restatement
+    tests/mi_ref.py).  Runs on the GPU only; call order (target, warped) like every criterion of the package; batch mean.
+    target_range / moving_range: (lo, hi) of the intensities, or None = fitted to the tensors of each call (the warped one widened to
+    contain 0).  Alone in flow_register(flow_model='direct' | 'bspline') the whole loop runs on the device (trx_flow_mi_run /
+    trx_bspline_mi_run) with the ranges taken once from (target, moving)."""
+
+    def __init__(self, bins=32, alpha=1.0, normalized=False, target_range=None, moving_range=None):
+        super().__init__()
+        self.bins, self.alpha, self.normalized = _engine._mi_bins(bins), float(alpha), bool(normalized)
+        for r in (target_range, moving_range):
+            if r is not None and (len(r) != 2 or not float(r[1]) >= float(r[0])):
+                raise ValueError(f"a range is (lo, hi) with hi >= lo, got {r!r}")
+        self.target_range = None if target_range is None else (float(target_range[0]), float(target_range[1]))
+        self.moving_range = None if moving_range is None else (float(moving_range[0]), float(moving_range[1]))
+
+    def settings(self, weight=1.0):
+        """The dict FlowSolver(mi=...) / BSplineSolver(mi=...) take, alpha multiplied by `weight`."""
+        return dict(bins=self.bins, alpha=self.alpha * float(weight), normalized=self.normalized, target_range=self.target_range,
+                    moving_range=self.moving_range)
+
+    def forward(self, y, yp):
+        rng = _engine.mi_range(y, yp, self.target_range, self.moving_range)
+        return _MIFn.apply(y, yp, rng, self.bins, self.alpha, self.normalized).mean()
+
+
 class SSDLoss(nn.Module):
     """alpha * sum((y - yp)^2) (ref:utils.py:208-221)."""
 

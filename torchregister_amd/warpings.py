@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 from . import _engine
 from ._engine import AffineSolver, FlowSolver, LossSpec
-from .utils import LocalNCCLoss, NCCLoss, NMILoss, SSDLoss, SpatialTransformer  # noqa: F401
+from .utils import LocalNCCLoss, MILoss, NCCLoss, NMILoss, SSDLoss, SpatialTransformer  # noqa: F401
 
 
 class _AffineWarpFn(torch.autograd.Function):
@@ -377,7 +377,7 @@ class flow_register(nn.Module):
     `optimize` reports 'Converged' only when every pair has stopped (`.iterations` holds the per-pair counts).
     flow_model='bspline' (extension): cubic B-spline free-form deformation - a control lattice with `spacing` voxels between control
     points (an int or one per axis) parameterises the flow, flow = base_flow + expand(control), optimised by trx_bspline_run like
-    'direct' (fused MSE / NCC / SSD criteria only; smooth_weight must stay 0).  bending_weight = lambda > 0 adds lambda * (bending energy of
+    'direct' (fused MSE / NCC / SSD criteria, or MILoss alone - trx_bspline_mi_run; smooth_weight must stay 0).  bending_weight = lambda > 0 adds lambda * (bending energy of
     the control lattice, bspline_bending: per voxel of this image size, in its voxel coordinates) to each pair's loss - `.losses` and
     stop_crit see the total, `base_flow` is not penalised; the other flow models raise for it.  `.control` is the final
     control tensor [B, nd, *grid]; `.init_control` (None = zero) and `.base_flow` (None = none) set the start."""
@@ -400,8 +400,8 @@ class flow_register(nn.Module):
             if smooth_weight != 0:
                 raise ValueError("flow_model='bspline' takes no smooth_weight: its regularisers are the control-point spacing and bending_weight")
             used = [nn.MSELoss(), NCCLoss(), NMILoss()] if criterions is None else criterions
-            if loss_spec_from(used, weights[: len(used)]) is None:
-                raise ValueError("flow_model='bspline' runs the fused criteria only: nn.MSELoss (mean), NCCLoss and SSDLoss, "
+            if loss_spec_from(used, weights[: len(used)]) is None and not (len(used) == 1 and isinstance(used[0], MILoss)):
+                raise ValueError("flow_model='bspline' runs the fused criteria only: nn.MSELoss (mean), NCCLoss and SSDLoss, or MILoss alone, "
                                  f"got {[type(c).__name__ for c in used]}")
         self.flow_model = flow_model
         self.criterions = [nn.MSELoss(), NCCLoss(), NMILoss()] if criterions is None else criterions
@@ -447,19 +447,22 @@ class flow_register(nn.Module):
             return self._optimize_unet(moving, target, spec, debug)
         if self.flow_model == "bspline":
             return self._optimize_bspline(moving, target, spec, debug)
-        lncc = None
+        lncc = mi = None
+        if spec is None and moving.dim() == 5 and len(self.criterions) == 1 and isinstance(self.criterions[0], MILoss):
+            # direct flow + mutual information (+ smoothness) as ONE device-side loop (trx_flow_mi_run); ranges fitted once to (target, moving)
+            mi = self.criterions[0].settings(self.weights[0])
         if spec is None and moving.dim() == 5 and len(self.criterions) == 1 and isinstance(self.criterions[0], LocalNCCLoss):
             # direct flow + local-window NCC (+ smoothness): the VoxelMorph-style objective as ONE device-side loop (trx_flow_lncc_run) -
             # no autograd, no torch optimiser; a batch is B independent registrations as on the fused global-loss path below
             c0 = self.criterions[0]
             lncc = dict(window=c0.window, alpha=c0.alpha * float(self.weights[0]), eps=c0.eps)
-        if spec is None and lncc is None:
+        if spec is None and lncc is None and mi is None:
             return self._optimize_generic(moving, target, debug)
         # The whole loop is ONE call: the early stop of ref:warpings.py:231-233 is tested on the device after every iteration (per
         # pair: a batch is B independent registrations), a pair that has converged ignores the remaining iterations, and the flow
         # of its last forward is kept beside the final one - exactly the state the reference leaves behind, with one host sync.
         solver = FlowSolver(moving, target, loss=spec, optimizer=self.optimizer_kind, lr=self.lr, capacity=max(1, self.max_epochs),
-                            smooth_weight=self.smooth_weight, stop_crit=self.stop_crit, keep_last=True, lncc=lncc, init=self.init_flow)
+                            smooth_weight=self.smooth_weight, stop_crit=self.stop_crit, keep_last=True, lncc=lncc, mi=mi, init=self.init_flow)
         solver.run(self.max_epochs)
         done = solver.step.cpu()                       # iterations executed per pair (the only host sync)
         n = int(done.max()) if self.max_epochs > 0 else 0
@@ -475,7 +478,8 @@ class flow_register(nn.Module):
     def _optimize_bspline(self, moving, target, spec, debug):
         """The 'direct' loop with a control lattice as the parameter: one trx_bspline_run call, per-pair early stop on the device, one host sync."""
         from ._engine import BSplineSolver
-        solver = BSplineSolver(moving, target, self.spacing, loss=spec, optimizer=self.optimizer_kind, lr=self.lr, init=self.init_control,
+        mi = self.criterions[0].settings(self.weights[0]) if spec is None else None     # __init__ admits MILoss alone beside the fused criteria
+        solver = BSplineSolver(moving, target, self.spacing, loss=spec, mi=mi, optimizer=self.optimizer_kind, lr=self.lr, init=self.init_control,
                                base=self.base_flow, capacity=max(1, self.max_epochs), stop_crit=self.stop_crit, keep_last=True,
                                bending_weight=self.bending_weight)
         solver.run(self.max_epochs)
