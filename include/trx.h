@@ -45,7 +45,9 @@ extern "C" {
  *        Later addition under the same number: trx_bspline_* and trx_bspline_state (cubic B-spline free-form deformation: control lattice <-> dense
  *        flow, its adjoint, and the device-side loop over them) - new entry points and one new struct only.
  *        Later addition under the same number: trx_mi_* , trx_flow_mi_* , trx_bspline_mi_* and trx_mi_cfg (Parzen joint-histogram mutual information
- *        and the two device-side loops over it) - new entry points and one new struct only. */
+ *        and the two device-side loops over it) - new entry points and one new struct only.
+ *        Later addition under the same number: trx_affine_mi_workspace_bytes, trx_affine_mi_loss_grad, trx_affine_mi_run (rigid / affine registration under
+ *        the mutual information, the warp fused into the histogram and gradient passes) - new entry points only. */
 #define TRX_VERSION 240
 #define TRX_PSTRIDE 12  /* floats per pair in theta / param / adam / best_theta arrays */
 
@@ -536,6 +538,36 @@ int trx_flow_mi_run(const trx_volumes *vol, const trx_mi_cfg *cfg, const trx_opt
 size_t trx_bspline_mi_workspace_bytes(int ndim, int B, int D, int H, int W, int sz, int sy, int sx, int bins);
 int trx_bspline_mi_run(const trx_volumes *vol, const trx_mi_cfg *cfg, const trx_opt_cfg *opt, const trx_bspline_state *st,
                        const int *spacing /*[host]*/, int iters, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- Rigid / affine registration under the mutual information above, the warp fused into its two passes (no warped volume).
+ * 2-D and 3-D.  vol->target: dense [B][D][H][W]; moving_stride and target_stride are honoured; xn / yn / zn as for every affine entry point.  theta
+ * [B][TRX_PSTRIDE] and range [B][4]: one of each per pair.  Sampling: the affine warp's (affine_grid + grid_sample, align_corners=False, zero padding, bi- /
+ * trilinear), coordinates formed as the row-walking affine kernels form them.  Histogram, loss and G exactly as trx_mi_loss_grad defines them, with
+ * w = the sample; dtheta = what trx_affine_warp_backward returns for grad_out = trx_mi_loss_grad's grad_warped (its out-of-bounds corners included).
+ * Per evaluation: one memset, pass 1 (sample + histogram, 8 B/voxel read), the K x K table kernel, pass 2 (sample + gradient rows, 8 B/voxel read), one
+ * reduction - against 36 B/voxel moved by the chain warp -> trx_mi_loss_grad -> warp backward.  A pair gets ceil(N / 16384) blocks and partial rows, whatever B:
+ * its loss and gradient are the same bits on every call and in every batch.  No float atomics, no host sync, no allocation.  cfg->range is read on the
+ * device and must outlive the call.  Status codes before any HIP call: TRX_ERR_ARG (null pointer, bins outside 8 .. 64, alpha not finite, B > 65535,
+ * >= 2^31 voxels), TRX_ERR_NDIM, TRX_ERR_WORKSPACE. */
+
+/* [host] bytes of workspace for this geometry (only ndim, B, D, H, W of `vol` are read) and bin count; 0 = rejected.  Pure arithmetic. */
+size_t trx_affine_mi_workspace_bytes(const trx_volumes *vol /*[host]*/, int bins);
+
+/* loss[B] and (dtheta != NULL) dtheta[B][TRX_PSTRIDE] at theta[B][TRX_PSTRIDE].  Replaces the chain trx_affine_warp -> trx_mi_loss_grad ->
+ * trx_affine_warp_backward (what get_affine_warp + MILoss + backward() enqueue).  Afterwards uint64 counts[B][K][K] lie at the start of the workspace, as
+ * after trx_mi_histogram.  dtheta == NULL: pass 2 is not launched, the loss has the same bits.  Extension: arbiter = oracle/compose.py::affine_warp +
+ * tests/mi_ref.py under torch autograd (tests/affine_mi_ref.py). */
+int trx_affine_mi_loss_grad(const trx_volumes *vol, const trx_mi_cfg *cfg, const float *theta /*[B][TRX_PSTRIDE]*/, float *loss /*[B]*/,
+                            float *dtheta /*nullable, [B][TRX_PSTRIDE]*/, void *workspace, size_t workspace_bytes, void *stream);
+
+/* `iters` iterations back to back: trx_affine_run with the mutual information as the criterion.  Per iteration four launches: pass 1, table, pass 2, and one
+ * update kernel per pair with trx_affine_step's epilogue - (rigid) dtheta -> dpose through Theta's vector-Jacobian product, SGD or Adam on param, theta of
+ * the next forward, losses[b][t] = the loss at the theta of THIS forward, best_theta / best_loss / best_idx by first strict minimum, step, optional grad.
+ * State and semantics: trx_affine_state / trx_affine_run (iters > losses_capacity: TRX_ERR_CAPACITY; the other refusals as above plus trx_affine_step's
+ * for opt and st).  Replaces the generic loop get_affine_warp -> MILoss -> backward() -> torch optimiser -> .item() per iteration.  Extension: arbiter =
+ * tests/affine_mi_ref.py (oracle/compose.py::affine_warp, pose_to_theta + tests/mi_ref.py under torch autograd and torch.optim). */
+int trx_affine_mi_run(const trx_volumes *vol, const trx_mi_cfg *cfg, const trx_opt_cfg *opt, const trx_affine_state *st, int iters, void *workspace,
+                      size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1308,6 +1308,125 @@ def mi_loss_grad(target, warped, rng, bins=32, alpha=1.0, normalized=False, need
     return loss, grad
 
 
+def _mi_pair_batch(moving, target):
+    """_Batch of B single-channel (moving, target) pairs for the fused affine mutual-information entry points."""
+    batch = _Batch(moving, target)
+    if batch.C != 1 or batch.target.shape[1] != 1:
+        raise ValueError("the mutual-information path takes single-channel volumes [B,1,...]")
+    if batch.target.shape[0] != batch.B:
+        raise ValueError("moving and target batch sizes differ")
+    return batch
+
+
+def affine_mi_loss_grad(moving, target, theta, rng, bins=32, alpha=1.0, normalized=False, need_grad=True):
+    """Mutual information of (target, affine warp of moving by theta) and its gradient with respect to theta without a warped volume (extension,
+    include/trx.h: trx_affine_mi_loss_grad): moving / target [B,1,*spatial] fp32 on the GPU, theta [B,nd,nd+1], rng [B,4] (mi_range).
+    Returns (loss [B], dtheta [B,nd,nd+1] or None) - what affine_warp -> mi_loss_grad -> affine_warp_backward give, in two passes over the pair."""
+    lib = _lib.load()
+    batch = _mi_pair_batch(moving, target)
+    B, nd = batch.B, batch.nd
+    if tuple(rng.shape) != (B, 4):
+        raise ValueError(f"expected a range tensor [{B}, 4], got {tuple(rng.shape)}")
+    rng = rng.detach().to(device=batch.device, dtype=torch.float32).contiguous()
+    th = pad_theta(theta.detach().to(batch.device).reshape(B, -1), nd)
+    cfg = _lib.MICfg()
+    cfg.bins, cfg.alpha, cfg.normalized, cfg.range = _mi_bins(bins), float(alpha), int(bool(normalized)), rng.data_ptr()
+    vol = batch.vol()
+    ws_bytes = lib.trx_affine_mi_workspace_bytes(ctypes.byref(vol), cfg.bins)
+    if ws_bytes == 0:
+        raise _lib.TrxError(f"trx_affine_mi_workspace_bytes rejected {B} x {batch.spatial} with {bins} bins")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=batch.device)
+    loss = torch.empty(B, device=batch.device)
+    dth = torch.zeros(B, PSTRIDE, device=batch.device) if need_grad else None
+    with torch.cuda.device(batch.device):
+        rc = lib.trx_affine_mi_loss_grad(ctypes.byref(vol), ctypes.byref(cfg), _lib.ptr(th), _lib.ptr(loss), _lib.ptr(dth), _lib.ptr(ws), ws_bytes,
+                                         _lib.current_stream(batch.device))
+    _lib.check(rc, "trx_affine_mi_loss_grad")
+    return loss, (dth[:, : nd * (nd + 1)].reshape(B, nd, nd + 1) if need_grad else None)
+
+
+class AffineMISolver:
+    """Batched rigid / affine registration under the Parzen joint-histogram mutual information, the whole loop on the GPU (extension, include/trx.h:
+    trx_affine_mi_run): per iteration the warp is fused into the histogram pass and into the gradient pass - no warped volume, no autograd, no
+    torch optimiser, no host sync.  The B pairs are independent: each has its own parameters and its own intensity range.
+
+    moving, target: [B,1,*spatial] fp32 on the GPU.  mode, init, optimizer, lr, capacity, betas, eps as for AffineSolver; the state tensors
+    (param, theta, losses, best_theta, best_loss, best_idx, step, grad) have AffineSolver's meaning.
+    mi: dict(bins=32, alpha=1.0, normalized=False, target_range=None, moving_range=None); a range of None is fitted once, here, to
+    (target, moving), the moving side widened to contain 0."""
+
+    def __init__(self, moving, target, mode="affine", mi=None, optimizer="sgd", lr=1e-5, init=None, capacity=1000, betas=(0.9, 0.999), eps=1e-8):
+        self.lib = _lib.load()
+        self.batch = _mi_pair_batch(moving, target)
+        b, nd, dev = self.batch.B, self.batch.nd, self.batch.device
+        self.nd, self.mode = nd, mode
+        self.opt = opt_cfg(optimizer, lr, betas, eps)
+        nt = nd * (nd + 1)
+        if mode == "affine":
+            th0 = torch.eye(nd, nd + 1, device=dev).repeat(b, 1, 1) if init is None else init.to(dev).reshape(b, nd, nd + 1)
+            self.param = pad_theta(th0, nd)
+            self.theta = self.param.clone()
+        elif mode == "rigid":
+            npose = 6 if nd == 3 else 3
+            if init is None:
+                raise ValueError("rigid mode needs an initial pose (init=[B,%d])" % npose)
+            pose = init.to(device=dev, dtype=torch.float32).reshape(b, npose)
+            self.param = torch.zeros(b, PSTRIDE, device=dev)
+            self.param[:, :npose] = pose
+            self.theta = torch.zeros(b, PSTRIDE, device=dev)
+            self.theta[:, :nt] = pose_to_theta(pose.double()).float()      # the update kernel's fp32 -> fp64 -> fp32 chain
+        else:
+            raise ValueError(f"mode must be 'affine' or 'rigid', got {mode!r}")
+        self.mi, self.mi_range = _mi_cfg({} if mi is None else mi, self.batch.target, self.batch.moving)
+        self.capacity = int(capacity)
+        self.adam_m = torch.zeros(b, PSTRIDE, device=dev)
+        self.adam_v = torch.zeros(b, PSTRIDE, device=dev)
+        self.best_theta = torch.zeros(b, PSTRIDE, device=dev)
+        self.best_loss = torch.full((b,), float("inf"), device=dev)
+        self.best_idx = torch.full((b,), -1, dtype=torch.int32, device=dev)
+        self.losses = torch.full((b, self.capacity), float("nan"), device=dev)
+        self.step = torch.zeros(b, dtype=torch.int32, device=dev)
+        self.grad = torch.zeros(b, PSTRIDE, device=dev)
+        self.vol = self.batch.vol()
+        self.ws_bytes = self.lib.trx_affine_mi_workspace_bytes(ctypes.byref(self.vol), self.mi.bins)
+        if self.ws_bytes == 0:
+            raise _lib.TrxError("trx_affine_mi_workspace_bytes rejected the batch geometry")
+        self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+        st = _lib.AffineState()
+        st.mode = _lib.PARAM_AFFINE if mode == "affine" else _lib.PARAM_RIGID
+        st.param, st.theta = self.param.data_ptr(), self.theta.data_ptr()
+        st.adam_m, st.adam_v = self.adam_m.data_ptr(), self.adam_v.data_ptr()
+        st.best_theta, st.best_loss, st.best_idx = self.best_theta.data_ptr(), self.best_loss.data_ptr(), self.best_idx.data_ptr()
+        st.losses, st.losses_capacity = self.losses.data_ptr(), self.capacity
+        st.step, st.grad = self.step.data_ptr(), self.grad.data_ptr()
+        self.state = st
+        self.enqueued = 0   # iterations enqueued so far (host-side mirror of the device counter `step`)
+
+    def run(self, iters):
+        """Enqueue `iters` iterations on the current stream (no host sync)."""
+        iters = int(iters)
+        if self.enqueued + iters > self.capacity:
+            raise _lib.TrxError(f"loss-curve capacity exceeded: {self.enqueued} iterations enqueued + {iters} requested > capacity "
+                                f"{self.capacity} (create the solver with a larger `capacity`)")
+        self.enqueued += iters
+        with torch.cuda.device(self.batch.device):
+            rc = self.lib.trx_affine_mi_run(ctypes.byref(self.vol), ctypes.byref(self.mi), ctypes.byref(self.opt), ctypes.byref(self.state), iters,
+                                            _lib.ptr(self.workspace), self.ws_bytes, _lib.current_stream(self.batch.device))
+        _lib.check(rc, "trx_affine_mi_run")
+
+    def _unpad(self, t):
+        nd = self.nd
+        return t[:, : nd * (nd + 1)].reshape(-1, nd, nd + 1)
+
+    @property
+    def current_theta(self):
+        return self._unpad(self.theta).clone()
+
+    @property
+    def best(self):
+        return self._unpad(self.best_theta).clone()
+
+
 def local_ncc_loss_grad(target, warped, window=9, alpha=1.0, eps=1e-5, need_grad=True):
     """Local-window NCC (extension, include/trx.h: trx_lncc_loss_grad): target / warped [B,1,*spatial] fp32 on the GPU.
     Returns (loss [B], d loss / d warped (same shape as warped) or None)."""

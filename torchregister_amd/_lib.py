@@ -157,6 +157,10 @@ SIGNATURES = {
     "trx_bspline_mi_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 9),
     "trx_bspline_mi_run": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MICfg), ctypes.POINTER(OptCfg), ctypes.POINTER(BSplineState), c_int_p,
                                           ctypes.c_int, _P, ctypes.c_size_t, _P]),
+    "trx_affine_mi_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Volumes), ctypes.c_int]),
+    "trx_affine_mi_loss_grad": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MICfg), _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "trx_affine_mi_run": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MICfg), ctypes.POINTER(OptCfg), ctypes.POINTER(AffineState), ctypes.c_int, _P,
+                                         ctypes.c_size_t, _P]),
 }
 
 _lib = None

@@ -152,35 +152,31 @@ __device__ __forceinline__ FinRegs<ND> fin_load(const float *param, const float 
     for (int k = 0; k < NPOSE; k++) r.pose_old[k] = rigid ? param[k] : 0.f;
     return r;
 }
-// Outputs: the pair's state (param / theta / Adam moments / step: nullable - the carry prologue's non-designated blocks write none), the caller-visible
-// per-iteration records (losses[t], best theta / loss / index, grad: `user`), and theta of the next forward into LDS (`theta_lds`, nullable).
+// Adam's bias terms of iteration t: 1 - beta1^(t+1) and 1 / sqrt(1 - beta2^(t+1)) (1 and 1 for SGD).  fin_apply keeps its own copy of these lines: calling
+// this function there changes the code of the step kernels' carry prologue (compared instruction by instruction), and those kernels are the headline.
+__device__ __forceinline__ void fin_bias(const trx_opt_cfg &oc, int t, double &bc1, double &rsbc2)
+{
+    bc1 = 1.0; rsbc2 = 1.0;
+    if (oc.kind == TRX_OPT_ADAM) {   // beta^(t+1) by repeated squaring: a dozen fp64 multiplies instead of two pow() calls
+        bc1 = 1.0 - ipow((double)oc.beta1, t + 1);
+        rsbc2 = 1.0 / sqrt(1.0 - ipow((double)oc.beta2, t + 1));
+    }
+}
+// The second half of the epilogue, behind whatever produced the pair's loss and lane i's dL/dtheta_i (fin_apply: the moments of the fused MSE / NCC / SSD
+// step; the mutual-information loop of affine_mi.hip: its table kernel and its own partial rows): the records, (rigid) the pose chain rule, the
+// optimiser update and theta of the next forward.  bc1, rsbc2: fin_bias.  Outputs: the pair's state (param / theta / Adam moments / step: nullable - the
+// carry prologue's non-designated blocks write none), the caller-visible per-iteration records (losses[t], best theta / loss / index, grad: `user`), and
+// theta of the next forward into LDS (`theta_lds`, nullable).
 template <int ND>
-__device__ __forceinline__ void fin_apply(const double *S, const FinRegs<ND> &r, int b, int i, double nvox, int D, int H, int W, const trx_loss_cfg &lc, const trx_opt_cfg &oc,
-                                          const trx_affine_state &st, int mse_rows, float *param_out, float *theta_out, float *m_out, float *v_out, int *step_out, bool user,
-                                          float *theta_lds, double *sh_dth, float *sh_pose)
+__device__ __forceinline__ void fin_update(double total, double dth_i, double bc1, double rsbc2, const FinRegs<ND> &r, int b, int i, const trx_opt_cfg &oc,
+                                           const trx_affine_state &st, float *param_out, float *theta_out, float *m_out, float *v_out, int *step_out, bool user,
+                                           float *theta_lds, double *sh_dth, float *sh_pose)
 {
     constexpr int NT = ND * (ND + 1);
     constexpr int NPOSE = (ND == 3) ? 6 : 3;
     const bool rigid = st.mode == TRX_PARAM_RIGID;
     const int np = rigid ? NPOSE : NT;
-    const int ic = min(i, NT - 1);
     const int t = r.t;
-    double bc1 = 1.0, rsbc2 = 1.0;
-    if (oc.kind == TRX_OPT_ADAM) {   // beta^(t+1) by repeated squaring: a dozen fp64 multiplies instead of two pow() calls
-        bc1 = 1.0 - ipow((double)oc.beta1, t + 1);
-        rsbc2 = 1.0 / sqrt(1.0 - ipow((double)oc.beta2, t + 1));
-    }
-    const double scale[3] = {0.5 * W, 0.5 * H, 0.5 * D};
-    double dth_i, total;
-    if (ND == 3 && mse_rows) {   // S[0] = sum (w - y)^2, S[1 + i] = sum (w - y) J_i:  L = (w_mse / n + w_ssd alpha) S[0],  dL/dw_p = q (w_p - y_p)
-        const double q = (double)lc.w_mse * 2.0 / nvox + (double)lc.w_ssd * (double)lc.ssd_alpha * 2.0;
-        total = 0.5 * q * S[0];
-        dth_i = scale[ic / (ND + 1)] * q * S[1 + ic];
-    } else {
-        const LossCoef L = loss_from_moments(S, nvox, lc);
-        total = L.total;
-        dth_i = scale[ic / (ND + 1)] * (L.c0 * S[5 + ic] + L.cy * S[5 + NT + ic] + L.cw * S[5 + 2 * NT + ic]);
-    }
     const float lossf = (float)total;
     // best = first strict minimum, theta of THIS forward (ref:warpings.py:85-93)
     const bool is_best = (t == 0) || (lossf < r.best_prev);
@@ -240,6 +236,34 @@ __device__ __forceinline__ void fin_apply(const double *S, const FinRegs<ND> &r,
         if (theta_out) theta_out[i] = th_new;
         if (theta_lds) theta_lds[i] = th_new;
     }
+}
+
+// The fused MSE / NCC / SSD step: loss and lane i's dL/dtheta_i from the reduced moments, then fin_update (outputs: see there).
+template <int ND>
+__device__ __forceinline__ void fin_apply(const double *S, const FinRegs<ND> &r, int b, int i, double nvox, int D, int H, int W, const trx_loss_cfg &lc, const trx_opt_cfg &oc,
+                                          const trx_affine_state &st, int mse_rows, float *param_out, float *theta_out, float *m_out, float *v_out, int *step_out, bool user,
+                                          float *theta_lds, double *sh_dth, float *sh_pose)
+{
+    constexpr int NT = ND * (ND + 1);
+    const int ic = min(i, NT - 1);
+    const int t = r.t;
+    double bc1 = 1.0, rsbc2 = 1.0;
+    if (oc.kind == TRX_OPT_ADAM) {   // beta^(t+1) by repeated squaring: a dozen fp64 multiplies instead of two pow() calls
+        bc1 = 1.0 - ipow((double)oc.beta1, t + 1);
+        rsbc2 = 1.0 / sqrt(1.0 - ipow((double)oc.beta2, t + 1));
+    }
+    const double scale[3] = {0.5 * W, 0.5 * H, 0.5 * D};
+    double dth_i, total;
+    if (ND == 3 && mse_rows) {   // S[0] = sum (w - y)^2, S[1 + i] = sum (w - y) J_i:  L = (w_mse / n + w_ssd alpha) S[0],  dL/dw_p = q (w_p - y_p)
+        const double q = (double)lc.w_mse * 2.0 / nvox + (double)lc.w_ssd * (double)lc.ssd_alpha * 2.0;
+        total = 0.5 * q * S[0];
+        dth_i = scale[ic / (ND + 1)] * q * S[1 + ic];
+    } else {
+        const LossCoef L = loss_from_moments(S, nvox, lc);
+        total = L.total;
+        dth_i = scale[ic / (ND + 1)] * (L.c0 * S[5 + ic] + L.cy * S[5 + NT + ic] + L.cw * S[5 + 2 * NT + ic]);
+    }
+    fin_update<ND>(total, dth_i, bc1, rsbc2, r, b, i, oc, st, param_out, theta_out, m_out, v_out, step_out, user, theta_lds, sh_dth, sh_pose);
 }
 
 // The carry buffers of trx_affine_run's one-launch iterations (two of them, by iteration parity): per pair 64 floats -

@@ -22,96 +22,27 @@
 // Fixed point: each converted weight is off by at most 2^-32 (and exact above 2^-8), the remainder absorbs the fp32 rounding of the four weights
 // (their sum is 1 to 2e-7) plus at most 3 * 2^-32, so beyond fp32 rounding of the weights themselves
 //   |P[a][k] - exact| <= 1.5 * 2^-31 * n[a][k] / N   (n: voxels that touch the cell)   and   sum over cells <= 3 * 2^-31.
-#include "trx_common.h"
+#include "mi_dev.h"   // scales and bins of a voxel, the LDS accumulate / flush, the gather from G: shared with affine_mi.hip
 
-#include <algorithm>
 #include <cmath>
 
 namespace trx {
-
-constexpr int kMiChunk = 16384;              // voxels per block of the histogram and gradient passes (64 per thread)
-#define TRX_MI_ONE 2147483648u              // fixed-point units per voxel (2^31)
-
-// K x K tables of 64-bit cells a block of the histogram pass keeps in LDS: one per wave while they fit into 64 KB
-static inline int mi_tables(int K) { return std::min(TRX_WAVES, 8192 / (K * K)); }
-
-struct MiScale {
-    float lo_t, s_t, lo_w, s_w;
-};
-
-// (lo_t, hi_t, lo_w, hi_w) -> offsets and scales, fp32 division
-__device__ __forceinline__ MiScale mi_scale(const float *__restrict__ range, int b, int K)
-{
-#pragma clang fp contract(off)
-    const float lo_t = range[b * 4], hi_t = range[b * 4 + 1], lo_w = range[b * 4 + 2], hi_w = range[b * 4 + 3];
-    MiScale m;
-    m.lo_t = lo_t; m.lo_w = lo_w;
-    m.s_t = hi_t > lo_t ? (float)K / (hi_t - lo_t) : 0.f;
-    m.s_w = hi_w > lo_w ? (float)(K - 3) / (hi_w - lo_w) : 0.f;
-    return m;
-}
-
-// One voxel: target bin a in [0, K - 1], first warped bin c - 1 with c in [1, K - 3], r = u - c in [0, 1], and whether x lies inside [0, K - 3].
-// The index arithmetic is a subtract and a multiply in fp32, never contracted; NaN falls into bin 0.
-struct MiVoxel {
-    int a, c;
-    float r;
-    bool inside;
-};
-
-__device__ __forceinline__ MiVoxel mi_voxel(float t, float w, const MiScale &m, int K)
-{
-#pragma clang fp contract(off)
-    MiVoxel v;
-    const float at = floorf((t - m.lo_t) * m.s_t);
-    v.a = (int)fminf(fmaxf(at, 0.f), (float)(K - 1));
-    const float x = (w - m.lo_w) * m.s_w, top = (float)(K - 3);
-    v.inside = x >= 0.f && x <= top;
-    const float u = 1.f + fminf(fmaxf(x, 0.f), top);
-    v.c = min((int)floorf(u), K - 3);
-    v.r = u - (float)v.c;
-    return v;
-}
 
 __global__ __launch_bounds__(TRX_BLOCK) void mi_hist_kernel(const float *__restrict__ target, const float *__restrict__ warped, unsigned N, int K, int T,
                                                               const float *__restrict__ range, unsigned long long *__restrict__ counts)
 {
     extern __shared__ unsigned long long mi_lds[];           // [T][K][K]
     const int b = blockIdx.y, tid = threadIdx.x, KK = K * K;
-    for (int i = tid; i < T * KK; i += TRX_BLOCK) mi_lds[i] = 0ull;
-    __syncthreads();
+    mi_lds_clear(mi_lds, T * KK);
     const MiScale m = mi_scale(range, b, K);
     const float *t = target + (size_t)b * N, *w = warped + (size_t)b * N;
     unsigned long long *mine = mi_lds + ((tid >> 6) % T) * KK;
     const unsigned first = blockIdx.x * (unsigned)kMiChunk, last = min(N, first + (unsigned)kMiChunk);
 #pragma unroll 4
-    for (unsigned i = first + tid; i < last; i += TRX_BLOCK) {
-        const MiVoxel v = mi_voxel(__builtin_nontemporal_load(t + i), __builtin_nontemporal_load(w + i), m, K);
-        const float r = v.r, r2 = r * r, r3 = r2 * r, u = 1.f - r;
-        const float w0 = u * u * u * (1.f / 6.f), w3 = r3 * (1.f / 6.f);
-        const float w1 = (3.f * r3 - 6.f * r2 + 4.f) * (1.f / 6.f), w2 = (-3.f * r3 + 3.f * r2 + 3.f * r + 1.f) * (1.f / 6.f);
-        const unsigned q0 = __float2uint_rn(w0 * (float)TRX_MI_ONE), q3 = __float2uint_rn(w3 * (float)TRX_MI_ONE);   // each <= 2^31 / 6
-        unsigned q1, q2;
-        if (r < 0.5f) {
-            q2 = __float2uint_rn(w2 * (float)TRX_MI_ONE);
-            q1 = TRX_MI_ONE - q0 - q2 - q3;
-        } else {
-            q1 = __float2uint_rn(w1 * (float)TRX_MI_ONE);
-            q2 = TRX_MI_ONE - q0 - q1 - q3;
-        }
-        unsigned long long *cell = mine + v.a * K + v.c - 1;
-        atomicAdd(cell, (unsigned long long)q0);
-        atomicAdd(cell + 1, (unsigned long long)q1);
-        atomicAdd(cell + 2, (unsigned long long)q2);
-        if (q3) atomicAdd(cell + 3, (unsigned long long)q3);
-    }
+    for (unsigned i = first + tid; i < last; i += TRX_BLOCK)
+        mi_accumulate(mine, mi_voxel(__builtin_nontemporal_load(t + i), __builtin_nontemporal_load(w + i), m, K), K);
     __syncthreads();
-    unsigned long long *dst = counts + (size_t)b * KK;
-    for (int i = tid; i < KK; i += TRX_BLOCK) {
-        unsigned long long s = 0;
-        for (int tb = 0; tb < T; tb++) s += mi_lds[tb * KK + i];
-        if (s) atomicAdd(dst + i, s);
-    }
+    mi_flush(mi_lds, T, KK, counts + (size_t)b * KK);
 }
 
 // sum of the block's 256 values in a fixed tree; every thread gets the total
@@ -184,16 +115,8 @@ __global__ __launch_bounds__(TRX_BLOCK) void mi_grad_kernel(const float *__restr
     float *out = grad + (size_t)b * N;
     const unsigned first = blockIdx.x * (unsigned)kMiChunk, last = min(N, first + (unsigned)kMiChunk);
 #pragma unroll 4
-    for (unsigned i = first + tid; i < last; i += TRX_BLOCK) {
-        const MiVoxel v = mi_voxel(__builtin_nontemporal_load(t + i), __builtin_nontemporal_load(w + i), m, K);
-        const float r = v.r, r2 = r * r, u = 1.f - r;
-        const float *g = mi_g + v.a * K + v.c - 1;
-        float acc = -0.5f * u * u * g[0];
-        acc = fmaf(0.5f * (3.f * r2 - 4.f * r), g[1], acc);
-        acc = fmaf(0.5f * (-3.f * r2 + 2.f * r + 1.f), g[2], acc);
-        acc = fmaf(0.5f * r2, g[3], acc);
-        out[i] = v.inside ? acc : 0.f;
-    }
+    for (unsigned i = first + tid; i < last; i += TRX_BLOCK)
+        out[i] = mi_voxel_grad(mi_g, mi_voxel(__builtin_nontemporal_load(t + i), __builtin_nontemporal_load(w + i), m, K), K);
 }
 
 struct MiGeom {
@@ -210,6 +133,13 @@ static int mi_geom(int ndim, int B, int D, int H, int W, int bins, MiGeom *g)
     g->nchunk = (g->N + kMiChunk - 1) / kMiChunk;
     g->g_offset = ((size_t)B * bins * bins * sizeof(unsigned long long) + 255) & ~(size_t)255;
     g->ws_bytes = g->g_offset + (((size_t)B * bins * bins * sizeof(float) + 255) & ~(size_t)255);
+    return TRX_OK;
+}
+
+int launch_mi_table(const unsigned long long *counts, unsigned N, int B, const trx_mi_cfg *cfg, float *loss, float *G, hipStream_t s)
+{
+    hipLaunchKernelGGL(mi_table_kernel, dim3((unsigned)B), dim3(TRX_BLOCK), 0, s, counts, N, cfg->bins, cfg->alpha, cfg->normalized ? 1 : 0, cfg->range, loss, G);
+    TRX_CHECK_LAUNCH();
     return TRX_OK;
 }
 
@@ -252,9 +182,8 @@ extern "C" int trx_mi_loss_grad(const float *target, const float *warped, int nd
     if (rc != TRX_OK) return rc;
     const int K = cfg->bins;
     float *G = (float *)((char *)workspace + g.g_offset);
-    hipLaunchKernelGGL(mi_table_kernel, dim3((unsigned)B), dim3(TRX_BLOCK), 0, s, (const unsigned long long *)workspace, g.N, K, cfg->alpha, cfg->normalized ? 1 : 0,
-                       cfg->range, loss, grad_warped ? G : (float *)nullptr);
-    TRX_CHECK_LAUNCH();
+    const int rc_table = launch_mi_table((const unsigned long long *)workspace, g.N, B, cfg, loss, grad_warped ? G : (float *)nullptr, s);
+    if (rc_table != TRX_OK) return rc_table;
     if (!grad_warped) return TRX_OK;
     hipLaunchKernelGGL(mi_grad_kernel, dim3(g.nchunk, (unsigned)B), dim3(TRX_BLOCK), (size_t)K * K * sizeof(float), s, target, warped, g.N, K, cfg->range,
                        (const float *)G, grad_warped);

@@ -11,7 +11,7 @@ from torch import cat
 
 from ._engine import _bending_weight
 from .pyramid import pyramid, pyramid_shapes, upsample_flow
-from .warpings import affine_register, flow_register, get_affine_warp, rigid_register
+from .warpings import affine_register, device_loop_settings, flow_register, get_affine_warp, rigid_register
 
 
 def _per_level(value, levels, name):
@@ -26,7 +26,7 @@ def _per_level(value, levels, name):
 class Register():
     def __init__(self, mode='rigid', device='cpu', criterion=None, weight=None, grad_edges=False, debug=False, *,
                  optimizer='sgd', honor_criterion=False, init=None, smooth_weight=0.0, flow_model='unet', levels=1, spacing=None,
-                 bending_weight=0.0):
+                 bending_weight=0.0, device_loop=False):
         '''
         Numerical registration on an AMD GPU (MI355X) behind the TorchRegister API.
 
@@ -52,9 +52,17 @@ class Register():
             bspline_bending) joins each pair's loss; `.losses` and the early stop see the total.  With levels > 1 the same lambda applies to
             each level's own lattice: the energy is per voxel of that level, in that level's voxel coordinates, nothing is rescaled between
             levels, and the base handed up from the coarser levels is not penalised.
+        device_loop : (keyword-only extension, mode='rigid' / 'affine') True: criterion must be exactly [MILoss] with a non-zero weight (ValueError
+            otherwise, here) and optim runs the whole loop on the device (trx_affine_mi_run: the warp fused into the histogram and gradient passes
+            of the mutual information, no host sync per iteration); honor_criterion is implied, a batch is B independent pairs, and with levels > 1
+            each level fits its intensity ranges to that level's images.  False (default): every route as before.
         '''
         if mode not in ('rigid', 'affine', 'flow'):
             raise ValueError("mode must be 'rigid', 'affine' or 'flow'")
+        if device_loop:
+            if mode == 'flow':
+                raise ValueError("device_loop is the fused mutual-information loop of mode='rigid' / 'affine' (mode='flow' with MILoss alone already runs on the device)")
+            device_loop_settings(criterion, weight)     # raises unless the list is exactly [MILoss] with a non-zero weight
         if not isinstance(levels, int) or isinstance(levels, bool) or levels < 1:
             raise ValueError(f"levels must be an int >= 1, got {levels!r}")
         if levels > 1 and mode == 'flow' and flow_model not in ('direct', 'bspline'):
@@ -86,6 +94,7 @@ class Register():
         self.spacing = spacing
         self.bending_weight = bending_weight
         self.levels = levels
+        self.device_loop = bool(device_loop)
         self.control = None
         self.losses = None
         self.final_theta = None
@@ -128,7 +137,7 @@ class Register():
         fn = affine_register if self.mode == 'affine' else rigid_register
         info = {}
         kw = dict(lr=lr, epochs=max_epochs, per=per, device=self.device, debug=self.debug, grad_edges=self.grad_edges,
-                  honor_criterion=self.honor_criterion, optimizer=self.optimizer, init=self.init, info=info)
+                  honor_criterion=self.honor_criterion, optimizer=self.optimizer, init=self.init, info=info, device_loop=self.device_loop)
         if self.criterion is not None and self.weight is not None:           # ref:torchregister.py:85-87,97-99
             kw.update(criterions=self.criterion, weights=self.weight)
         elif self.weight is not None:                                         # ref:torchregister.py:88-90,100-102
@@ -170,7 +179,7 @@ class Register():
                 fn = affine_register if self.mode == 'affine' else rigid_register
                 info = {}
                 kw = dict(lr=lrs[k], epochs=epochs[k], per=per, device=self.device, debug=False, grad_edges=self.grad_edges,
-                          honor_criterion=self.honor_criterion, optimizer=self.optimizer, init=init, info=info)
+                          honor_criterion=self.honor_criterion, optimizer=self.optimizer, init=init, info=info, device_loop=self.device_loop)
                 if self.criterion is not None and self.weight is not None:
                     kw.update(criterions=self.criterion, weights=self.weight)
                 elif self.weight is not None:

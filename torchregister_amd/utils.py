@@ -113,7 +113,11 @@ class MILoss(nn.Module):
     tests/mi_ref.py).  Runs on the GPU only; call order (target, warped) like every criterion of the package; batch mean.
     target_range / moving_range: (lo, hi) of the intensities, or None = fitted to the tensors of each call (the warped one widened to
     contain 0).  Alone in flow_register(flow_model='direct' | 'bspline') the whole loop runs on the device (trx_flow_mi_run /
-    trx_bspline_mi_run) with the ranges taken once from (target, moving)."""
+    trx_bspline_mi_run) with the ranges taken once from (target, moving).  Alone in Register('rigid' | 'affine', ..., device_loop=True) - or
+    affine_register / rigid_register with that keyword - the whole loop runs on the device too (trx_affine_mi_run, AffineMISolver: the warp is
+    fused into the histogram and gradient passes, no warped volume exists), again with the ranges taken once from (target, moving), per pair,
+    and with one theta per pair; without device_loop it is an autograd criterion of the generic rigid / affine loop, which refits the ranges to
+    the warped image on every call and shares one theta among the pairs of a batch."""
 
     def __init__(self, bins=32, alpha=1.0, normalized=False, target_range=None, moving_range=None):
         super().__init__()

@@ -20,7 +20,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _engine
-from ._engine import AffineSolver, FlowSolver, LossSpec
+from ._engine import AffineMISolver, AffineSolver, FlowSolver, LossSpec
 from .utils import LocalNCCLoss, MILoss, NCCLoss, NMILoss, SSDLoss, SpatialTransformer  # noqa: F401
 
 
@@ -279,8 +279,20 @@ def _nmi_affine_loop(moving, target, mode, spec, nmi, w_nmi, lr, epochs, init):
     return [get_affine_warp(final_theta, moving), get_affine_warp(best_theta, moving)], [final_theta, best_theta], res
 
 
+def device_loop_settings(criterions, weights):
+    """device_loop=True (rigid / affine): the criterion list must be exactly one MILoss with a non-zero weight - returns its settings dict
+    (MILoss.settings(weight)), raises ValueError for anything else.  Looks at the list only, never at a tensor."""
+    ok = criterions is not None and weights is not None and len(criterions) == 1 and len(weights) >= 1 and type(criterions[0]) is MILoss and float(weights[0]) != 0.0
+    if not ok:
+        names = None if criterions is None else [type(c).__name__ for c in criterions]
+        raise ValueError(f"device_loop=True runs the fused mutual-information loop: criterions must be exactly [MILoss] with a non-zero weight, got {names} "
+                         f"with weights {None if weights is None else list(weights)[: len(criterions or [])]}")
+    return criterions[0].settings(weights[0])
+
+
 def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, weights, grad_edges, honor_criterion,
-                   optimizer, init, info):
+                   optimizer, init, info, device_loop=False):
+    mi = device_loop_settings(criterions, weights) if device_loop else None      # (before anything else: a refused list touches no tensor)
     if grad_edges:
         raise NotImplementedError("grad_edges=True: the reference's Edge3D pre-filter reflect-pads by 5000 voxels and "
                                   "crashes for every realistic volume (SURVEY Q6); it is not part of the HIP path.")
@@ -289,8 +301,23 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
     npose = 6 if nd == 3 else 3
     if mode == "rigid" and init is None:
         init = torch.rand((6 if nd == 3 else 3), device=moving.device)      # ref:utils.py:316-321 (Q9)
-    spec = loss_spec_from(criterions, weights)
-    if spec is None:
+    spec = None if mi is not None else loss_spec_from(criterions, weights)
+    if mi is not None:
+        # MILoss alone with device_loop=True: the whole loop in trx_affine_mi_run (the warp fused into the histogram and gradient passes), ranges fitted
+        # once to (target, moving); a batch is B independent pairs, each with its own parameters - the same returns as the fused branch below
+        B = moving.shape[0]
+        init_b = None if init is None else (init.reshape(-1, npose).expand(B, -1) if mode == "rigid" else init.reshape(-1, nd, nd + 1).expand(B, nd, nd + 1))
+        solver = AffineMISolver(moving, target, mode=mode, mi=mi, optimizer=optimizer, lr=lr, init=init_b, capacity=max(1, epochs))
+        solver.run(epochs)
+        final_theta, best_theta = solver.current_theta, solver.best
+        if epochs == 0:
+            best_theta = final_theta.clone()
+        warped = [get_affine_warp(final_theta, moving), get_affine_warp(best_theta, moving)]
+        theta = [final_theta, best_theta]
+        res = dict(losses=solver.losses[:, :epochs], final_theta=final_theta, best_theta=best_theta, best_idx=solver.best_idx, solver=solver)
+        if mode == "rigid":
+            res["final_pose"] = solver.param[:, :npose].clone()
+    elif spec is None:
         out = None
         fast = _nmi_fast_path(moving, target, criterions, weights, optimizer)
         if fast is not None:
@@ -318,20 +345,25 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
 
 
 def affine_register(moving, target, lr=1E-5, epochs=1000, per=0.1, device="cpu", debug=True, criterions=None,
-                    weights=[0.33, 0.33, 0.33], grad_edges=True, *, honor_criterion=False, optimizer="sgd", init=None, info=None):
+                    weights=[0.33, 0.33, 0.33], grad_edges=True, *, honor_criterion=False, optimizer="sgd", init=None, info=None,
+                    device_loop=False):
     """ref:warpings.py:30-113.  Returns ([final_warped, best_warped], [final_theta, best_theta]).
 
     NOTE: like the reference, grad_edges defaults to True here when called directly (and then
-    raises, Q6); Register passes grad_edges=False."""
+    raises, Q6); Register passes grad_edges=False.
+    device_loop=True (keyword-only extension, also on rigid_register): criterions must be exactly [MILoss] with a non-zero weight (ValueError
+    otherwise) and the whole loop runs on the device in trx_affine_mi_run (AffineMISolver): honor_criterion is implied, the pairs of a batch are
+    independent, info gets the keys of the fused MSE / NCC / SSD branch.  The default False changes no existing route."""
     return _affine_family("affine", moving, target, lr, epochs, device, debug, criterions, weights, grad_edges,
-                          honor_criterion, optimizer, init, info)
+                          honor_criterion, optimizer, init, info, device_loop)
 
 
 def rigid_register(moving, target, lr=1E-5, epochs=1000, per=0.1, device="cpu", debug=True, criterions=None,
-                   weights=[0.33, 0.33, 0.33], grad_edges=True, *, honor_criterion=False, optimizer="sgd", init=None, info=None):
+                   weights=[0.33, 0.33, 0.33], grad_edges=True, *, honor_criterion=False, optimizer="sgd", init=None, info=None,
+                   device_loop=False):
     """ref:warpings.py:117-174.  `init` = initial pose (default torch.rand on the tensors' device)."""
     return _affine_family("rigid", moving, target, lr, epochs, device, debug, criterions, weights, grad_edges,
-                          honor_criterion, optimizer, init, info)
+                          honor_criterion, optimizer, init, info, device_loop)
 
 
 class _FlowLossFn(torch.autograd.Function):
