@@ -47,7 +47,10 @@ extern "C" {
  *        Later addition under the same number: trx_mi_* , trx_flow_mi_* , trx_bspline_mi_* and trx_mi_cfg (Parzen joint-histogram mutual information
  *        and the two device-side loops over it) - new entry points and one new struct only.
  *        Later addition under the same number: trx_affine_mi_workspace_bytes, trx_affine_mi_loss_grad, trx_affine_mi_run (rigid / affine registration under
- *        the mutual information, the warp fused into the histogram and gradient passes) - new entry points only. */
+ *        the mutual information, the warp fused into the histogram and gradient passes) - new entry points only.
+ *        Later addition under the same number: trx_svf_workspace_bytes, trx_svf_exp, trx_svf_exp_backward, trx_bspline_svf_workspace_bytes,
+ *        trx_bspline_svf_run (stationary velocity field: the exponential by scaling and squaring, its exact adjoint, and the diffeomorphic form of the
+ *        free-form-deformation loop) - new entry points only. */
 #define TRX_VERSION 240
 #define TRX_PSTRIDE 12  /* floats per pair in theta / param / adam / best_theta arrays */
 
@@ -568,6 +571,47 @@ int trx_affine_mi_loss_grad(const trx_volumes *vol, const trx_mi_cfg *cfg, const
  * tests/affine_mi_ref.py (oracle/compose.py::affine_warp, pose_to_theta + tests/mi_ref.py under torch autograd and torch.optim). */
 int trx_affine_mi_run(const trx_volumes *vol, const trx_mi_cfg *cfg, const trx_opt_cfg *opt, const trx_affine_state *st, int iters, void *workspace,
                       size_t workspace_bytes, void *stream);
+
+/* ---- Stationary velocity field (Arsigny et al. 2006; NiftyReg's -vel, VoxelMorph-diff's VecInt; extension: the reference has no such model, its flows
+ * are displacements, ref:warpings.py:178-242).  Fields are [B][ndim][D][H][W] fp32 contiguous (2-D: [B][2][H][W], D = 1), voxel units and channel order
+ * of `flow` above.  S(f, p) = the bi / trilinear sample of field f at the voxel position p, corners outside the volume contributing zero (the sampler
+ * of trx_flow_warp).  With K = squarings in 0 .. 12 and s = inverse ? -1 : +1:
+ *   exp:      u_0 = s 2^-K vel (exact);   u_{k+1}(x) = u_k(x) + S(u_k, x + u_k(x)), k = 0 .. K - 1;   flow = u_K   (K = 0: flow = s vel).
+ *             A position is ONE fp32 add of the voxel index and the displacement; i0 = floor(p), t = p - i0, corner kappa has the weight
+ *             w_kappa(t) = prod_a (kappa_a ? t_a : 1 - t_a) and ok_kappa = whether i0 + kappa lies inside the volume.
+ *   adjoint of one squaring (g = dL/du_{k+1}, u = u_k, i0 and t of p = y + u(y)):
+ *             dL/du_c(y) = g_c(y) + sum_x sum_kappa [i0(x) + kappa = y] ok_kappa w_kappa(t(x)) g_c(x)
+ *                                 + sum_kappa ok_kappa (dw_kappa/dt_c)(t(y)) sum_a g_a(y) u_a(i0(y) + kappa);     dL/dvel = s 2^-K dL/du_0.
+ * exp(vel) is a diffeomorphism up to the discretisation, and inverse != 0 gives its inverse for the price of a second integration.
+ * Forward: one launch for u_0 and one per squaring (a gather; 24 B/voxel moved in 3-D).  Backward: per squaring a scatter-add (splat) and a
+ * finishing pass.  The splat runs in fixed point: with m = max |g| of the pair at that level and m < 2^E, each contribution w g is rounded once to a
+ * multiple of 2^(E - 31) and added with 64-bit integer atomics, LDS first (a tile of source voxels and a halo of 2), then global - at most 2^31
+ * contributions of magnitude <= 2^31 per voxel, so a sum stays below 2^62; beyond the fp32 rounding of w g the splat's error per voxel is at most
+ * 2^(E - 32) per contribution.  No float atomics: the same bits on every call, and a pair's result does not depend on the batch around it.  A
+ * non-finite dflow gives a non-finite dvel for that pair only.  No host sync, no allocation; status codes before any HIP call: TRX_ERR_ARG (null
+ * pointer, squarings outside 0 .. 12, B > 65535, more than 2^31 voxels), TRX_ERR_NDIM, TRX_ERR_WORKSPACE.
+ * Workspace (trx_svf_workspace_bytes; 0 = arguments rejected), each part rounded up to 256 bytes: the levels u_0 .. u_{K-1} (K fields of
+ * 4 B ndim D H W bytes), for K > 0 two gradient fields and the int64 accumulator (8 B ndim D H W bytes), and 13 B maxima of 4 bytes - 1 x 256^3 with
+ * K = 6: 2.0 GB.  CPU restatement: tests/svf_ref.py (exp, exp_backward). */
+size_t trx_svf_workspace_bytes(int ndim, int B, int D, int H, int W, int squarings);
+/* flow = exp(+-vel); leaves u_0 .. u_{K-1} in the workspace. */
+int trx_svf_exp(const float *vel, float *flow, int ndim, int B, int D, int H, int W, int squarings, int inverse, void *workspace,
+                size_t workspace_bytes, void *stream);
+/* dvel = (d exp(+-vel) / d vel)^T dflow.  MUST follow a trx_svf_exp call with the same vel, geometry, squarings, inverse and workspace, with nothing
+ * else writing to that workspace in between: it reads the levels that call kept (vel itself is not read again).  dvel must not overlap dflow. */
+int trx_svf_exp_backward(const float *vel, const float *dflow, float *dvel, int ndim, int B, int D, int H, int W, int squarings, int inverse,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
+/* Diffeomorphic free-form deformation: trx_bspline_run with the expanded lattice (+ st->base) read as a stationary VELOCITY.  Per iteration: expand ->
+ * trx_svf_exp (phi, in the workspace) -> trx_flow_loss_grad at phi -> trx_svf_exp_backward into st->dflow -> reduce -> the bending / decide / update
+ * launches of trx_bspline_run.  trx_bspline_state keeps its whole meaning with `flow` = the velocity: base (a velocity), bending_weight (of the velocity's
+ * lattice), stop_crit, stopped, losses, flow_last (the VELOCITY of the last forward; its deformation is trx_svf_exp of it).  squarings == 0: the data term
+ * is trx_bspline_run's own and the run is bit-identical to it.  Workspace: trx_bspline_svf_workspace_bytes = trx_bspline_workspace_bytes + two fields +
+ * trx_svf_workspace_bytes.  Extension: arbiter = tests/bspline_ref.py::expand + tests/svf_ref.py::exp + oracle/compose.py (flow_warp, weighted_loss) under
+ * torch autograd. */
+size_t trx_bspline_svf_workspace_bytes(int ndim, int B, int D, int H, int W, int sz, int sy, int sx, int squarings);
+int trx_bspline_svf_run(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt, const trx_bspline_state *st,
+                        const int *spacing /*[host]*/, int squarings, int iters, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

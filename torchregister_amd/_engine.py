@@ -530,16 +530,101 @@ def bspline_bending(ctrl, spatial, spacing, grad=False):
     return (energy, dctrl) if grad else energy
 
 
+def _squarings(value):
+    """An int in 0 .. 12, or ValueError."""
+    if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value <= 12:
+        raise ValueError(f"squarings must be an int in 0 .. 12, got {value!r}")
+    return value
+
+
+def _svf_call(velocity, squarings, inverse):
+    _require_gpu(velocity, "velocity")
+    nd = velocity.dim() - 2
+    if nd not in (2, 3) or velocity.shape[1] != nd:
+        raise ValueError(f"expected a velocity field [B,nd,*spatial], got {tuple(velocity.shape)}")
+    K = _squarings(squarings)
+    lib = _lib.load()
+    vel = velocity.detach().to(torch.float32).contiguous()
+    geom = (nd, vel.shape[0]) + _dhw(vel.shape[2:]) + (K, 1 if inverse else 0)
+    ws_bytes = lib.trx_svf_workspace_bytes(*geom[:-1])
+    if ws_bytes == 0:
+        raise _lib.TrxError(f"trx_svf_workspace_bytes rejected {tuple(vel.shape)} with {K} squarings")
+    return lib, vel, geom, torch.empty(ws_bytes, dtype=torch.uint8, device=vel.device), ws_bytes
+
+
+def _svf_forward(velocity, squarings, inverse):
+    """flow and what the backward needs: (lib, vel, geom, workspace with the kept levels, its size)."""
+    call = _svf_call(velocity, squarings, inverse)
+    lib, vel, geom, ws, ws_bytes = call
+    flow = torch.empty_like(vel)
+    with torch.cuda.device(vel.device):
+        rc = lib.trx_svf_exp(_lib.ptr(vel), _lib.ptr(flow), *geom, _lib.ptr(ws), ws_bytes, _lib.current_stream(vel.device))
+    _lib.check(rc, "trx_svf_exp")
+    return flow, call
+
+
+def _svf_backward(call, dflow):
+    lib, vel, geom, ws, ws_bytes = call
+    if dflow.shape != vel.shape:
+        raise ValueError(f"dflow shape {tuple(dflow.shape)} does not match the velocity {tuple(vel.shape)}")
+    _require_gpu(dflow, "dflow")
+    dflow = dflow.detach().to(torch.float32).contiguous()
+    dvel = torch.empty_like(vel)
+    with torch.cuda.device(vel.device):
+        rc = lib.trx_svf_exp_backward(_lib.ptr(vel), _lib.ptr(dflow), _lib.ptr(dvel), *geom, _lib.ptr(ws), ws_bytes, _lib.current_stream(vel.device))
+    _lib.check(rc, "trx_svf_exp_backward")
+    return dvel
+
+
+class _SvfExpFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, velocity, squarings, inverse):
+        flow, ctx.call = _svf_forward(velocity, squarings, inverse)
+        return flow
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        call, ctx.call = ctx.call, None      # the kept levels serve one backward
+        if call is None:
+            raise RuntimeError("svf_exp: backward through the same graph a second time (the kept levels are released after the first)")
+        return _svf_backward(call, grad_out), None, None
+
+
+def svf_exp(velocity, squarings=6, inverse=False):
+    """The exponential of a stationary velocity field [B, nd, *spatial] (fp32, GPU; voxel units, channel i along spatial axis i) by scaling and
+    squaring (trx_svf_exp): u_0 = +-2^-squarings v, u_{k+1}(x) = u_k(x) + u_k(x + u_k(x)) (bi / trilinear, zeros outside); inverse=True
+    integrates -v, the inverse deformation.  Differentiable: the backward is the exact adjoint (trx_svf_exp_backward), so a velocity from
+    any torch module can be integrated."""
+    _squarings(squarings)
+    if torch.is_grad_enabled() and velocity.requires_grad:
+        return _SvfExpFn.apply(velocity, squarings, bool(inverse))
+    return _svf_forward(velocity, squarings, bool(inverse))[0]
+
+
+def svf_exp_backward(velocity, dflow, squarings=6, inverse=False):
+    """dL/dvelocity for flow = svf_exp(velocity, squarings, inverse) and dL/dflow = dflow: trx_svf_exp followed by trx_svf_exp_backward."""
+    return _svf_backward(_svf_forward(velocity, squarings, bool(inverse))[1], dflow)
+
+
 class BSplineSolver:
     """Cubic B-spline free-form deformation (extension): the control lattice `ctrl` [B, nd, *grid] is the parameter, the displacement field
     is base + expand(ctrl); the whole loop (expand, fused loss and dL/dflow, reduce, SGD / Adam, early stop) runs in trx_bspline_run.
     bending_weight = lambda > 0 adds lambda * (bending energy of ctrl, bspline_bending) to each pair's loss: `losses` and the early stop see
     the total; `base` is not penalised.  After run(): `flow` = expand of the current ctrl (+ base), `flow_last` (keep_last or stop_crit) = the flow of the last forward.
     mi = dict(bins=32, alpha=1.0, normalized=False, target_range=None, moving_range=None): the data term is the Parzen joint-histogram mutual
-    information (mi_loss_grad) instead of `loss`, and the loop runs in trx_bspline_mi_run; a range of None is fitted once, here, to (target, moving)."""
+    information (mi_loss_grad) instead of `loss`, and the loop runs in trx_bspline_mi_run; a range of None is fitted once, here, to (target, moving).
+    squarings = None: the above, launch for launch.  squarings = K (an int in 0 .. 12): diffeomorphic - base + expand(ctrl) is a stationary
+    VELOCITY, the deformation is its exponential (svf_exp, K squarings) and the loop runs in trx_bspline_svf_run.  Then `velocity` is the
+    expanded lattice (+ base), `flow` = svf_exp(velocity), `flow_last` the exponential of the last forward's velocity (`velocity_last`),
+    inverse_flow() = svf_exp(velocity, inverse=True); `base` is a velocity.  Not with `mi`."""
 
     def __init__(self, moving, target, spacing, loss=None, optimizer="sgd", lr=1e-3, init=None, base=None, capacity=1000, stop_crit=None,
-                 keep_last=False, betas=(0.9, 0.999), eps=1e-8, bending_weight=0.0, mi=None):
+                 keep_last=False, betas=(0.9, 0.999), eps=1e-8, bending_weight=0.0, mi=None, squarings=None):
+        if squarings is not None:
+            _squarings(squarings)
+            if mi is not None:
+                raise ValueError("squarings (the diffeomorphic model) runs the fused criteria only: mutual information on a velocity field is not built")
+        self.squarings = squarings
         if mi is not None and loss is not None:
             raise ValueError("mi is a data term of its own: give it without `loss`")
         self.lib = _lib.load()
@@ -571,16 +656,23 @@ class BSplineSolver:
         adam = self.opt.kind == _lib.OPT_ADAM
         self.adam_m = torch.zeros(cshape, device=dev) if adam else None
         self.adam_v = torch.zeros(cshape, device=dev) if adam else None
-        self.flow = torch.empty(fshape, device=dev)
+        self.flow = torch.empty(fshape, device=dev)       # squarings: the velocity the loop writes; .flow is replaced by its exponential
         self.dflow = torch.empty(fshape, device=dev)
+        self.velocity = self.flow if squarings is not None else None
         self.capacity = int(capacity)
         self.losses = torch.full((b, self.capacity), float("nan"), device=dev)
         self.step = torch.zeros(b, dtype=torch.int32, device=dev)
         self.stopped = torch.zeros(b, dtype=torch.int32, device=dev) if stop_crit is not None else None
         self.flow_last = torch.empty(fshape, device=dev) if (keep_last or stop_crit is not None) else None
+        self.velocity_last = self.flow_last if squarings is not None else None
         self.vol = self.batch.vol()
         self.mi = None
-        if mi is not None:
+        if squarings is not None:
+            self.ws_bytes = self.lib.trx_bspline_svf_workspace_bytes(nd, b, *_dhw(self.batch.spatial), *self.sp3, squarings)
+            if self.ws_bytes == 0:
+                raise _lib.TrxError(f"trx_bspline_svf_workspace_bytes rejected {b} x {tuple(self.batch.spatial)} with spacing {self.spacing}")
+            self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+        elif mi is not None:
             self.mi, self.mi_range = _mi_cfg(mi, self.batch.target, self.batch.moving)
             self.ws_bytes = self.lib.trx_bspline_mi_workspace_bytes(nd, b, *_dhw(self.batch.spatial), *self.sp3, self.mi.bins)
             if self.ws_bytes == 0:
@@ -593,7 +685,7 @@ class BSplineSolver:
         st.adam_m = self.adam_m.data_ptr() if adam else None
         st.adam_v = self.adam_v.data_ptr() if adam else None
         st.base = self.base.data_ptr() if self.base is not None else None
-        st.flow, st.dflow = self.flow.data_ptr(), self.dflow.data_ptr()
+        st.flow, st.dflow = self.flow.data_ptr(), self.dflow.data_ptr()       # (squarings: self.flow is still the velocity buffer here)
         st.losses, st.losses_capacity, st.step = self.losses.data_ptr(), self.capacity, self.step.data_ptr()
         st.stop_crit = float(stop_crit) if stop_crit is not None else 0.0
         st.stopped = self.stopped.data_ptr() if self.stopped is not None else None
@@ -604,12 +696,24 @@ class BSplineSolver:
         self._expand()
 
     def _expand(self):
-        """flow = base + expand(ctrl): the same call the loop makes, so the bits are those of a forward at the current ctrl."""
+        """flow = base + expand(ctrl): the same call the loop makes, so the bits are those of a forward at the current ctrl.  With squarings
+        that is the velocity, and flow / flow_last become the exponentials of velocity / velocity_last."""
         D, H, W = _dhw(self.batch.spatial)
+        dst = self.flow if self.squarings is None else self.velocity
         with torch.cuda.device(self.batch.device):
-            rc = self.lib.trx_bspline_expand(_lib.ptr(self.ctrl), _lib.ptr(self.base), _lib.ptr(self.flow), self.nd, self.batch.B, D, H, W, *self.sp3,
+            rc = self.lib.trx_bspline_expand(_lib.ptr(self.ctrl), _lib.ptr(self.base), _lib.ptr(dst), self.nd, self.batch.B, D, H, W, *self.sp3,
                                              _lib.ptr(self.workspace), self.ws_bytes, _lib.current_stream(self.batch.device))
         _lib.check(rc, "trx_bspline_expand")
+        if self.squarings is not None:
+            self.flow = svf_exp(self.velocity, self.squarings)
+            if self.velocity_last is not None and self.enqueued > 0:
+                self.flow_last = svf_exp(self.velocity_last, self.squarings)
+
+    def inverse_flow(self):
+        """svf_exp(velocity, inverse=True): the inverse of `flow` (diffeomorphic model only)."""
+        if self.squarings is None:
+            raise ValueError("inverse_flow() needs the diffeomorphic model: create the solver with squarings=K")
+        return svf_exp(self.velocity, self.squarings, inverse=True)
 
     def run(self, iters):
         iters = int(iters)
@@ -618,13 +722,17 @@ class BSplineSolver:
                                 f"{self.capacity} (create the solver with a larger `capacity`)")
         self.enqueued += iters
         with torch.cuda.device(self.batch.device):
-            if self.mi is not None:
+            if self.squarings is not None:
+                rc = self.lib.trx_bspline_svf_run(ctypes.byref(self.vol), ctypes.byref(self.loss_c), ctypes.byref(self.opt), ctypes.byref(self.state),
+                                                  self.sp3, self.squarings, iters, _lib.ptr(self.workspace), self.ws_bytes,
+                                                  _lib.current_stream(self.batch.device))
+            elif self.mi is not None:
                 rc = self.lib.trx_bspline_mi_run(ctypes.byref(self.vol), ctypes.byref(self.mi), ctypes.byref(self.opt), ctypes.byref(self.state),
                                                  self.sp3, iters, _lib.ptr(self.workspace), self.ws_bytes, _lib.current_stream(self.batch.device))
             else:
                 rc = self.lib.trx_bspline_run(ctypes.byref(self.vol), ctypes.byref(self.loss_c), ctypes.byref(self.opt), ctypes.byref(self.state),
                                               self.sp3, iters, _lib.ptr(self.workspace), self.ws_bytes, _lib.current_stream(self.batch.device))
-        _lib.check(rc, "trx_bspline_mi_run" if self.mi is not None else "trx_bspline_run")
+        _lib.check(rc, "trx_bspline_svf_run" if self.squarings is not None else "trx_bspline_mi_run" if self.mi is not None else "trx_bspline_run")
         self._expand()
 
 

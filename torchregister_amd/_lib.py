@@ -161,6 +161,12 @@ SIGNATURES = {
     "trx_affine_mi_loss_grad": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MICfg), _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "trx_affine_mi_run": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MICfg), ctypes.POINTER(OptCfg), ctypes.POINTER(AffineState), ctypes.c_int, _P,
                                          ctypes.c_size_t, _P]),
+    "trx_svf_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
+    "trx_svf_exp": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 7 + [_P, ctypes.c_size_t, _P]),
+    "trx_svf_exp_backward": (ctypes.c_int, [_P, _P, _P] + [ctypes.c_int] * 7 + [_P, ctypes.c_size_t, _P]),
+    "trx_bspline_svf_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 9),
+    "trx_bspline_svf_run": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(LossCfg), ctypes.POINTER(OptCfg), ctypes.POINTER(BSplineState), c_int_p,
+                                           ctypes.c_int, ctypes.c_int, _P, ctypes.c_size_t, _P]),
 }
 
 _lib = None

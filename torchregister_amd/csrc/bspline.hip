@@ -1,6 +1,8 @@
 // Cubic B-spline free-form deformation (Rueckert et al. 1999; extension, the reference has no such model): the operator between a control
 // lattice and a dense flow (trx_bspline_expand), its exact adjoint (trx_bspline_reduce) and a device-side optimisation loop over them
 // (trx_bspline_run), and the bending energy of the lattice with its gradient (trx_bspline_bending; in the loop: trx_bspline_state.bending_weight).
+// The same loop with other data terms: mutual information (trx_bspline_mi_run, csrc/mi.hip) and the diffeomorphic form, in which the expanded
+// lattice is a stationary velocity field (trx_bspline_svf_run, csrc/svf.hip).
 // CPU restatements: tests/bspline_ref.py, tests/bspline_bending_ref.py.
 //
 // Definition (include/trx.h): an axis of S voxels with spacing d has G = (S - 1) / d + 4 control points, point i at voxel (i - 1) d; at
@@ -838,6 +840,58 @@ extern "C" int trx_bspline_mi_run(const trx_volumes *vol, const trx_mi_cfg *cfg,
         r = trx_mi_loss_grad(vol->target, warped, vol->ndim, vol->B, vol->D, vol->H, vol->W, cfg, mloss, go, ws + l.o_mi, l.mi_bytes, stream);
         if (r != TRX_OK) return r;
         return trx_flow_warp_backward(vol, st->flow, 1, go, st->dflow, stream);
+    });
+}
+
+// Diffeomorphic free-form deformation (csrc/svf.hip): the expanded lattice is a stationary velocity field.  Behind the loop's workspace lie
+// phi = exp(v), dL/dphi and trx_svf_exp's workspace (the kept levels, which its backward reads).
+struct BsSvfLayout {
+    size_t o_phi, o_dphi, o_svf, svf_bytes, ws_bytes;
+};
+
+static int bspline_svf_layout(const BsGeom &g, int squarings, BsSvfLayout *l)
+{
+    l->svf_bytes = trx_svf_workspace_bytes(g.ndim, g.B, g.S[0], g.S[1], g.S[2], squarings);
+    if (l->svf_bytes == 0) return TRX_ERR_ARG;
+    const size_t field = (((size_t)g.B * g.ndim * g.S[0] * g.S[1] * g.S[2] * sizeof(float)) + 255) & ~(size_t)255;
+    l->o_phi = (g.ws_bytes + 255) & ~(size_t)255;
+    l->o_dphi = l->o_phi + field;
+    l->o_svf = l->o_dphi + field;
+    l->ws_bytes = l->o_svf + l->svf_bytes;
+    return TRX_OK;
+}
+
+extern "C" size_t trx_bspline_svf_workspace_bytes(int ndim, int B, int D, int H, int W, int sz, int sy, int sx, int squarings)
+{
+    BsGeom g;
+    BsSvfLayout l;
+    if (bspline_geom(ndim, B, D, H, W, sz, sy, sx, &g) != TRX_OK || bspline_svf_layout(g, squarings, &l) != TRX_OK) return 0;
+    return l.ws_bytes;
+}
+
+extern "C" int trx_bspline_svf_run(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt, const trx_bspline_state *st, const int *spacing,
+                                   int squarings, int iters, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!loss) return TRX_ERR_ARG;
+    BsGeom g;
+    int rc = bspline_run_checks(vol, opt, st, spacing, iters, workspace, &g);
+    if (rc != TRX_OK) return rc;
+    BsSvfLayout l;
+    if ((rc = bspline_svf_layout(g, squarings, &l)) != TRX_OK) return rc;
+    if (workspace_bytes < l.ws_bytes) return TRX_ERR_WORKSPACE;
+    if (st->losses && iters > st->losses_capacity) return TRX_ERR_CAPACITY;
+    char *ws = (char *)workspace;
+    float *terms = (float *)(ws + g.terms_offset), *phi = (float *)(ws + l.o_phi), *dphi = (float *)(ws + l.o_dphi);
+    if (squarings == 0)   // exp is the identity: trx_bspline_run's data term, launch for launch
+        return bspline_loop(g, vol, opt, st, iters, terms, 4, workspace, (hipStream_t)stream, [&]() {
+            return trx_flow_loss_grad(vol, loss, st->flow, terms, st->dflow, ws + g.flow_offset, g.flow_bytes, stream);
+        });
+    return bspline_loop(g, vol, opt, st, iters, terms, 4, workspace, (hipStream_t)stream, [&]() {
+        int r = trx_svf_exp(st->flow, phi, g.ndim, g.B, g.S[0], g.S[1], g.S[2], squarings, 0, ws + l.o_svf, l.svf_bytes, stream);
+        if (r != TRX_OK) return r;
+        r = trx_flow_loss_grad(vol, loss, phi, terms, dphi, ws + g.flow_offset, g.flow_bytes, stream);
+        if (r != TRX_OK) return r;
+        return trx_svf_exp_backward(st->flow, dphi, st->dflow, g.ndim, g.B, g.S[0], g.S[1], g.S[2], squarings, 0, ws + l.o_svf, l.svf_bytes, stream);
     });
 }
 

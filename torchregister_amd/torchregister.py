@@ -9,7 +9,7 @@ U-Net-generated flow, 'direct' = the flow field itself is the parameter), levels
 import torch
 from torch import cat
 
-from ._engine import _bending_weight
+from ._engine import _bending_weight, _squarings
 from .pyramid import pyramid, pyramid_shapes, upsample_flow
 from .warpings import affine_register, device_loop_settings, flow_register, get_affine_warp, rigid_register
 
@@ -26,7 +26,7 @@ def _per_level(value, levels, name):
 class Register():
     def __init__(self, mode='rigid', device='cpu', criterion=None, weight=None, grad_edges=False, debug=False, *,
                  optimizer='sgd', honor_criterion=False, init=None, smooth_weight=0.0, flow_model='unet', levels=1, spacing=None,
-                 bending_weight=0.0, device_loop=False):
+                 bending_weight=0.0, device_loop=False, diffeomorphic=False, squarings=6):
         '''
         Numerical registration on an AMD GPU (MI355X) behind the TorchRegister API.
 
@@ -52,6 +52,13 @@ class Register():
             bspline_bending) joins each pair's loss; `.losses` and the early stop see the total.  With levels > 1 the same lambda applies to
             each level's own lattice: the energy is per voxel of that level, in that level's voxel coordinates, nothing is rescaled between
             levels, and the base handed up from the coarser levels is not penalised.
+        diffeomorphic, squarings : (keyword-only extension, mode='flow' with flow_model='bspline' and the fused criteria only; ValueError otherwise,
+            and with MILoss, here) True: the lattice parameterises a stationary VELOCITY field and the deformation is its exponential by `squarings`
+            (0 .. 12, default 6) steps of scaling and squaring (svf_exp; trx_bspline_svf_run) - free of folds up to the discretisation, and
+            invertible.  After optim: `.theta` is the flow of the last forward as always, `.velocity` its velocity, `.control` the lattice,
+            `.inverse_flow` = exp(-velocity), and `.inverse(x)` warps x with it.  With levels > 1 the hand-over passes the VELOCITY: a level's base
+            is upsample_flow(the previous level's final velocity), its velocity is base + expand(control), and the exponential is taken of the
+            sum; bending_weight acts on each level's own lattice as without diffeomorphic.
         device_loop : (keyword-only extension, mode='rigid' / 'affine') True: criterion must be exactly [MILoss] with a non-zero weight (ValueError
             otherwise, here) and optim runs the whole loop on the device (trx_affine_mi_run: the warp fused into the histogram and gradient passes
             of the mutual information, no host sync per iteration); honor_criterion is implied, a batch is B independent pairs, and with levels > 1
@@ -78,6 +85,16 @@ class Register():
         bending_weight = _bending_weight(bending_weight)
         if bending_weight != 0 and not (mode == 'flow' and flow_model == 'bspline'):
             raise ValueError("bending_weight is the bending-energy penalty of mode='flow' with flow_model='bspline'")
+        squarings = _squarings(squarings)
+        if diffeomorphic:
+            if not (mode == 'flow' and flow_model == 'bspline'):
+                raise ValueError("diffeomorphic=True is the velocity-field form of mode='flow' with flow_model='bspline'")
+            from .utils import MILoss
+            if any(isinstance(c, MILoss) for c in (criterion or [])):
+                raise ValueError("diffeomorphic=True runs the fused criteria only (nn.MSELoss, NCCLoss, SSDLoss): mutual information on a velocity field is not built")
+        self.diffeomorphic, self.squarings = bool(diffeomorphic), squarings
+        self.velocity = self.inverse_flow = None
+        self._inverse_warp = None
         self.criterion = criterion
         self.weight = weight
         self.mode = mode
@@ -106,7 +123,7 @@ class Register():
         kw = dict(mode='bilinear', n=n, lr=lr, max_epochs=max_epochs, optimizer=self.optimizer, smooth_weight=self.smooth_weight,
                   flow_model=self.flow_model)
         if self.flow_model == 'bspline':
-            kw.update(spacing=self.spacing, bending_weight=self.bending_weight)
+            kw.update(spacing=self.spacing, bending_weight=self.bending_weight, diffeomorphic=self.diffeomorphic, squarings=self.squarings)
         if self.criterion is not None and self.weight is not None:           # ref:torchregister.py:71-73
             kw.update(criterions=self.criterion, weights=self.weight)
         elif self.weight is not None:                                         # ref:torchregister.py:74-76
@@ -132,6 +149,7 @@ class Register():
             self.losses = flowreg.losses
             self.final_theta = flowreg.final_flow
             self.control = flowreg.control
+            self.velocity, self.inverse_flow, self._inverse_warp = flowreg.velocity, flowreg.inverse_flow, flowreg.inverse
             return
 
         fn = affine_register if self.mode == 'affine' else rigid_register
@@ -171,7 +189,8 @@ class Register():
                 else:
                     reg.init_flow = up
                 reg.optimize(movs[k], tgts[k], self.device, False)
-                init = reg.final_flow
+                init = reg.final_velocity if self.diffeomorphic else reg.final_flow      # diffeomorphic: the levels add up as velocities
+                self.velocity, self.inverse_flow, self._inverse_warp = reg.velocity, reg.inverse_flow, reg.inverse
                 self.theta, self.warp, self.final_theta = reg.flow, reg.deform, reg.final_flow
                 self.control = reg.control
                 self.losses = reg.losses
@@ -205,3 +224,11 @@ class Register():
         if self.mode == 'flow':
             return self.warp(moving)
         return self.warp(self.theta.detach(), moving)
+
+    def inverse(self, x):
+        '''
+        Warp x [B,c,x,y(,z)] with the inverse of the deformation found by optim, exp(-velocity) (diffeomorphic=True only).
+        '''
+        if self.inverse_flow is None:
+            raise RuntimeError("inverse() needs diffeomorphic=True and optim() first")
+        return self._inverse_warp(x)

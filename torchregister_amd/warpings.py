@@ -412,14 +412,26 @@ class flow_register(nn.Module):
     'direct' (fused MSE / NCC / SSD criteria, or MILoss alone - trx_bspline_mi_run; smooth_weight must stay 0).  bending_weight = lambda > 0 adds lambda * (bending energy of
     the control lattice, bspline_bending: per voxel of this image size, in its voxel coordinates) to each pair's loss - `.losses` and
     stop_crit see the total, `base_flow` is not penalised; the other flow models raise for it.  `.control` is the final
-    control tensor [B, nd, *grid]; `.init_control` (None = zero) and `.base_flow` (None = none) set the start."""
+    control tensor [B, nd, *grid]; `.init_control` (None = zero) and `.base_flow` (None = none) set the start.
+    diffeomorphic=True (keyword-only extension, flow_model='bspline' with the fused criteria only; ValueError otherwise, and with MILoss):
+    base_flow + expand(control) is a stationary VELOCITY and the deformation is its exponential by `squarings` (0 .. 12) steps of scaling and
+    squaring (_engine.svf_exp; the loop runs in trx_bspline_svf_run) - free of folds up to the discretisation, with exp(-velocity) as its
+    inverse.  Then `.flow` / `.final_flow` are the exponentials of `.velocity` (the last forward's) / `.final_velocity`, `.inverse_flow` =
+    exp(-velocity), `.inverse(x)` warps x with it, and `base_flow` is a velocity."""
 
     def __init__(self, img_size, mode="bilinear", in_c=1, n=1, criterions=None, weights=[0.33, 0.33, 0.33], lr=1E-3,
                  max_epochs=2000, stop_crit=1E-4, *, flow_model="unet", optimizer="sgd", smooth_weight=0.0, spacing=None,
-                 bending_weight=0.0):
+                 bending_weight=0.0, diffeomorphic=False, squarings=6):
         super().__init__()
         if flow_model not in ("unet", "direct", "bspline"):
             raise ValueError("flow_model must be 'unet', 'direct' or 'bspline'")
+        self.diffeomorphic = bool(diffeomorphic)
+        self.squarings = _engine._squarings(squarings)
+        if self.diffeomorphic:
+            if flow_model != "bspline":
+                raise ValueError(f"diffeomorphic=True is the velocity-field form of flow_model='bspline'; flow_model={flow_model!r} has none")
+            if any(isinstance(c, MILoss) for c in (criterions or [])):
+                raise ValueError("diffeomorphic=True runs the fused criteria only (nn.MSELoss, NCCLoss, SSDLoss): mutual information on a velocity field is not built")
         self.img_size = tuple(int(s) for s in img_size)
         if flow_model != "bspline" and spacing is not None:
             raise ValueError(f"spacing is the control-point spacing of flow_model='bspline'; flow_model={flow_model!r} has none")
@@ -456,6 +468,7 @@ class flow_register(nn.Module):
         self.control = None        # flow_model='bspline': the final control tensor
         self.init_control = None   # flow_model='bspline': the control tensor the optimisation starts from (None = zero)
         self.base_flow = None      # flow_model='bspline': a fixed dense flow the lattice adds to (None = none; Register's coarse-to-fine loop)
+        self.velocity = self.final_velocity = self.inverse_flow = None   # diffeomorphic=True: see the class docstring
 
     def forward(self, x, device=None):
         if self.model is not None:
@@ -513,12 +526,16 @@ class flow_register(nn.Module):
         mi = self.criterions[0].settings(self.weights[0]) if spec is None else None     # __init__ admits MILoss alone beside the fused criteria
         solver = BSplineSolver(moving, target, self.spacing, loss=spec, mi=mi, optimizer=self.optimizer_kind, lr=self.lr, init=self.init_control,
                                base=self.base_flow, capacity=max(1, self.max_epochs), stop_crit=self.stop_crit, keep_last=True,
-                               bending_weight=self.bending_weight)
+                               bending_weight=self.bending_weight, squarings=self.squarings if self.diffeomorphic else None)
         solver.run(self.max_epochs)
         done = solver.step.cpu()
         n = int(done.max()) if self.max_epochs > 0 else 0
         self.flow = solver.flow_last if self.max_epochs > 0 else solver.flow
         self.final_flow = solver.flow
+        if self.diffeomorphic:
+            self.velocity = solver.velocity_last if self.max_epochs > 0 else solver.velocity
+            self.final_velocity = solver.velocity
+            self.inverse_flow = _engine.svf_exp(self.velocity, self.squarings, inverse=True)
         self.control = solver.ctrl
         self.losses = solver.losses[:, :n]
         self.iterations = done
@@ -582,3 +599,9 @@ class flow_register(nn.Module):
 
     def deform(self, x):
         return self.warp(x, self.flow)
+
+    def inverse(self, x):
+        """x warped with exp(-velocity), the inverse of the deformation `deform` applies (diffeomorphic=True only)."""
+        if self.inverse_flow is None:
+            raise RuntimeError("inverse() needs diffeomorphic=True and a finished optimize()")
+        return self.warp(x, self.inverse_flow)
