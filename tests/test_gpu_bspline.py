@@ -13,6 +13,7 @@ import torch.nn as nn
 import bspline_ref as ref
 import phantoms as ph
 from conftest import bar
+from loop_arbiters import bspline_arbiter as _arbiter, bspline_ctrl0 as _ctrl0, loop_pair as _pair, rand as _rand
 
 pytestmark = pytest.mark.gpu
 
@@ -22,11 +23,6 @@ def tr():
     import torchregister_amd as tr
     assert torch.cuda.is_available()
     return tr
-
-
-def _rand(shape, seed, lo=-1.0, hi=3.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.rand(shape, generator=g) * (hi - lo) + lo
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -116,17 +112,6 @@ def test_constant_and_linear_control_lattices(tr):
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # 5. determinism and batch independence
 # ---------------------------------------------------------------------------------------------------------------------------------------
-def _pair(shape, seed=0, B=1):
-    """Targets and movings of the local-NCC loop test: two different blob phantoms plus a ripple."""
-    tgt = torch.cat([ph.blobs(shape, 61 + 10 * b + seed) + 0.05 * ph.vol(shape, 0.031, "sin") for b in range(B)])
-    mov = torch.cat([ph.blobs(shape, 62 + 10 * b + seed) + 0.05 * ph.vol(shape, 0.027, "cos") for b in range(B)])
-    return mov, tgt
-
-
-def _ctrl0(B, shape, spacing, seed, amp=0.4):
-    return _rand((B, len(shape)) + ref.grid(shape, spacing), seed, -amp, amp)
-
-
 def test_two_calls_give_equal_bits_and_pairs_do_not_see_each_other(tr):
     sp, d = (13, 18, 23), (4, 5, 3)
     c, base, g = _rand((2, 3) + ref.grid(sp, d), 3).cuda(), _rand((2, 3) + sp, 4).cuda(), _rand((2, 3) + sp, 5).cuda()
@@ -230,23 +215,6 @@ def test_calls_stay_inside_their_buffers(tr, B, sp, d):
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # 7. the loop against torch autograd on the CPU
 # ---------------------------------------------------------------------------------------------------------------------------------------
-def _arbiter(mov, tgt, spacing, ctrl0, lr, iters, optimizer, dtype, base=None, **loss_kw):
-    """tests/bspline_ref.py::expand -> oracle/compose.py flow_warp -> weighted_loss under torch autograd + torch.optim, on the CPU."""
-    from oracle import compose
-    sp = tuple(mov.shape[2:])
-    mov, tgt = mov.to(dtype), tgt.to(dtype)
-    c = ctrl0.to(dtype).clone().requires_grad_()
-    opt = torch.optim.SGD([c], lr) if optimizer == "sgd" else torch.optim.Adam([c], lr)
-    losses = []
-    for _ in range(iters):
-        opt.zero_grad()
-        e = compose.weighted_loss(tgt, compose.flow_warp(mov, ref.expand(c, sp, spacing, base=base, dtype=dtype)), **loss_kw)
-        e.backward()
-        opt.step()
-        losses.append(e.item())
-    return np.asarray(losses), c.detach().numpy()
-
-
 @pytest.mark.parametrize("shape,spacing,optimizer,lr,loss_kw", [((20, 24, 28), (5, 4, 6), "adam", 0.1, dict(w_ncc=1.0)),
                                                                 ((20, 24, 28), (5, 4, 6), "sgd", 1000.0, dict(w_mse=1.0)),
                                                                 ((40, 44), (5, 6), "adam", 0.05, dict(w_mse=1.0, w_ncc=0.01))])

@@ -11,6 +11,7 @@ import torch
 import oracle
 import phantoms as ph
 from conftest import bar
+from loop_arbiters import torch_flow_loop as _torch_flow_ref     # plain-torch reference of the extensions (Adam, smoothness) on CPU
 
 pytestmark = pytest.mark.gpu
 
@@ -87,29 +88,6 @@ def test_flow_trajectories_vs_golden(eng, trajectories, name, loss):
     assert np.max(np.abs(s.flow.cpu().numpy() - f32)) <= bar(f32, f64, 1e-4)
     w = eng.flow_warp(mov.cuda(), s.flow).cpu().numpy()
     assert np.max(np.abs(w - g[f"{name}/final_warped32"])) <= bar(g[f"{name}/final_warped32"], g[f"{name}/final_warped64"], 1e-4)
-
-
-def _torch_flow_ref(mov, tgt, lr, iters, optimizer, smooth, dtype):
-    """Plain-torch reference of the extensions (Adam, smoothness) on CPU."""
-    from oracle import compose
-    nd = mov.dim() - 2
-    mov, tgt = mov.to(dtype), tgt.to(dtype)
-    fl = torch.zeros(1, nd, *mov.shape[2:], dtype=dtype, requires_grad=True)
-    opt = torch.optim.SGD([fl], lr) if optimizer == "sgd" else torch.optim.Adam([fl], lr)
-    losses = []
-    for _ in range(iters):
-        opt.zero_grad()
-        e = compose.ncc_loss(tgt, compose.flow_warp(mov, fl))
-        if smooth:
-            reg = 0.0
-            for d in range(nd):
-                df = fl.diff(dim=2 + d)
-                reg = reg + (df * df).mean()
-            e = e + smooth * reg / nd
-        e.backward()
-        opt.step()
-        losses.append(e.item())
-    return np.asarray(losses), fl.detach().numpy()
 
 
 @pytest.mark.parametrize("optimizer,smooth", [("sgd", 5.0), ("adam", 0.0), ("adam", 2.0)])

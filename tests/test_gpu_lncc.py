@@ -8,6 +8,7 @@ import torch
 
 import phantoms as ph
 from conftest import bar
+from loop_arbiters import lncc_pair as _pair, lncc_ref as _ref, torch_lncc_flow_loop as _torch_lncc_flow_loop
 from oracle import compose
 
 pytestmark = pytest.mark.gpu
@@ -18,28 +19,6 @@ def eng():
     import torchregister_amd._engine as e
     assert torch.cuda.is_available()
     return e
-
-
-def _ref(tgt, wrp, window, alpha, dtype):
-    y = tgt.to(dtype)
-    w = wrp.to(dtype).clone().requires_grad_()
-    losses, grads = [], []
-    for b in range(y.shape[0]):      # per pair: the kernel returns one loss per pair
-        l = compose.local_ncc_loss(y[b:b + 1], w[b:b + 1], window, alpha)
-        (g,) = torch.autograd.grad(l, w)
-        losses.append(l.item())
-        grads.append(g[b:b + 1].numpy())
-    return np.asarray(losses), np.concatenate(grads)
-
-
-def _pair(shape, B=1):
-    nd = len(shape)
-    tgt = torch.cat([ph.blobs(shape, 300 + b) + 0.05 * ph.vol(shape, 0.37 + 0.01 * b, "sin") for b in range(B)])
-    if nd == 3:
-        wrp = torch.cat([compose.affine_warp(torch.tensor(ph.THETA_STAR3)[None], tgt[b:b + 1]) for b in range(B)])
-    else:
-        wrp = torch.cat([compose.affine_warp(torch.tensor(ph.THETA_STAR2)[None], tgt[b:b + 1]) for b in range(B)])
-    return tgt, wrp + 0.02 * ph.vol(tuple(wrp.shape[2:]), 0.23, "cos")
 
 
 CASES = [((70, 20, 36), 9, 1), ((97, 12, 33), 5, 2), ((20, 18, 44), 9, 1), ((9, 33, 36), 9, 2), ((12, 40, 70), 5, 1), ((7, 7, 7), 9, 1), ((16, 16, 32), 3, 1), ((24, 40, 33), 7, 1),
@@ -127,24 +106,6 @@ def test_lncc_full_size_properties(eng):
 
 
 # ----------------------------------------------------------------------------- round 3: the local-NCC loop on the device
-def _torch_lncc_flow_loop(mov, tgt, lr, iters, optimizer, smooth, window, flow0, dtype):
-    """arbiter: oracle/compose.py (local_ncc_loss, flow_warp, smooth_regulariser) under torch autograd + torch.optim, on the CPU"""
-    from oracle import compose
-    mov, tgt = mov.to(dtype), tgt.to(dtype)
-    fl = flow0.to(dtype).clone().requires_grad_()
-    opt = torch.optim.SGD([fl], lr) if optimizer == "sgd" else torch.optim.Adam([fl], lr)
-    losses = []
-    for _ in range(iters):
-        opt.zero_grad()
-        e = compose.local_ncc_loss(tgt, compose.flow_warp(mov, fl), window=window)
-        if smooth:
-            e = e + compose.smooth_regulariser(fl, smooth)
-        e.backward()
-        opt.step()
-        losses.append(e.item())
-    return np.asarray(losses), fl.detach().numpy()
-
-
 @pytest.mark.parametrize("optimizer,lr,smooth,window", [("sgd", 30.0, 0.0, 5), ("adam", 0.05, 2.0, 9), ("adam", 0.05, 0.0, 7), ("sgd", 20.0, 3.0, 9)])
 def test_lncc_flow_loop_vs_torch_autograd(optimizer, lr, smooth, window):
     """trx_flow_lncc_run (warp -> window sums -> gradient -> smoothness -> SGD / Adam, all on the device) against the same objective
