@@ -50,7 +50,9 @@ extern "C" {
  *        the mutual information, the warp fused into the histogram and gradient passes) - new entry points only.
  *        Later addition under the same number: trx_svf_workspace_bytes, trx_svf_exp, trx_svf_exp_backward, trx_bspline_svf_workspace_bytes,
  *        trx_bspline_svf_run (stationary velocity field: the exponential by scaling and squaring, its exact adjoint, and the diffeomorphic form of the
- *        free-form-deformation loop) - new entry points only. */
+ *        free-form-deformation loop) - new entry points only.
+ *        Later addition under the same number: trx_mi_cfg grows by one trailing field, `mask` (a region of interest on the target lattice for every
+ *        mutual-information entry point; NULL = every voxel, the launches and bits of before) - no entry point changed its signature. */
 #define TRX_VERSION 240
 #define TRX_PSTRIDE 12  /* floats per pair in theta / param / adam / best_theta arrays */
 
@@ -509,12 +511,26 @@ int trx_bspline_run(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_
  * |P[a][k] - exact| <= 1.5 * 2^-31 n[a][k] / N for the n[a][k] voxels that touch the cell, at most 3 * 2^-31 summed over the table.  No float atomics; entropies in fp64 in a fixed order: the same bits on every call, and a pair's result does not depend on
  * the batch around it.  One memset and three launches (histogram 8 B/voxel, the K x K table, gradient 12 B/voxel; grad_warped == NULL: two), no host
  * sync, no allocation; status codes (TRX_ERR_ARG: null pointer, bins outside 8 .. 64, alpha not finite; TRX_ERR_NDIM; TRX_ERR_WORKSPACE) before any
- * HIP call.  CPU restatement: tests/mi_ref.py. */
+ * HIP call.  CPU restatement: tests/mi_ref.py.
+ * Region of interest, cfg->mask != NULL: a binary mask on the target lattice, one per pair, M_b = {v : mask[b][v] != 0}, N_m = |M_b|.
+ *   histogram    only voxels v in M_b are accumulated, each adding exactly 2^31 units as above: sum(counts[b]) = N_m 2^31 exactly;
+ *   P, G         P = counts / (N_m 2^31), G scaled by s_w / N_m.  N_m is never known to the host and costs no sync: the table kernel sums the pair's
+ *                K^2 64-bit cells (integers: exact, any order) and divides by 2^31.  With an all-ones mask N_m = N and every operation behind it is
+ *                the unmasked call's: the same bits;
+ *   N_m = 0      loss[b] = 0, G = 0, gradient 0: no division by zero, no NaN, the other pairs of the batch untouched;
+ *   grad_warped  0 for v outside M_b (the array is fully written); inside, the definition above with N_m for N.
+ * Mutual information depends on nothing but the multiset of (t, w) pairs, so this is the unmasked definition applied to the selected voxels (CPU
+ * restatement: tests/mi_mask_ref.py).  The masked passes read one byte more per voxel (9 and 9 B/voxel read).  Same bits on every call, a pair
+ * does not depend on its batch, no new status code, the workspace sizes do not change.  cfg->mask == NULL: the launches and bits of before.
+ * Every entry point that takes a trx_mi_cfg honours it: trx_mi_histogram, trx_flow_mi_run and trx_bspline_mi_run (through trx_mi_loss_grad, once per
+ * iteration), trx_affine_mi_loss_grad and trx_affine_mi_run (below). */
 typedef struct {
     int bins;            /* K: 8 .. 64 */
     float alpha;
     int normalized;      /* 0: alpha (H_TW - H_W);  otherwise: alpha (2 - (H_T + H_W) / H_TW) */
     const float *range;  /* device [B][4]: lo_t, hi_t, lo_w, hi_w */
+    const unsigned char *mask;   /* device [B][D][H][W] (D = 1 for ndim 2), dense, N bytes between pairs; NULL = every voxel (today's launches and bits);
+                                    non-zero = the voxel counts.  Read on the device on every evaluation: it must outlive the call / run. */
 } trx_mi_cfg;
 size_t trx_mi_workspace_bytes(int ndim, int B, int D, int H, int W, int bins);   /* 0 = arguments rejected */
 int trx_mi_loss_grad(const float *target, const float *warped, int ndim, int B, int D, int H, int W, const trx_mi_cfg *cfg, float *loss /*[B]*/,
@@ -551,7 +567,10 @@ int trx_bspline_mi_run(const trx_volumes *vol, const trx_mi_cfg *cfg, const trx_
  * reduction - against 36 B/voxel moved by the chain warp -> trx_mi_loss_grad -> warp backward.  A pair gets ceil(N / 16384) blocks and partial rows, whatever B:
  * its loss and gradient are the same bits on every call and in every batch.  No float atomics, no host sync, no allocation.  cfg->range is read on the
  * device and must outlive the call.  Status codes before any HIP call: TRX_ERR_ARG (null pointer, bins outside 8 .. 64, alpha not finite, B > 65535,
- * >= 2^31 voxels), TRX_ERR_NDIM, TRX_ERR_WORKSPACE. */
+ * >= 2^31 voxels), TRX_ERR_NDIM, TRX_ERR_WORKSPACE.
+ * cfg->mask (trx_mi_loss_grad's semantics; dense [B][D][H][W] whatever target_stride / moving_stride say): a voxel outside the mask is not sampled at
+ * all, in either pass - it costs its mask byte - and its contribution to the partial rows is exactly zero; dtheta = what trx_affine_warp_backward
+ * returns for grad_out = the masked grad_warped.  A pair with an empty mask has loss 0 and dtheta 0, and a run leaves its theta where it was. */
 
 /* [host] bytes of workspace for this geometry (only ndim, B, D, H, W of `vol` are read) and bin count; 0 = rejected.  Pure arithmetic. */
 size_t trx_affine_mi_workspace_bytes(const trx_volumes *vol /*[host]*/, int bins);

@@ -332,7 +332,7 @@ class FlowSolver:
     """Direct dense flow-field optimisation (the flow itself is the parameter), batched."""
 
     def __init__(self, moving, target, loss=None, optimizer="sgd", lr=1e-3, init=None, capacity=1000, smooth_weight=0.0,
-                 betas=(0.9, 0.999), eps=1e-8, stop_crit=None, keep_last=False, flags=0, lncc=None, mi=None):
+                 betas=(0.9, 0.999), eps=1e-8, stop_crit=None, keep_last=False, flags=0, lncc=None, mi=None, mask=None):
         """stop_crit: the reference's early stop (ref:warpings.py:231-233), tested on the device per pair - a pair whose recorded loss
         is <= stop_crit keeps that iteration's update and ignores every later iteration; `step[b]` = number of recorded losses.
         keep_last: also keep `flow_last`, the flow of the last forward (what the reference's flow_register.flow holds).
@@ -340,9 +340,16 @@ class FlowSolver:
         (warp, window sums, gradient, smoothness, SGD / Adam) runs in trx_flow_lncc_run, 3-D only.
         mi: dict(bins=32, alpha=1.0, normalized=False, target_range=None, moving_range=None) - the data term is the Parzen joint-histogram
         mutual information (extension, mi_loss_grad) instead of `loss`: the whole loop runs in trx_flow_mi_run, 3-D only.  A range of None
-        is fitted once, here, to (target, moving)."""
+        is fitted once, here, to (target, moving).
+        mask (with mi only; see _mask_u8): a region of interest on the target lattice, one per pair - only voxels inside it enter the mutual
+        information, so the flow of a voxel outside it gets no data-term gradient; the target's range is fitted inside it; kept alive as `.mask`."""
         if mi is not None and (lncc is not None or loss is not None):
             raise ValueError("mi is a data term of its own: give it without `loss` and without `lncc`")
+        if mask is not None:
+            if mi is None:
+                raise ValueError("mask is the region of interest of the mutual-information data term: give it with `mi`")
+            mask = _mask_u8(mask, target)
+        self.mask = None
         self.lib = _lib.load()
         self.batch = _Batch(moving, target, tables=False, flags=flags)
         if self.batch.C != 1:
@@ -371,7 +378,7 @@ class FlowSolver:
         elif mi is not None:
             if nd != 3:
                 raise ValueError("the fused mutual-information flow loop is 3-D only (2-D: MILoss through the generic autograd path, or BSplineSolver)")
-            self.mi, self.mi_range = _mi_cfg(mi, self.batch.target, self.batch.moving)
+            self.mi, self.mi_range, self.mask = _mi_cfg(mi, self.batch.target, self.batch.moving, mask)
             self.ws_bytes = self.lib.trx_flow_mi_workspace_bytes(ctypes.byref(self.vol), self.mi.bins)
         else:
             self.ws_bytes = self.lib.trx_flow_workspace_bytes(ctypes.byref(self.vol))
@@ -613,13 +620,19 @@ class BSplineSolver:
     the total; `base` is not penalised.  After run(): `flow` = expand of the current ctrl (+ base), `flow_last` (keep_last or stop_crit) = the flow of the last forward.
     mi = dict(bins=32, alpha=1.0, normalized=False, target_range=None, moving_range=None): the data term is the Parzen joint-histogram mutual
     information (mi_loss_grad) instead of `loss`, and the loop runs in trx_bspline_mi_run; a range of None is fitted once, here, to (target, moving).
+    mask (with mi only; see _mask_u8): a region of interest on the target lattice, one per pair; the target's range is fitted inside it; kept alive as `.mask`.
     squarings = None: the above, launch for launch.  squarings = K (an int in 0 .. 12): diffeomorphic - base + expand(ctrl) is a stationary
     VELOCITY, the deformation is its exponential (svf_exp, K squarings) and the loop runs in trx_bspline_svf_run.  Then `velocity` is the
     expanded lattice (+ base), `flow` = svf_exp(velocity), `flow_last` the exponential of the last forward's velocity (`velocity_last`),
     inverse_flow() = svf_exp(velocity, inverse=True); `base` is a velocity.  Not with `mi`."""
 
     def __init__(self, moving, target, spacing, loss=None, optimizer="sgd", lr=1e-3, init=None, base=None, capacity=1000, stop_crit=None,
-                 keep_last=False, betas=(0.9, 0.999), eps=1e-8, bending_weight=0.0, mi=None, squarings=None):
+                 keep_last=False, betas=(0.9, 0.999), eps=1e-8, bending_weight=0.0, mi=None, squarings=None, mask=None):
+        if mask is not None:
+            if mi is None:
+                raise ValueError("mask is the region of interest of the mutual-information data term: give it with `mi`")
+            mask = _mask_u8(mask, target)
+        self.mask = None
         if squarings is not None:
             _squarings(squarings)
             if mi is not None:
@@ -673,7 +686,7 @@ class BSplineSolver:
                 raise _lib.TrxError(f"trx_bspline_svf_workspace_bytes rejected {b} x {tuple(self.batch.spatial)} with spacing {self.spacing}")
             self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
         elif mi is not None:
-            self.mi, self.mi_range = _mi_cfg(mi, self.batch.target, self.batch.moving)
+            self.mi, self.mi_range, self.mask = _mi_cfg(mi, self.batch.target, self.batch.moving, mask)
             self.ws_bytes = self.lib.trx_bspline_mi_workspace_bytes(nd, b, *_dhw(self.batch.spatial), *self.sp3, self.mi.bins)
             if self.ws_bytes == 0:
                 raise _lib.TrxError(f"trx_bspline_mi_workspace_bytes rejected {b} x {tuple(self.batch.spatial)} with spacing {self.spacing}")
@@ -1357,10 +1370,23 @@ def _mi_bins(bins):
     return bins
 
 
-def mi_range(target, moving, target_range=None, moving_range=None):
+def _mask_u8(mask, like):
+    """A region-of-interest mask on the target lattice of `like` [B,1,*spatial]: bool / uint8 / any numeric tensor of shape [B,1,*spatial] or
+    [B,*spatial], non-zero = the voxel counts -> contiguous uint8 [B,1,*spatial] of 0 / 1 on like's device (what trx_mi_cfg.mask points to: the
+    caller keeps it alive).  ValueError on a shape mismatch, before anything touches a device."""
+    if not isinstance(mask, torch.Tensor):
+        raise ValueError(f"mask must be a tensor of shape {tuple(like.shape)}, got {type(mask).__name__}")
+    want = (like.shape[0], 1) + tuple(like.shape[2:])
+    if tuple(mask.shape) not in (want, (want[0],) + want[2:]):
+        raise ValueError(f"mask {tuple(mask.shape)} does not match the target lattice: expected {want} or {(want[0],) + want[2:]}")
+    return (mask.detach().reshape(want) != 0).to(device=like.device, dtype=torch.uint8).contiguous()
+
+
+def mi_range(target, moving, target_range=None, moving_range=None, mask=None):
     """[B,4] fp32 on the tensors' device: (lo_t, hi_t, lo_w, hi_w) per pair.  None: the target's min / max, the moving (or warped) image's min /
     max widened to contain 0 - the value of a zero-padded warp outside the field of view.  A (lo, hi) pair of numbers serves every pair of the
-    batch.  No host sync."""
+    batch.  mask (see _mask_u8): the target's min / max are taken over the voxels that count - a pair whose mask is empty falls back to its whole
+    target; the moving side does not change.  No host sync."""
     B = target.shape[0]
     cols = []
     for x, r, widen in ((target, target_range, False), (moving, moving_range, True)):
@@ -1369,26 +1395,36 @@ def mi_range(target, moving, target_range=None, moving_range=None):
             lo, hi = flat.amin(1), flat.amax(1)
             if widen:
                 lo, hi = lo.clamp(max=0.0), hi.clamp(min=0.0)
+            elif mask is not None:
+                m = _mask_u8(mask, target).reshape(B, -1) != 0
+                inf = torch.full_like(flat, float("inf"))
+                some = m.any(1)
+                lo, hi = torch.where(some, torch.where(m, flat, inf).amin(1), lo), torch.where(some, torch.where(m, flat, -inf).amax(1), hi)
         else:
             lo, hi = (torch.full((B,), float(v), dtype=torch.float32, device=target.device) for v in r)
         cols += [lo, hi]
     return torch.stack(cols, dim=1).contiguous()
 
 
-def _mi_cfg(mi, target, moving):
-    """dict -> (trx_mi_cfg, the range tensor it points to: the caller keeps it alive)."""
+def _mi_cfg(mi, target, moving, mask=None):
+    """dict -> (trx_mi_cfg, the range tensor it points to, the uint8 mask it points to or None: the caller keeps both alive)."""
     unknown = set(mi) - {"bins", "alpha", "normalized", "target_range", "moving_range"}
     if unknown:
         raise ValueError(f"unknown mutual-information settings {sorted(unknown)}")
-    rng = mi_range(target, moving, mi.get("target_range"), mi.get("moving_range"))
+    m8 = None if mask is None else _mask_u8(mask, target)
+    rng = mi_range(target, moving, mi.get("target_range"), mi.get("moving_range"), m8)
     cfg = _lib.MICfg()
     cfg.bins, cfg.alpha, cfg.normalized, cfg.range = _mi_bins(mi.get("bins", 32)), float(mi.get("alpha", 1.0)), int(bool(mi.get("normalized", False))), rng.data_ptr()
-    return cfg, rng
+    cfg.mask = None if m8 is None else m8.data_ptr()
+    return cfg, rng, m8
 
 
-def mi_loss_grad(target, warped, rng, bins=32, alpha=1.0, normalized=False, need_grad=True):
+def mi_loss_grad(target, warped, rng, bins=32, alpha=1.0, normalized=False, need_grad=True, mask=None):
     """Parzen joint-histogram mutual information (extension, include/trx.h: trx_mi_loss_grad): target / warped [B,1,*spatial] fp32 on the GPU,
-    rng [B,4] (mi_range).  Returns (loss [B], d loss / d warped (same shape as warped) or None)."""
+    rng [B,4] (mi_range), mask (see _mask_u8) or None = every voxel.  Returns (loss [B], d loss / d warped (same shape as warped, zero outside
+    the mask) or None)."""
+    if mask is not None:
+        mask = _mask_u8(mask, target)
     lib = _lib.load()
     if not (target.is_cuda and warped.is_cuda):
         raise _lib.TrxError("mi_loss_grad needs CUDA (HIP) tensors: there is no CPU fallback")
@@ -1403,6 +1439,7 @@ def mi_loss_grad(target, warped, rng, bins=32, alpha=1.0, normalized=False, need
     D, H, W = (1, *y.shape[2:]) if nd == 2 else y.shape[2:]
     cfg = _lib.MICfg()
     cfg.bins, cfg.alpha, cfg.normalized, cfg.range = _mi_bins(bins), float(alpha), int(bool(normalized)), rng.data_ptr()
+    cfg.mask = None if mask is None else mask.data_ptr()
     loss = torch.empty(B, device=y.device)
     grad = torch.empty_like(w) if need_grad else None
     ws_bytes = lib.trx_mi_workspace_bytes(nd, B, D, H, W, cfg.bins)
@@ -1426,10 +1463,13 @@ def _mi_pair_batch(moving, target):
     return batch
 
 
-def affine_mi_loss_grad(moving, target, theta, rng, bins=32, alpha=1.0, normalized=False, need_grad=True):
+def affine_mi_loss_grad(moving, target, theta, rng, bins=32, alpha=1.0, normalized=False, need_grad=True, mask=None):
     """Mutual information of (target, affine warp of moving by theta) and its gradient with respect to theta without a warped volume (extension,
-    include/trx.h: trx_affine_mi_loss_grad): moving / target [B,1,*spatial] fp32 on the GPU, theta [B,nd,nd+1], rng [B,4] (mi_range).
-    Returns (loss [B], dtheta [B,nd,nd+1] or None) - what affine_warp -> mi_loss_grad -> affine_warp_backward give, in two passes over the pair."""
+    include/trx.h: trx_affine_mi_loss_grad): moving / target [B,1,*spatial] fp32 on the GPU, theta [B,nd,nd+1], rng [B,4] (mi_range), mask (see
+    _mask_u8) or None = every voxel.  Returns (loss [B], dtheta [B,nd,nd+1] or None) - what affine_warp -> mi_loss_grad -> affine_warp_backward
+    give, in two passes over the pair."""
+    if mask is not None:
+        mask = _mask_u8(mask, target)
     lib = _lib.load()
     batch = _mi_pair_batch(moving, target)
     B, nd = batch.B, batch.nd
@@ -1439,6 +1479,9 @@ def affine_mi_loss_grad(moving, target, theta, rng, bins=32, alpha=1.0, normaliz
     th = pad_theta(theta.detach().to(batch.device).reshape(B, -1), nd)
     cfg = _lib.MICfg()
     cfg.bins, cfg.alpha, cfg.normalized, cfg.range = _mi_bins(bins), float(alpha), int(bool(normalized)), rng.data_ptr()
+    if mask is not None:
+        mask = mask.to(batch.device)
+        cfg.mask = mask.data_ptr()
     vol = batch.vol()
     ws_bytes = lib.trx_affine_mi_workspace_bytes(ctypes.byref(vol), cfg.bins)
     if ws_bytes == 0:
@@ -1461,9 +1504,13 @@ class AffineMISolver:
     moving, target: [B,1,*spatial] fp32 on the GPU.  mode, init, optimizer, lr, capacity, betas, eps as for AffineSolver; the state tensors
     (param, theta, losses, best_theta, best_loss, best_idx, step, grad) have AffineSolver's meaning.
     mi: dict(bins=32, alpha=1.0, normalized=False, target_range=None, moving_range=None); a range of None is fitted once, here, to
-    (target, moving), the moving side widened to contain 0."""
+    (target, moving), the moving side widened to contain 0.
+    mask: a region of interest on the target lattice (see _mask_u8), one per pair, or None = every voxel: only voxels inside it enter the
+    histogram and the gradient, the target's range is fitted inside it, and the solver keeps the uint8 tensor (`.mask`) alive."""
 
-    def __init__(self, moving, target, mode="affine", mi=None, optimizer="sgd", lr=1e-5, init=None, capacity=1000, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, moving, target, mode="affine", mi=None, optimizer="sgd", lr=1e-5, init=None, capacity=1000, betas=(0.9, 0.999), eps=1e-8, mask=None):
+        if mask is not None:
+            mask = _mask_u8(mask, target)
         self.lib = _lib.load()
         self.batch = _mi_pair_batch(moving, target)
         b, nd, dev = self.batch.B, self.batch.nd, self.batch.device
@@ -1485,7 +1532,7 @@ class AffineMISolver:
             self.theta[:, :nt] = pose_to_theta(pose.double()).float()      # the update kernel's fp32 -> fp64 -> fp32 chain
         else:
             raise ValueError(f"mode must be 'affine' or 'rigid', got {mode!r}")
-        self.mi, self.mi_range = _mi_cfg({} if mi is None else mi, self.batch.target, self.batch.moving)
+        self.mi, self.mi_range, self.mask = _mi_cfg({} if mi is None else mi, self.batch.target, self.batch.moving, mask)
         self.capacity = int(capacity)
         self.adam_m = torch.zeros(b, PSTRIDE, device=dev)
         self.adam_v = torch.zeros(b, PSTRIDE, device=dev)

@@ -72,7 +72,8 @@ class BSplineState(ctypes.Structure):
 
 
 class MICfg(ctypes.Structure):
-    _fields_ = [("bins", ctypes.c_int), ("alpha", ctypes.c_float), ("normalized", ctypes.c_int), ("range", ctypes.c_void_p)]
+    _fields_ = [("bins", ctypes.c_int), ("alpha", ctypes.c_float), ("normalized", ctypes.c_int), ("range", ctypes.c_void_p),
+                ("mask", ctypes.c_void_p)]
 
 
 # name -> (restype, argtypes); must list every symbol include/trx.h declares (tests check this)

@@ -15,6 +15,10 @@
 // A pair gets ceil(N / kMiChunk) blocks and partial rows: a function of (D, H, W) alone.  Integer histogram sums are associative, every float sum
 // has a fixed order: a pair's loss and gradient are the same bits on every call and whatever batch surrounds it.  No float atomics.
 // The loop's update kernel also zeroes the pair's counts for the next iteration, so an iteration is four launches: pass 1, table, pass 2, update.
+// Region of interest (cfg->mask): both passes have a second instance that reads the voxel's mask byte first (9 B/voxel inside the
+// mask, 1 outside) and skips a voxel outside it before any coordinate is formed - nothing is sampled, nothing enters the LDS tables or the thread's
+// sums.  A block whose chunk lies wholly outside the mask still clears and flushes (adding nothing) and still writes its partial row (zeros): the
+// reduction reads a fixed number of rows.  The table kernel takes N_m from the counts; the update kernel zeroes all K x K cells, masked or not.
 #include "affine_finalize.h"   // reduce_partials, fin_load / fin_update (the epilogue of the affine step), launch_bwd_finalize (affine_host.h)
 #include "mi_dev.h"
 
@@ -75,9 +79,9 @@ __device__ __forceinline__ AmiSample<ND> ami_sample(const trx_volumes &vol, cons
 }
 
 // pass 1: warp and histogram
-template <int ND>
+template <int ND, bool MASKED>
 __global__ __launch_bounds__(TRX_BLOCK) void ami_hist_kernel(trx_volumes vol, const float *__restrict__ theta, unsigned N, int K, int T, const float *__restrict__ range,
-                                                               unsigned long long *__restrict__ counts)
+                                                               unsigned long long *__restrict__ counts, const unsigned char *__restrict__ mask)
 {
     extern __shared__ unsigned long long ami_lds[];           // [T][K][K]
     const int b = blockIdx.y, tid = threadIdx.x, KK = K * K;
@@ -86,9 +90,11 @@ __global__ __launch_bounds__(TRX_BLOCK) void ami_hist_kernel(trx_volumes vol, co
     const float *__restrict__ th = theta + (size_t)b * TRX_PSTRIDE;
     const float *__restrict__ mov = vol.moving + (size_t)b * vol.moving_stride;
     const float *__restrict__ tgt = vol.target + (size_t)b * vol.target_stride;
+    const unsigned char *mk = MASKED ? mask + (size_t)b * N : nullptr;      // dense, whatever target_stride says
     unsigned long long *mine = ami_lds + ((tid >> 6) % T) * KK;
     const unsigned first = blockIdx.x * (unsigned)kMiChunk, last = min(N, first + (unsigned)kMiChunk);
     for (VoxelWalk vw(first + tid, TRX_BLOCK, vol.H, vol.W); vw.i < last; vw.next(vol.H, vol.W)) {
+        if (!mi_counts<MASKED>(mk, vw.i)) continue;      // before any coordinate: a voxel outside the mask costs its mask byte and nothing else
         const float xn = base_coord(vol.xn, vw.x, vol.W), yn = base_coord(vol.yn, vw.y, vol.H), zn = ND == 3 ? base_coord(vol.zn, vw.z, vol.D) : 0.f;
         const AmiSample<ND> s = ami_sample<ND>(vol, th, mov, vw.x, vw.y, vw.z, xn, yn, zn);
         mi_accumulate(mine, mi_voxel(__builtin_nontemporal_load(tgt + vw.i), s.v, m, K), K);
@@ -122,9 +128,9 @@ __device__ __forceinline__ void ami_block_sum_store(const float (&vals)[NV], flo
 }
 
 // pass 2: gradient rows
-template <int ND>
+template <int ND, bool MASKED>
 __global__ __launch_bounds__(TRX_BLOCK) void ami_grad_kernel(trx_volumes vol, const float *__restrict__ theta, unsigned N, int K, const float *__restrict__ range,
-                                                               const float *__restrict__ G, float *__restrict__ partials)
+                                                               const float *__restrict__ G, float *__restrict__ partials, const unsigned char *__restrict__ mask)
 {
     constexpr int NT = ND * (ND + 1);
     extern __shared__ float ami_g[];                // [K][K]
@@ -138,8 +144,10 @@ __global__ __launch_bounds__(TRX_BLOCK) void ami_grad_kernel(trx_volumes vol, co
     float vals[NT];
 #pragma unroll
     for (int k = 0; k < NT; k++) vals[k] = 0.f;
+    const unsigned char *mk = MASKED ? mask + (size_t)b * N : nullptr;
     const unsigned first = blockIdx.x * (unsigned)kMiChunk, last = min(N, first + (unsigned)kMiChunk);
     for (VoxelWalk vw(first + tid, TRX_BLOCK, vol.H, vol.W); vw.i < last; vw.next(vol.H, vol.W)) {
+        if (!mi_counts<MASKED>(mk, vw.i)) continue;      // grad_warped is 0 there: nothing is sampled, the row below is still written (zeros if the chunk is empty)
         const float xn = base_coord(vol.xn, vw.x, vol.W), yn = base_coord(vol.yn, vw.y, vol.H), zn = ND == 3 ? base_coord(vol.zn, vw.z, vol.D) : 0.f;
         const AmiSample<ND> s = ami_sample<ND>(vol, th, mov, vw.x, vw.y, vw.z, xn, yn, zn);
         const float gw = mi_voxel_grad(ami_g, mi_voxel(__builtin_nontemporal_load(tgt + vw.i), s.v, m, K), K);
@@ -194,14 +202,20 @@ static int ami_evaluate(const trx_volumes *vol, const trx_mi_cfg *cfg, const Ami
     unsigned long long *counts = (unsigned long long *)workspace;
     float *G = (float *)((char *)workspace + g.o_g), *partials = (float *)((char *)workspace + g.o_part);
     const dim3 grid(g.nchunk, (unsigned)vol->B), block(TRX_BLOCK);
+    const unsigned char *mask = cfg->mask;               // read here on every evaluation, so on every iteration of the loop
+    const size_t lds = (size_t)T * K * K * sizeof(unsigned long long);
     with_ndim(vol->ndim, [&](auto nd) {
-        hipLaunchKernelGGL((ami_hist_kernel<decltype(nd)::value>), grid, block, (size_t)T * K * K * sizeof(unsigned long long), s, *vol, theta, g.N, K, T, cfg->range, counts);
+        constexpr int ND = decltype(nd)::value;
+        if (mask) hipLaunchKernelGGL((ami_hist_kernel<ND, true>), grid, block, lds, s, *vol, theta, g.N, K, T, cfg->range, counts, mask);
+        else hipLaunchKernelGGL((ami_hist_kernel<ND, false>), grid, block, lds, s, *vol, theta, g.N, K, T, cfg->range, counts, mask);
     });
     TRX_CHECK_LAUNCH();
     const int rc = launch_mi_table(counts, g.N, vol->B, cfg, loss, need_grad ? G : (float *)nullptr, s);
     if (rc != TRX_OK || !need_grad) return rc;
     with_ndim(vol->ndim, [&](auto nd) {
-        hipLaunchKernelGGL((ami_grad_kernel<decltype(nd)::value>), grid, block, (size_t)K * K * sizeof(float), s, *vol, theta, g.N, K, cfg->range, (const float *)G, partials);
+        constexpr int ND = decltype(nd)::value;
+        if (mask) hipLaunchKernelGGL((ami_grad_kernel<ND, true>), grid, block, (size_t)K * K * sizeof(float), s, *vol, theta, g.N, K, cfg->range, (const float *)G, partials, mask);
+        else hipLaunchKernelGGL((ami_grad_kernel<ND, false>), grid, block, (size_t)K * K * sizeof(float), s, *vol, theta, g.N, K, cfg->range, (const float *)G, partials, mask);
     });
     TRX_CHECK_LAUNCH();
     return TRX_OK;

@@ -19,6 +19,9 @@
 //                    table G = d loss / d P scaled by s_w / N, rounded to fp32, into the workspace.
 //   mi_grad_kernel   reads t and w again, writes grad (12 B/voxel): a block copies the pair's G to LDS (16 KB at K = 64), a voxel recomputes
 //                    (a, c, r) and gathers four entries.
+// Region of interest (cfg->mask, one byte per voxel of the target lattice, non-zero = the voxel counts): each of the three kernels has a second
+// instance, chosen by the host from cfg->mask != NULL; the unmasked instances are the code they were.  The masked passes read 9 and 9 B/voxel: the
+// histogram adds only voxels inside the mask, the gradient writes 0 outside it, and the table kernel takes N_m from the counts it is given.
 // Fixed point: each converted weight is off by at most 2^-32 (and exact above 2^-8), the remainder absorbs the fp32 rounding of the four weights
 // (their sum is 1 to 2e-7) plus at most 3 * 2^-32, so beyond fp32 rounding of the weights themselves
 //   |P[a][k] - exact| <= 1.5 * 2^-31 * n[a][k] / N   (n: voxels that touch the cell)   and   sum over cells <= 3 * 2^-31.
@@ -28,19 +31,25 @@
 
 namespace trx {
 
+template <bool MASKED>
 __global__ __launch_bounds__(TRX_BLOCK) void mi_hist_kernel(const float *__restrict__ target, const float *__restrict__ warped, unsigned N, int K, int T,
-                                                              const float *__restrict__ range, unsigned long long *__restrict__ counts)
+                                                              const float *__restrict__ range, unsigned long long *__restrict__ counts,
+                                                              const unsigned char *__restrict__ mask)
 {
     extern __shared__ unsigned long long mi_lds[];           // [T][K][K]
     const int b = blockIdx.y, tid = threadIdx.x, KK = K * K;
     mi_lds_clear(mi_lds, T * KK);
     const MiScale m = mi_scale(range, b, K);
     const float *t = target + (size_t)b * N, *w = warped + (size_t)b * N;
+    const unsigned char *mk = MASKED ? mask + (size_t)b * N : nullptr;
     unsigned long long *mine = mi_lds + ((tid >> 6) % T) * KK;
     const unsigned first = blockIdx.x * (unsigned)kMiChunk, last = min(N, first + (unsigned)kMiChunk);
 #pragma unroll 4
-    for (unsigned i = first + tid; i < last; i += TRX_BLOCK)
-        mi_accumulate(mine, mi_voxel(__builtin_nontemporal_load(t + i), __builtin_nontemporal_load(w + i), m, K), K);
+    for (unsigned i = first + tid; i < last; i += TRX_BLOCK) {
+        const bool on = mi_counts<MASKED>(mk, i);      // the three streams are loaded side by side; a voxel outside the mask adds nothing
+        const MiVoxel v = mi_voxel(__builtin_nontemporal_load(t + i), __builtin_nontemporal_load(w + i), m, K);
+        if (on) mi_accumulate(mine, v, K);
+    }
     __syncthreads();
     mi_flush(mi_lds, T, KK, counts + (size_t)b * KK);
 }
@@ -60,12 +69,32 @@ __device__ __forceinline__ double mi_block_sum(double v, double *red)
 
 __device__ __forceinline__ double mi_plogp(double p) { return p > 0.0 ? p * log(p) : 0.0; }
 
+// MASKED: N (the host's voxel count) is replaced by N_m = (sum of the pair's counts) / TRX_MI_ONE - every voxel inside the mask added exactly
+// TRX_MI_ONE, so the integer sum of the K^2 cells gives N_m exactly and in any order, without a counter of its own and without a host sync.  From
+// there on the arithmetic is the unmasked instance's, operation for operation: an all-ones mask gives its bits.  N_m = 0: loss 0, G 0.
+template <bool MASKED>
 __global__ __launch_bounds__(TRX_BLOCK) void mi_table_kernel(const unsigned long long *__restrict__ counts, unsigned N, int K, float alpha, int normalized,
                                                                const float *__restrict__ range, float *__restrict__ loss, float *__restrict__ G)
 {
     __shared__ double s_p[64 * 64];
     __shared__ double s_pt[64], s_pw[64], s_red[TRX_BLOCK];
     const int b = blockIdx.x, tid = threadIdx.x, KK = K * K;
+    if constexpr (MASKED) {
+        __shared__ unsigned long long s_units;
+        if (tid == 0) s_units = 0ull;
+        __syncthreads();
+        unsigned long long mine = 0ull;
+        for (int i = tid; i < KK; i += TRX_BLOCK) mine += counts[(size_t)b * KK + i];
+        if (mine) atomicAdd(&s_units, mine);
+        __syncthreads();
+        N = (unsigned)(s_units / TRX_MI_ONE);
+        if (N == 0u) {                                   // an empty mask: nothing to normalise by (the whole block takes this branch)
+            if (tid == 0 && loss) loss[b] = 0.f;
+            if (G)
+                for (int i = tid; i < KK; i += TRX_BLOCK) G[(size_t)b * KK + i] = 0.f;
+            return;
+        }
+    }
     const double inv = 1.0 / ((double)N * (double)TRX_MI_ONE);
     for (int i = tid; i < KK; i += TRX_BLOCK) s_p[i] = (double)counts[(size_t)b * KK + i] * inv;
     __syncthreads();
@@ -103,8 +132,10 @@ __global__ __launch_bounds__(TRX_BLOCK) void mi_table_kernel(const unsigned long
     }
 }
 
+template <bool MASKED>
 __global__ __launch_bounds__(TRX_BLOCK) void mi_grad_kernel(const float *__restrict__ target, const float *__restrict__ warped, unsigned N, int K,
-                                                              const float *__restrict__ range, const float *__restrict__ G, float *__restrict__ grad)
+                                                              const float *__restrict__ range, const float *__restrict__ G, float *__restrict__ grad,
+                                                              const unsigned char *__restrict__ mask)
 {
     extern __shared__ float mi_g[];                // [K][K]
     const int b = blockIdx.y, tid = threadIdx.x, KK = K * K;
@@ -113,10 +144,14 @@ __global__ __launch_bounds__(TRX_BLOCK) void mi_grad_kernel(const float *__restr
     const MiScale m = mi_scale(range, b, K);
     const float *t = target + (size_t)b * N, *w = warped + (size_t)b * N;
     float *out = grad + (size_t)b * N;
+    const unsigned char *mk = MASKED ? mask + (size_t)b * N : nullptr;
     const unsigned first = blockIdx.x * (unsigned)kMiChunk, last = min(N, first + (unsigned)kMiChunk);
 #pragma unroll 4
-    for (unsigned i = first + tid; i < last; i += TRX_BLOCK)
-        out[i] = mi_voxel_grad(mi_g, mi_voxel(__builtin_nontemporal_load(t + i), __builtin_nontemporal_load(w + i), m, K), K);
+    for (unsigned i = first + tid; i < last; i += TRX_BLOCK) {
+        const bool on = mi_counts<MASKED>(mk, i);
+        const float g = mi_voxel_grad(mi_g, mi_voxel(__builtin_nontemporal_load(t + i), __builtin_nontemporal_load(w + i), m, K), K);
+        out[i] = on ? g : 0.f;                           // the array is fully written: exactly 0 outside the mask
+    }
 }
 
 struct MiGeom {
@@ -138,7 +173,10 @@ static int mi_geom(int ndim, int B, int D, int H, int W, int bins, MiGeom *g)
 
 int launch_mi_table(const unsigned long long *counts, unsigned N, int B, const trx_mi_cfg *cfg, float *loss, float *G, hipStream_t s)
 {
-    hipLaunchKernelGGL(mi_table_kernel, dim3((unsigned)B), dim3(TRX_BLOCK), 0, s, counts, N, cfg->bins, cfg->alpha, cfg->normalized ? 1 : 0, cfg->range, loss, G);
+    if (cfg->mask)
+        hipLaunchKernelGGL(mi_table_kernel<true>, dim3((unsigned)B), dim3(TRX_BLOCK), 0, s, counts, N, cfg->bins, cfg->alpha, cfg->normalized ? 1 : 0, cfg->range, loss, G);
+    else
+        hipLaunchKernelGGL(mi_table_kernel<false>, dim3((unsigned)B), dim3(TRX_BLOCK), 0, s, counts, N, cfg->bins, cfg->alpha, cfg->normalized ? 1 : 0, cfg->range, loss, G);
     TRX_CHECK_LAUNCH();
     return TRX_OK;
 }
@@ -166,8 +204,12 @@ static int mi_histogram_impl(const float *target, const float *warped, int ndim,
     const int K = cfg->bins, T = mi_tables(K);
     unsigned long long *counts = (unsigned long long *)workspace;
     if (hipMemsetAsync(counts, 0, (size_t)B * K * K * sizeof(unsigned long long), s) != hipSuccess) return TRX_ERR_HIP;
-    hipLaunchKernelGGL(mi_hist_kernel, dim3(g->nchunk, (unsigned)B), dim3(TRX_BLOCK), (size_t)T * K * K * sizeof(unsigned long long), s, target, warped, g->N, K, T,
-                       cfg->range, counts);
+    const dim3 grid(g->nchunk, (unsigned)B), block(TRX_BLOCK);
+    const size_t lds = (size_t)T * K * K * sizeof(unsigned long long);
+    if (cfg->mask)
+        hipLaunchKernelGGL(mi_hist_kernel<true>, grid, block, lds, s, target, warped, g->N, K, T, cfg->range, counts, cfg->mask);
+    else
+        hipLaunchKernelGGL(mi_hist_kernel<false>, grid, block, lds, s, target, warped, g->N, K, T, cfg->range, counts, (const unsigned char *)nullptr);
     TRX_CHECK_LAUNCH();
     return TRX_OK;
 }
@@ -185,8 +227,12 @@ extern "C" int trx_mi_loss_grad(const float *target, const float *warped, int nd
     const int rc_table = launch_mi_table((const unsigned long long *)workspace, g.N, B, cfg, loss, grad_warped ? G : (float *)nullptr, s);
     if (rc_table != TRX_OK) return rc_table;
     if (!grad_warped) return TRX_OK;
-    hipLaunchKernelGGL(mi_grad_kernel, dim3(g.nchunk, (unsigned)B), dim3(TRX_BLOCK), (size_t)K * K * sizeof(float), s, target, warped, g.N, K, cfg->range,
-                       (const float *)G, grad_warped);
+    const dim3 grid(g.nchunk, (unsigned)B), block(TRX_BLOCK);
+    if (cfg->mask)
+        hipLaunchKernelGGL(mi_grad_kernel<true>, grid, block, (size_t)K * K * sizeof(float), s, target, warped, g.N, K, cfg->range, (const float *)G, grad_warped, cfg->mask);
+    else
+        hipLaunchKernelGGL(mi_grad_kernel<false>, grid, block, (size_t)K * K * sizeof(float), s, target, warped, g.N, K, cfg->range, (const float *)G, grad_warped,
+                           (const unsigned char *)nullptr);
     TRX_CHECK_LAUNCH();
     return TRX_OK;
 }

@@ -106,7 +106,17 @@ __device__ __forceinline__ float mi_voxel_grad(const float *G, const MiVoxel &v,
     return v.inside ? acc : 0.f;
 }
 
-// mi.hip: mi_table_kernel, one block per pair - counts [B][K][K] -> loss [B] (nullable) and G [B][K][K] = d loss / d P scaled by s_w / N (nullable)
+// The region-of-interest mask (trx_mi_cfg.mask: one byte per voxel of the target lattice, non-zero = the voxel counts), read like t and w:
+// thread-strided within the chunk, non-temporal.  A pass is instantiated with and without it; the unmasked instance has no mask code at all.
+template <bool MASKED>
+__device__ __forceinline__ bool mi_counts(const unsigned char *__restrict__ mask, unsigned i)
+{
+    if constexpr (MASKED) return __builtin_nontemporal_load(mask + i) != 0;
+    else return true;
+}
+
+// mi.hip: mi_table_kernel, one block per pair - counts [B][K][K] -> loss [B] (nullable) and G [B][K][K] = d loss / d P scaled by s_w / N (nullable).
+// With cfg->mask set N is ignored: the kernel takes N_m = (sum of the pair's counts) / TRX_MI_ONE, an exact integer, from the table itself.
 TRX_HIDDEN int launch_mi_table(const unsigned long long *counts, unsigned N, int B, const trx_mi_cfg *cfg, float *loss, float *G, hipStream_t s);
 
 }  // namespace trx

@@ -78,6 +78,21 @@ def pyramid(x, levels, align_corners=False):
     return out[::-1]
 
 
+def pyramid_masks(mask, levels, align_corners=False):
+    """[coarsest, ..., finest] uint8 masks of a region-of-interest mask [B, 1, *sp] (GPU, non-zero = the voxel counts): the mask as 0.0 / 1.0
+    floats through the pyramid() call that makes the target's levels (same blur, same positions, same align_corners), a voxel of a level counting
+    where the result is >= 0.5.  ValueError if some pair's mask is empty at some level (level 1 = the coarsest); one host sync per level."""
+    out = []
+    for k, m in enumerate(pyramid((mask != 0).float(), levels, align_corners)):
+        m8 = (m >= 0.5).to(torch.uint8).contiguous()
+        empty = (m8.flatten(1).amax(1) == 0).nonzero().flatten().tolist()
+        if empty:
+            raise ValueError(f"mask: pair {empty[0]} has no voxel left at level {k + 1} of {levels} (shape {tuple(m.shape[2:])}); "
+                             f"a level's mask is the pyramid of the mask thresholded at 0.5 - use fewer levels or a larger region")
+        out.append(m8)
+    return out
+
+
 def upsample_flow(flow, size):
     """A flow [B, nd, *sp] (voxel units, channel i along spatial dim i, SpatialTransformer's align_corners=True convention) moved to
     the grid `size`: linear interpolation with align_corners=True, channel i scaled by (S_i - 1) / (s_i - 1) (1 where the axis keeps

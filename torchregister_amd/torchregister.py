@@ -9,9 +9,9 @@ U-Net-generated flow, 'direct' = the flow field itself is the parameter), levels
 import torch
 from torch import cat
 
-from ._engine import _bending_weight, _squarings
-from .pyramid import pyramid, pyramid_shapes, upsample_flow
-from .warpings import affine_register, device_loop_settings, flow_register, get_affine_warp, rigid_register
+from ._engine import _bending_weight, _mask_u8, _squarings
+from .pyramid import pyramid, pyramid_masks, pyramid_shapes, upsample_flow
+from .warpings import MASK_SUPPORT, affine_register, device_loop_settings, flow_register, get_affine_warp, rigid_register
 
 
 def _per_level(value, levels, name):
@@ -116,6 +116,7 @@ class Register():
         self.losses = None
         self.final_theta = None
         self.best_idx = None
+        self.final_pose = None      # mode='rigid' on the device paths: the pose [B,6] (3-D) / [B,3] (2-D) behind final_theta
         self.level_losses = None
         self.level_shapes = None
 
@@ -130,7 +131,19 @@ class Register():
             kw.update(weights=self.weight)
         return kw
 
-    def optim(self, moving, target, lr=1E-5, max_epochs=1000, n=32, per=0.1):
+    def _check_mask(self, mask, target):
+        '''mask=... of optim: ValueError unless the loop is one of the device-side mutual-information loops; the uint8 mask [B,1,*spatial].'''
+        if self.mode == 'flow':
+            from .utils import MILoss
+            alone = self.criterion is not None and self.weight is not None and len(self.criterion) == 1 and isinstance(self.criterion[0], MILoss)
+            ok = alone and not self.diffeomorphic and (self.flow_model == 'bspline' or (self.flow_model == 'direct' and target.dim() == 5))
+        else:
+            ok = self.device_loop
+        if not ok:
+            raise ValueError(MASK_SUPPORT)
+        return _mask_u8(mask, target)
+
+    def optim(self, moving, target, lr=1E-5, max_epochs=1000, n=32, per=0.1, *, mask=None):
         '''
         Optimisation loop: moving, target [1,1,x,y(,z)] float32 GPU tensors (a leading batch > 1 of
         independent pairs is an extension).  Sets self.theta (best theta [B,nd,nd+1], or the flow
@@ -138,12 +151,20 @@ class Register():
         With levels > 1, lr and max_epochs may each be one value for every level or a sequence of `levels` values, coarse to fine.
         A level with max_epochs 0 runs no iteration and hands its starting parameters to the next level unchanged (its entry in
         .level_losses is empty).
+        mask : (keyword-only extension) a region of interest on the TARGET lattice, one per pair: bool / uint8 / numeric, [B,1,*spatial] or
+            [B,*spatial], non-zero = the voxel counts.  Only those voxels enter the mutual information (histogram, normalisation, gradient) and
+            the fitted target range - a couch, a coil or a lesion the moving image lacks is left out.  Supported where the loop is one of the
+            device-side mutual-information loops: mode 'rigid' / 'affine' with device_loop=True, or mode 'flow' with flow_model 'direct' (3-D) or
+            'bspline' and MILoss alone; ValueError anywhere else, before any device work.  With levels > 1 a level's mask is the float mask sent
+            through the pyramid call of the target and thresholded at >= 0.5; a pair whose mask is empty at some level raises ValueError.
         '''
+        if mask is not None:
+            mask = self._check_mask(mask, target)
         if self.levels > 1:
-            return self._optim_levels(moving, target, lr, max_epochs, n, per)
+            return self._optim_levels(moving, target, lr, max_epochs, n, per, mask)
         if self.mode == 'flow':
             flowreg = flow_register(target.shape[2:], **self._flow_kw(n, lr, max_epochs)).to(moving.device)
-            flowreg.optimize(moving, target, self.device, self.debug)
+            flowreg.optimize(moving, target, self.device, self.debug, mask=mask)
             self.theta = flowreg.flow
             self.warp = flowreg.deform
             self.losses = flowreg.losses
@@ -160,13 +181,16 @@ class Register():
             kw.update(criterions=self.criterion, weights=self.weight)
         elif self.weight is not None:                                         # ref:torchregister.py:88-90,100-102
             kw.update(weights=self.weight)
+        if mask is not None:
+            kw.update(mask=mask)
         _, theta = fn(moving, target, **kw)
         self.theta = theta[-1]                                                # best theta (Q8)
         self.final_theta = theta[0]
         self.losses = info.get('losses')
         self.best_idx = info.get('best_idx')
+        self.final_pose = info.get('final_pose')
 
-    def _optim_levels(self, moving, target, lr, max_epochs, n, per):
+    def _optim_levels(self, moving, target, lr, max_epochs, n, per, mask=None):
         '''Coarse-to-fine: the single-level machinery (flow_register / _affine_family) on each level of pyramid(moving) and
         pyramid(target), coarsest first; each level starts from the previous level's FINAL parameters (rigid: the pose, drawn by
         torch.rand for the coarsest level as a single-level run draws it; affine: theta; flow: upsample_flow of the flow).  Optimiser
@@ -178,6 +202,7 @@ class Register():
             raise ValueError(f"moving {tuple(moving.shape)} and target {tuple(target.shape)} differ in spatial size")
         flow = self.mode == 'flow'
         movs, tgts = pyramid(moving, L, align_corners=flow), pyramid(target, L, align_corners=flow)
+        masks = [None] * L if mask is None else pyramid_masks(mask, L, align_corners=flow)      # raises for a pair whose mask empties at some level
         init = None if flow else self.init
         self.level_losses, self.level_shapes = [], shapes
         for k in range(L):
@@ -188,7 +213,7 @@ class Register():
                     reg.base_flow = up       # the level's lattice starts from zero and adds to what the coarser levels found
                 else:
                     reg.init_flow = up
-                reg.optimize(movs[k], tgts[k], self.device, False)
+                reg.optimize(movs[k], tgts[k], self.device, False, mask=masks[k])
                 init = reg.final_velocity if self.diffeomorphic else reg.final_flow      # diffeomorphic: the levels add up as velocities
                 self.velocity, self.inverse_flow, self._inverse_warp = reg.velocity, reg.inverse_flow, reg.inverse
                 self.theta, self.warp, self.final_theta = reg.flow, reg.deform, reg.final_flow
@@ -203,10 +228,13 @@ class Register():
                     kw.update(criterions=self.criterion, weights=self.weight)
                 elif self.weight is not None:
                     kw.update(weights=self.weight)
+                if masks[k] is not None:
+                    kw.update(mask=masks[k])
                 _, theta = fn(movs[k], tgts[k], **kw)
                 init = info['final_pose'] if self.mode == 'rigid' else theta[0]
                 self.theta, self.final_theta = theta[-1], theta[0]
                 self.losses, self.best_idx = info.get('losses'), info.get('best_idx')
+                self.final_pose = info.get('final_pose')
             self.level_losses.append(self.losses)
             if self.debug:
                 ls = self.losses.detach().flatten().cpu()

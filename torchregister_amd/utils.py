@@ -90,9 +90,9 @@ class _MIFn(torch.autograd.Function):
     """loss [B] = Parzen joint-histogram mutual-information loss of (target, warped) through the HIP kernels; gradient wrt warped only."""
 
     @staticmethod
-    def forward(ctx, y, yp, rng, bins, alpha, normalized):
+    def forward(ctx, y, yp, rng, bins, alpha, normalized, mask=None):
         from . import _engine
-        loss, grad = _engine.mi_loss_grad(y, yp, rng, bins, alpha, normalized, need_grad=yp.requires_grad)
+        loss, grad = _engine.mi_loss_grad(y, yp, rng, bins, alpha, normalized, need_grad=yp.requires_grad, mask=mask)
         ctx.save_for_backward(grad)
         return loss
 
@@ -100,8 +100,8 @@ class _MIFn(torch.autograd.Function):
     def backward(ctx, gl):
         (grad,) = ctx.saved_tensors
         if grad is None:
-            return None, None, None, None, None, None
-        return None, grad * gl.view(-1, *([1] * (grad.dim() - 1))), None, None, None, None
+            return None, None, None, None, None, None, None
+        return None, grad * gl.view(-1, *([1] * (grad.dim() - 1))), None, None, None, None, None      # the mask gets no gradient
 
 
 class MILoss(nn.Module):
@@ -133,9 +133,13 @@ class MILoss(nn.Module):
         return dict(bins=self.bins, alpha=self.alpha * float(weight), normalized=self.normalized, target_range=self.target_range,
                     moving_range=self.moving_range)
 
-    def forward(self, y, yp):
-        rng = _engine.mi_range(y, yp, self.target_range, self.moving_range)
-        return _MIFn.apply(y, yp, rng, self.bins, self.alpha, self.normalized).mean()
+    def forward(self, y, yp, mask=None):
+        """mask: a region of interest on the target lattice (bool / uint8 / numeric, [B,1,*spatial] or [B,*spatial], non-zero = the voxel counts):
+        only those voxels enter the histogram, the gradient is zero elsewhere, a fitted target range is taken inside it.  It gets no gradient."""
+        if mask is not None:
+            mask = _engine._mask_u8(mask, y)
+        rng = _engine.mi_range(y, yp, self.target_range, self.moving_range, mask)
+        return _MIFn.apply(y, yp, rng, self.bins, self.alpha, self.normalized, mask).mean()
 
 
 class SSDLoss(nn.Module):

@@ -279,6 +279,11 @@ def _nmi_affine_loop(moving, target, mode, spec, nmi, w_nmi, lr, epochs, init):
     return [get_affine_warp(final_theta, moving), get_affine_warp(best_theta, moving)], [final_theta, best_theta], res
 
 
+MASK_SUPPORT = ("mask is the region of interest of the device-side mutual-information loops: mode='rigid' / 'affine' with device_loop=True and "
+                "criterion=[MILoss()], or mode='flow' with flow_model='direct' (3-D) or 'bspline' (2-D, 3-D) and MILoss alone; "
+                "the other criteria and loops have no mask")
+
+
 def device_loop_settings(criterions, weights):
     """device_loop=True (rigid / affine): the criterion list must be exactly one MILoss with a non-zero weight - returns its settings dict
     (MILoss.settings(weight)), raises ValueError for anything else.  Looks at the list only, never at a tensor."""
@@ -291,8 +296,12 @@ def device_loop_settings(criterions, weights):
 
 
 def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, weights, grad_edges, honor_criterion,
-                   optimizer, init, info, device_loop=False):
+                   optimizer, init, info, device_loop=False, mask=None):
     mi = device_loop_settings(criterions, weights) if device_loop else None      # (before anything else: a refused list touches no tensor)
+    if mask is not None:
+        if mi is None:
+            raise ValueError(MASK_SUPPORT)
+        mask = _engine._mask_u8(mask, target)
     if grad_edges:
         raise NotImplementedError("grad_edges=True: the reference's Edge3D pre-filter reflect-pads by 5000 voxels and "
                                   "crashes for every realistic volume (SURVEY Q6); it is not part of the HIP path.")
@@ -307,7 +316,7 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
         # once to (target, moving); a batch is B independent pairs, each with its own parameters - the same returns as the fused branch below
         B = moving.shape[0]
         init_b = None if init is None else (init.reshape(-1, npose).expand(B, -1) if mode == "rigid" else init.reshape(-1, nd, nd + 1).expand(B, nd, nd + 1))
-        solver = AffineMISolver(moving, target, mode=mode, mi=mi, optimizer=optimizer, lr=lr, init=init_b, capacity=max(1, epochs))
+        solver = AffineMISolver(moving, target, mode=mode, mi=mi, optimizer=optimizer, lr=lr, init=init_b, capacity=max(1, epochs), mask=mask)
         solver.run(epochs)
         final_theta, best_theta = solver.current_theta, solver.best
         if epochs == 0:
@@ -346,24 +355,26 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
 
 def affine_register(moving, target, lr=1E-5, epochs=1000, per=0.1, device="cpu", debug=True, criterions=None,
                     weights=[0.33, 0.33, 0.33], grad_edges=True, *, honor_criterion=False, optimizer="sgd", init=None, info=None,
-                    device_loop=False):
+                    device_loop=False, mask=None):
     """ref:warpings.py:30-113.  Returns ([final_warped, best_warped], [final_theta, best_theta]).
 
     NOTE: like the reference, grad_edges defaults to True here when called directly (and then
     raises, Q6); Register passes grad_edges=False.
     device_loop=True (keyword-only extension, also on rigid_register): criterions must be exactly [MILoss] with a non-zero weight (ValueError
     otherwise) and the whole loop runs on the device in trx_affine_mi_run (AffineMISolver): honor_criterion is implied, the pairs of a batch are
-    independent, info gets the keys of the fused MSE / NCC / SSD branch.  The default False changes no existing route."""
+    independent, info gets the keys of the fused MSE / NCC / SSD branch.  The default False changes no existing route.
+    mask (keyword-only extension, with device_loop=True only; ValueError otherwise, before any device work; also on rigid_register): a region of
+    interest on the target lattice, [B,1,*spatial] or [B,*spatial], non-zero = the voxel counts - only those voxels enter the mutual information."""
     return _affine_family("affine", moving, target, lr, epochs, device, debug, criterions, weights, grad_edges,
-                          honor_criterion, optimizer, init, info, device_loop)
+                          honor_criterion, optimizer, init, info, device_loop, mask)
 
 
 def rigid_register(moving, target, lr=1E-5, epochs=1000, per=0.1, device="cpu", debug=True, criterions=None,
                    weights=[0.33, 0.33, 0.33], grad_edges=True, *, honor_criterion=False, optimizer="sgd", init=None, info=None,
-                   device_loop=False):
+                   device_loop=False, mask=None):
     """ref:warpings.py:117-174.  `init` = initial pose (default torch.rand on the tensors' device)."""
     return _affine_family("rigid", moving, target, lr, epochs, device, debug, criterions, weights, grad_edges,
-                          honor_criterion, optimizer, init, info, device_loop)
+                          honor_criterion, optimizer, init, info, device_loop, mask)
 
 
 class _FlowLossFn(torch.autograd.Function):
@@ -476,9 +487,20 @@ class flow_register(nn.Module):
             return y
         return self.warp(x, self.flow)
 
-    def optimize(self, moving, target, device=None, debug=True, grad_edges=False):
+    def mask_supported(self, ndim):
+        """Whether optimize() on `ndim`-dimensional images runs one of the device-side mutual-information loops, the ones that take a mask."""
+        alone = len(self.criterions) == 1 and isinstance(self.criterions[0], MILoss)
+        return alone and not self.diffeomorphic and (self.flow_model == "bspline" or (self.flow_model == "direct" and ndim == 3))
+
+    def optimize(self, moving, target, device=None, debug=True, grad_edges=False, *, mask=None):
+        """mask (keyword-only extension): a region of interest on the target lattice, [B,1,*spatial] or [B,*spatial], non-zero = the voxel counts,
+        for MILoss alone with flow_model='direct' (3-D) or 'bspline'; ValueError anywhere else, before any device work."""
         if grad_edges:
             raise NotImplementedError("grad_edges=True is not supported (SURVEY Q6)")
+        if mask is not None:
+            if not self.mask_supported(target.dim() - 2):
+                raise ValueError(MASK_SUPPORT)
+            mask = _engine._mask_u8(mask, target)
         spec = loss_spec_from(self.criterions, self.weights[: len(self.criterions)])
         if self.flow_model == "unet":
             # The U-Net's convolutions run in MIOpen through torch.  With torch's default (benchmark off) MIOpen's immediate mode picks
@@ -491,7 +513,7 @@ class flow_register(nn.Module):
                     return self._optimize_unet(moving, target, spec, debug)
             return self._optimize_unet(moving, target, spec, debug)
         if self.flow_model == "bspline":
-            return self._optimize_bspline(moving, target, spec, debug)
+            return self._optimize_bspline(moving, target, spec, debug, mask)
         lncc = mi = None
         if spec is None and moving.dim() == 5 and len(self.criterions) == 1 and isinstance(self.criterions[0], MILoss):
             # direct flow + mutual information (+ smoothness) as ONE device-side loop (trx_flow_mi_run); ranges fitted once to (target, moving)
@@ -507,7 +529,7 @@ class flow_register(nn.Module):
         # pair: a batch is B independent registrations), a pair that has converged ignores the remaining iterations, and the flow
         # of its last forward is kept beside the final one - exactly the state the reference leaves behind, with one host sync.
         solver = FlowSolver(moving, target, loss=spec, optimizer=self.optimizer_kind, lr=self.lr, capacity=max(1, self.max_epochs),
-                            smooth_weight=self.smooth_weight, stop_crit=self.stop_crit, keep_last=True, lncc=lncc, mi=mi, init=self.init_flow)
+                            smooth_weight=self.smooth_weight, stop_crit=self.stop_crit, keep_last=True, lncc=lncc, mi=mi, init=self.init_flow, mask=mask)
         solver.run(self.max_epochs)
         done = solver.step.cpu()                       # iterations executed per pair (the only host sync)
         n = int(done.max()) if self.max_epochs > 0 else 0
@@ -520,13 +542,13 @@ class flow_register(nn.Module):
         if debug:
             print("Optimization ended with status: %s" % message)
 
-    def _optimize_bspline(self, moving, target, spec, debug):
+    def _optimize_bspline(self, moving, target, spec, debug, mask=None):
         """The 'direct' loop with a control lattice as the parameter: one trx_bspline_run call, per-pair early stop on the device, one host sync."""
         from ._engine import BSplineSolver
         mi = self.criterions[0].settings(self.weights[0]) if spec is None else None     # __init__ admits MILoss alone beside the fused criteria
         solver = BSplineSolver(moving, target, self.spacing, loss=spec, mi=mi, optimizer=self.optimizer_kind, lr=self.lr, init=self.init_control,
                                base=self.base_flow, capacity=max(1, self.max_epochs), stop_crit=self.stop_crit, keep_last=True,
-                               bending_weight=self.bending_weight, squarings=self.squarings if self.diffeomorphic else None)
+                               bending_weight=self.bending_weight, squarings=self.squarings if self.diffeomorphic else None, mask=mask)
         solver.run(self.max_epochs)
         done = solver.step.cpu()
         n = int(done.max()) if self.max_epochs > 0 else 0
