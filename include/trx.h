@@ -52,7 +52,10 @@ extern "C" {
  *        trx_bspline_svf_run (stationary velocity field: the exponential by scaling and squaring, its exact adjoint, and the diffeomorphic form of the
  *        free-form-deformation loop) - new entry points only.
  *        Later addition under the same number: trx_mi_cfg grows by one trailing field, `mask` (a region of interest on the target lattice for every
- *        mutual-information entry point; NULL = every voxel, the launches and bits of before) - no entry point changed its signature. */
+ *        mutual-information entry point; NULL = every voxel, the launches and bits of before) - no entry point changed its signature.
+ *        Later addition under the same number: trx_moving_grid, trx_affine_mi_loss_grad_grids, trx_affine_mi_run_grids, trx_affine_warp_grids (rigid /
+ *        affine mutual information and the forward warp for a moving image on a lattice and voxel size of its own) - new entry points and one new
+ *        struct only. */
 #define TRX_VERSION 240
 #define TRX_PSTRIDE 12  /* floats per pair in theta / param / adam / best_theta arrays */
 
@@ -572,7 +575,8 @@ int trx_bspline_mi_run(const trx_volumes *vol, const trx_mi_cfg *cfg, const trx_
  * all, in either pass - it costs its mask byte - and its contribution to the partial rows is exactly zero; dtheta = what trx_affine_warp_backward
  * returns for grad_out = the masked grad_warped.  A pair with an empty mask has loss 0 and dtheta 0, and a run leaves its theta where it was. */
 
-/* [host] bytes of workspace for this geometry (only ndim, B, D, H, W of `vol` are read) and bin count; 0 = rejected.  Pure arithmetic. */
+/* [host] bytes of workspace for this geometry (only ndim, B, D, H, W of `vol` are read) and bin count; 0 = rejected.  Pure arithmetic.  Also the
+ * query of the *_grids entry points below: their workspace depends on the target lattice (vol) alone, not on the moving one. */
 size_t trx_affine_mi_workspace_bytes(const trx_volumes *vol /*[host]*/, int bins);
 
 /* loss[B] and (dtheta != NULL) dtheta[B][TRX_PSTRIDE] at theta[B][TRX_PSTRIDE].  Replaces the chain trx_affine_warp -> trx_mi_loss_grad ->
@@ -590,6 +594,37 @@ int trx_affine_mi_loss_grad(const trx_volumes *vol, const trx_mi_cfg *cfg, const
  * tests/affine_mi_ref.py (oracle/compose.py::affine_warp, pose_to_theta + tests/mi_ref.py under torch autograd and torch.optim). */
 int trx_affine_mi_run(const trx_volumes *vol, const trx_mi_cfg *cfg, const trx_opt_cfg *opt, const trx_affine_state *st, int iters, void *workspace,
                       size_t workspace_bytes, void *stream);
+
+/* ---- The same three operations for a moving image on a lattice of its own, and in millimetres.  Extension.
+ * vol->D / H / W describe the TARGET lattice: the voxels the passes walk, cfg->mask, the base-coordinate tables xn / yn / zn, the output of the warp,
+ * the workspace.  vol->moving holds volumes of mg->D x mg->H x mg->W voxels, vol->moving_stride counts moving elements.
+ * Sampling: for target voxel (x, y, z) the normalised coordinate (xn, yn, zn) is formed as above; the moving coordinate is
+ *   theta_eff . (xn, yn, zn, 1),  theta_eff[k] = theta[k] * scale[k] (one fp32 multiply, k < ndim (ndim + 1), theta's own layout),
+ * un-normalised with the MOVING sizes and sampled in the moving volume with zero padding:
+ *   grid_sample(moving, affine_grid(theta_eff, target.shape), align_corners=False).
+ * World space: with e = size * voxel size / 2 the half extent of an axis in mm, scale[r][c] = e_target[c] / e_moving[r] on the matrix entries and 1 on
+ * the translation column give  moving_mm = theta[:, :nd] target_mm + e_moving (.) theta[:, nd]  for two volumes whose centres coincide and whose axes
+ * are aligned: with theta = Theta(pose) the map is rigid in millimetres whatever the voxel sizes.  scale == 1 everywhere: the two normalised cubes
+ * coincide, and with equal sizes every number below has the bits of the entry point above.
+ * theta, dtheta, st->theta, st->param, st->best_theta are the UNSCALED theta: dtheta = dL/dtheta_eff (.) scale (formed in fp64 in the reduction behind pass
+ * 2, whose order does not change; the S / 2 per row is the moving size's), so the rigid chain rule and the whole epilogue are trx_affine_mi_run's.
+ * Everything else keeps its meaning: losses, best tracking, SGD / Adam, capacity, the mask (target lattice, one byte per target voxel), N_m, the
+ * fixed-point histogram, the same bits on every call and in every batch, the launches per evaluation.
+ * Workspace: it depends on the target lattice alone - trx_affine_mi_workspace_bytes(vol, bins) is the query.
+ * Refusals on top of the entry points above, before any HIP call: TRX_ERR_ARG (mg NULL, a moving size < 1, >= 2^31 moving voxels, a scale entry that
+ * is not finite, a matrix scale entry <= 0), TRX_ERR_NDIM (ndim 2 with mg->D != 1). */
+typedef struct {
+    int D, H, W;                 /* the MOVING lattice (D = 1 for ndim 2) */
+    float scale[TRX_PSTRIDE];    /* theta's own layout, row-major [ndim][ndim + 1]; entries past ndim (ndim + 1) are not read */
+} trx_moving_grid;
+int trx_affine_mi_loss_grad_grids(const trx_volumes *vol, const trx_moving_grid *mg /*[host]*/, const trx_mi_cfg *cfg, const float *theta, float *loss,
+                                  float *dtheta /*nullable*/, void *workspace, size_t workspace_bytes, void *stream);
+int trx_affine_mi_run_grids(const trx_volumes *vol, const trx_moving_grid *mg /*[host]*/, const trx_mi_cfg *cfg, const trx_opt_cfg *opt,
+                            const trx_affine_state *st, int iters, void *workspace, size_t workspace_bytes, void *stream);
+/* out[B][channels][target lattice] = the sample of moving[B][channels][moving lattice] at theta_eff; channels share coordinates (trx_affine_warp's
+ * layout: vol->moving_stride between batch items).  vol->target is not read.  Equal sizes and scale == 1: trx_affine_warp itself, the same bits.  No
+ * backward and no nearest-neighbour form. */
+int trx_affine_warp_grids(const trx_volumes *vol, const trx_moving_grid *mg /*[host]*/, const float *theta, int channels, float *out, void *stream);
 
 /* ---- Stationary velocity field (Arsigny et al. 2006; NiftyReg's -vel, VoxelMorph-diff's VecInt; extension: the reference has no such model, its flows
  * are displacements, ref:warpings.py:178-242).  Fields are [B][ndim][D][H][W] fp32 contiguous (2-D: [B][2][H][W], D = 1), voxel units and channel order

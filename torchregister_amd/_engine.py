@@ -296,9 +296,14 @@ class AffineSolver:
         return self._unpad(self.best_theta).clone()
 
 
-def affine_warp(theta, moving):
-    """get_affine_warp forward on the GPU: moving [B,C,*sp], theta [B,nd,nd+1] -> warped [B,C,*sp]."""
+def affine_warp(theta, moving, *, size=None):
+    """get_affine_warp forward on the GPU: moving [B,C,*sp], theta [B,nd,nd+1] -> warped [B,C,*sp].
+    size (keyword-only extension): the spatial shape of the output lattice when it is not moving's own - warped [B,C,*size] =
+    F.grid_sample(moving, F.affine_grid(theta, [B,C,*size]), align_corners=False), theta being the effective theta affine_grid takes
+    (include/trx.h: trx_affine_warp_grids).  No backward on that route."""
     lib = _lib.load()
+    if size is not None and tuple(int(s) for s in size) != tuple(moving.shape[2:]):
+        return _affine_warp_grids(lib, theta, moving, tuple(int(s) for s in size))
     batch = _Batch(moving)
     th = pad_theta(theta.detach().reshape(batch.B, -1), batch.nd)
     out = torch.empty_like(batch.moving)
@@ -1463,14 +1468,132 @@ def _mi_pair_batch(moving, target):
     return batch
 
 
-def affine_mi_loss_grad(moving, target, theta, rng, bins=32, alpha=1.0, normalized=False, need_grad=True, mask=None):
+def _half_extents(shape, voxel, name):
+    """Half extents in mm of a lattice, in theta's row order (x, y(, z)): size * voxel size / 2.  shape / voxel: the tensor's axis order."""
+    voxel = tuple(float(v) for v in voxel)
+    if len(voxel) != len(shape):
+        raise ValueError(f"{name} must have {len(shape)} entries in the tensor's axis order {'(dz, dy, dx)' if len(shape) == 3 else '(dy, dx)'}, got {voxel}")
+    if not all(v > 0.0 and v != float("inf") for v in voxel):       # (NaN fails v > 0)
+        raise ValueError(f"{name} must be positive and finite, got {voxel}")
+    return torch.tensor([s * v / 2.0 for s, v in zip(shape, voxel)][::-1], dtype=torch.float64)
+
+
+def grid_scale(moving_shape, target_shape, moving_voxel=None, target_voxel=None):
+    """The scale [nd, nd+1] (fp64, CPU; host arithmetic only) that the cross-lattice entry points multiply theta by, theta_eff = theta * scale
+    (include/trx.h: trx_moving_grid).  Without voxel sizes: all ones - the two normalised cubes coincide, theta means what F.affine_grid(theta,
+    target.shape) + F.grid_sample(moving, ...) make of it.  With both: scale[r][c] = e_target[c] / e_moving[r] on the matrix and 1 on the
+    translation column, e = size * voxel size / 2 in mm, so that theta acts between the two volumes in millimetres (centres coinciding, axes
+    aligned): Theta(pose) is then rigid whatever the voxel sizes.  Shapes and voxel sizes in the tensors' axis order, (dz, dy, dx) / (dy, dx)."""
+    moving_shape, target_shape = tuple(int(s) for s in moving_shape), tuple(int(s) for s in target_shape)
+    nd = len(target_shape)
+    if nd not in (2, 3) or len(moving_shape) != nd or min(moving_shape + target_shape) < 1:
+        raise ValueError(f"expected two spatial shapes of 2 or 3 positive sizes, got {moving_shape} and {target_shape}")
+    if (moving_voxel is None) != (target_voxel is None):
+        raise ValueError("moving_voxel and target_voxel go together: give both voxel sizes (theta acts in millimetres) or neither (theta acts "
+                         "between the two normalised cubes)")
+    scale = torch.ones(nd, nd + 1, dtype=torch.float64)
+    if moving_voxel is not None:
+        e_m, e_t = _half_extents(moving_shape, moving_voxel, "moving_voxel"), _half_extents(target_shape, target_voxel, "target_voxel")
+        scale[:, :nd] = e_t[None, :] / e_m[:, None]
+    return scale
+
+
+class _GridPair:
+    """B single-channel (moving, target) pairs on two lattices, described for the cross-lattice entry points (include/trx.h: trx_moving_grid):
+    the Volumes carry the TARGET lattice and its base-coordinate tables, the MovingGrid the moving lattice and the scales.  _Batch keeps
+    refusing differing shapes; this is the description of the pair the new path uses."""
+
+    def __init__(self, moving, target, scale=None, moving_voxel=None, target_voxel=None):
+        _require_gpu(moving, "moving")
+        _require_gpu(target, "target")
+        if moving.dim() not in (4, 5) or target.dim() != moving.dim():
+            raise ValueError(f"expected two [B,1,H,W] or two [B,1,D,H,W] tensors, got {tuple(moving.shape)} and {tuple(target.shape)}")
+        if moving.shape[1] != 1 or target.shape[1] != 1:
+            raise ValueError("the mutual-information path takes single-channel volumes [B,1,...]")
+        if moving.shape[0] != target.shape[0]:
+            raise ValueError("moving and target batch sizes differ")
+        self.moving, self.target = moving.contiguous(), target.contiguous()
+        self.nd, self.B, self.C, self.device = moving.dim() - 2, moving.shape[0], 1, moving.device
+        self.spatial, self.moving_spatial = tuple(target.shape[2:]), tuple(moving.shape[2:])
+        if scale is None:
+            scale = grid_scale(self.moving_spatial, self.spatial, moving_voxel, target_voxel)
+        scale = torch.as_tensor(scale).detach().to("cpu", torch.float32)
+        if tuple(scale.shape) != (self.nd, self.nd + 1):
+            raise ValueError(f"expected a scale of shape {(self.nd, self.nd + 1)}, got {tuple(scale.shape)}")
+        self.scale = scale                                        # what the kernels multiply by: fp32
+        self.half_extent_moving = None if moving_voxel is None else _half_extents(self.moving_spatial, moving_voxel, "moving_voxel")
+        self.tables = base_tables(self.spatial, self.device)
+
+    def vol(self):
+        v = _lib.Volumes()
+        v.moving, v.target = self.moving.data_ptr(), self.target.data_ptr()
+        v.moving_stride, v.target_stride = self.moving[0].numel(), self.target[0].numel()      # moving elements, target elements
+        v.ndim, v.B = self.nd, self.B
+        v.D, v.H, v.W = _dhw(self.spatial)
+        v.flags = 0
+        v.zn = None
+        if self.nd == 3:
+            v.zn, v.yn, v.xn = (t.data_ptr() for t in self.tables)
+        else:
+            v.yn, v.xn = (t.data_ptr() for t in self.tables)
+        return v
+
+    def grid(self):
+        return _moving_grid(self.moving_spatial, self.scale)
+
+
+def _moving_grid(moving_spatial, scale=None):
+    """trx_moving_grid of a moving lattice (the tensor's spatial shape) and a scale [nd, nd+1] (None: ones)."""
+    g = _lib.MovingGrid()
+    g.D, g.H, g.W = _dhw(tuple(moving_spatial))
+    nd = len(moving_spatial)
+    flat = [1.0] * (nd * (nd + 1)) if scale is None else [float(s) for s in scale.reshape(-1)]
+    for k in range(PSTRIDE):
+        g.scale[k] = flat[k] if k < len(flat) else 0.0
+    return g
+
+
+def _affine_warp_grids(lib, theta, moving, size):
+    """affine_warp(..., size=) on a lattice other than moving's: trx_affine_warp_grids with scale 1 (theta is the effective one)."""
+    _require_gpu(moving, "moving")
+    if moving.dim() not in (4, 5) or len(size) != moving.dim() - 2 or min(size) < 1:
+        raise ValueError(f"expected [B,C,H,W] or [B,C,D,H,W] and a size of as many positive entries, got {tuple(moving.shape)} and {size}")
+    mov = moving.contiguous()
+    B, C, nd, dev = mov.shape[0], mov.shape[1], mov.dim() - 2, mov.device
+    th = pad_theta(theta.detach().to(dev).reshape(B, -1), nd)
+    out = torch.empty((B, C) + size, dtype=torch.float32, device=dev)
+    tables = base_tables(size, dev)
+    v = _lib.Volumes()
+    v.moving, v.target = mov.data_ptr(), None
+    v.moving_stride, v.target_stride = mov[0].numel(), 0
+    v.ndim, v.B = nd, B
+    v.D, v.H, v.W = _dhw(size)
+    v.flags = 0
+    v.zn = None
+    if nd == 3:
+        v.zn, v.yn, v.xn = (t.data_ptr() for t in tables)
+    else:
+        v.yn, v.xn = (t.data_ptr() for t in tables)
+    mg = _moving_grid(tuple(mov.shape[2:]))
+    with torch.cuda.device(dev):
+        rc = lib.trx_affine_warp_grids(ctypes.byref(v), ctypes.byref(mg), _lib.ptr(th), C, _lib.ptr(out), _lib.current_stream(dev))
+    _lib.check(rc, "trx_affine_warp_grids")
+    return out
+
+
+def affine_mi_loss_grad(moving, target, theta, rng, bins=32, alpha=1.0, normalized=False, need_grad=True, mask=None, scale=None):
     """Mutual information of (target, affine warp of moving by theta) and its gradient with respect to theta without a warped volume (extension,
     include/trx.h: trx_affine_mi_loss_grad): moving / target [B,1,*spatial] fp32 on the GPU, theta [B,nd,nd+1], rng [B,4] (mi_range), mask (see
     _mask_u8) or None = every voxel.  Returns (loss [B], dtheta [B,nd,nd+1] or None) - what affine_warp -> mi_loss_grad -> affine_warp_backward
-    give, in two passes over the pair."""
+    give, in two passes over the pair.
+    moving may live on a lattice of its own (another spatial shape), and scale [nd, nd+1] (grid_scale; None = ones) multiplies theta entry by
+    entry in front of the sampler (trx_affine_mi_loss_grad_grids): theta and dtheta are the unscaled ones, the mask and the loop's voxels are
+    the target's.  With moving's shape equal to target's and scale None this is the one-lattice entry point, the bits of before."""
     if mask is not None:
         mask = _mask_u8(mask, target)
     lib = _lib.load()
+    if scale is not None or (isinstance(moving, torch.Tensor) and isinstance(target, torch.Tensor) and moving.shape[2:] != target.shape[2:]):
+        return _affine_mi_loss_grad_grids(lib, _GridPair(moving, target, scale), theta, rng, bins, alpha, normalized, need_grad, mask)
     batch = _mi_pair_batch(moving, target)
     B, nd = batch.B, batch.nd
     if tuple(rng.shape) != (B, 4):
@@ -1496,6 +1619,32 @@ def affine_mi_loss_grad(moving, target, theta, rng, bins=32, alpha=1.0, normaliz
     return loss, (dth[:, : nd * (nd + 1)].reshape(B, nd, nd + 1) if need_grad else None)
 
 
+def _affine_mi_loss_grad_grids(lib, pair, theta, rng, bins, alpha, normalized, need_grad, mask):
+    """affine_mi_loss_grad on two lattices (pair: _GridPair; mask: uint8 on the target lattice or None)."""
+    B, nd, dev = pair.B, pair.nd, pair.device
+    if tuple(rng.shape) != (B, 4):
+        raise ValueError(f"expected a range tensor [{B}, 4], got {tuple(rng.shape)}")
+    rng = rng.detach().to(device=dev, dtype=torch.float32).contiguous()
+    th = pad_theta(theta.detach().to(dev).reshape(B, -1), nd)
+    cfg = _lib.MICfg()
+    cfg.bins, cfg.alpha, cfg.normalized, cfg.range = _mi_bins(bins), float(alpha), int(bool(normalized)), rng.data_ptr()
+    if mask is not None:
+        mask = mask.to(dev)
+        cfg.mask = mask.data_ptr()
+    vol, mg = pair.vol(), pair.grid()
+    ws_bytes = lib.trx_affine_mi_workspace_bytes(ctypes.byref(vol), cfg.bins)
+    if ws_bytes == 0:
+        raise _lib.TrxError(f"trx_affine_mi_workspace_bytes rejected {B} x {pair.spatial} with {bins} bins")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    loss = torch.empty(B, device=dev)
+    dth = torch.zeros(B, PSTRIDE, device=dev) if need_grad else None
+    with torch.cuda.device(dev):
+        rc = lib.trx_affine_mi_loss_grad_grids(ctypes.byref(vol), ctypes.byref(mg), ctypes.byref(cfg), _lib.ptr(th), _lib.ptr(loss), _lib.ptr(dth), _lib.ptr(ws),
+                                               ws_bytes, _lib.current_stream(dev))
+    _lib.check(rc, "trx_affine_mi_loss_grad_grids")
+    return loss, (dth[:, : nd * (nd + 1)].reshape(B, nd, nd + 1) if need_grad else None)
+
+
 class AffineMISolver:
     """Batched rigid / affine registration under the Parzen joint-histogram mutual information, the whole loop on the GPU (extension, include/trx.h:
     trx_affine_mi_run): per iteration the warp is fused into the histogram pass and into the gradient pass - no warped volume, no autograd, no
@@ -1506,13 +1655,21 @@ class AffineMISolver:
     mi: dict(bins=32, alpha=1.0, normalized=False, target_range=None, moving_range=None); a range of None is fitted once, here, to
     (target, moving), the moving side widened to contain 0.
     mask: a region of interest on the target lattice (see _mask_u8), one per pair, or None = every voxel: only voxels inside it enter the
-    histogram and the gradient, the target's range is fitted inside it, and the solver keeps the uint8 tensor (`.mask`) alive."""
+    histogram and the gradient, the target's range is fitted inside it, and the solver keeps the uint8 tensor (`.mask`) alive.
+    moving may live on a lattice of its own (another spatial shape), and moving_voxel / target_voxel (both or neither; the tensors' axis order,
+    mm) make theta act in millimetres: the loop is trx_affine_mi_run_grids, sampling at theta * scale (grid_scale).  The state (theta, param,
+    best_theta) stays the UNSCALED theta; .effective(theta) is what F.affine_grid takes, .world_matrix(theta) the map in mm.  With equal shapes
+    and no voxel sizes the solver is the one-lattice one: the same entry point, the same bits."""
 
-    def __init__(self, moving, target, mode="affine", mi=None, optimizer="sgd", lr=1e-5, init=None, capacity=1000, betas=(0.9, 0.999), eps=1e-8, mask=None):
+    def __init__(self, moving, target, mode="affine", mi=None, optimizer="sgd", lr=1e-5, init=None, capacity=1000, betas=(0.9, 0.999), eps=1e-8, mask=None,
+                 moving_voxel=None, target_voxel=None):
         if mask is not None:
             mask = _mask_u8(mask, target)
         self.lib = _lib.load()
-        self.batch = _mi_pair_batch(moving, target)
+        two = moving_voxel is not None or target_voxel is not None or (
+            isinstance(moving, torch.Tensor) and isinstance(target, torch.Tensor) and moving.shape[2:] != target.shape[2:])
+        self.batch = _GridPair(moving, target, None, moving_voxel, target_voxel) if two else _mi_pair_batch(moving, target)
+        self.grid = self.batch.grid() if two else None      # trx_moving_grid, or None: one lattice
         b, nd, dev = self.batch.B, self.batch.nd, self.batch.device
         self.nd, self.mode = nd, mode
         self.opt = opt_cfg(optimizer, lr, betas, eps)
@@ -1565,9 +1722,14 @@ class AffineMISolver:
                                 f"{self.capacity} (create the solver with a larger `capacity`)")
         self.enqueued += iters
         with torch.cuda.device(self.batch.device):
-            rc = self.lib.trx_affine_mi_run(ctypes.byref(self.vol), ctypes.byref(self.mi), ctypes.byref(self.opt), ctypes.byref(self.state), iters,
-                                            _lib.ptr(self.workspace), self.ws_bytes, _lib.current_stream(self.batch.device))
-        _lib.check(rc, "trx_affine_mi_run")
+            if self.grid is None:
+                rc = self.lib.trx_affine_mi_run(ctypes.byref(self.vol), ctypes.byref(self.mi), ctypes.byref(self.opt), ctypes.byref(self.state), iters,
+                                                _lib.ptr(self.workspace), self.ws_bytes, _lib.current_stream(self.batch.device))
+            else:
+                rc = self.lib.trx_affine_mi_run_grids(ctypes.byref(self.vol), ctypes.byref(self.grid), ctypes.byref(self.mi), ctypes.byref(self.opt),
+                                                      ctypes.byref(self.state), iters, _lib.ptr(self.workspace), self.ws_bytes,
+                                                      _lib.current_stream(self.batch.device))
+        _lib.check(rc, "trx_affine_mi_run" if self.grid is None else "trx_affine_mi_run_grids")
 
     def _unpad(self, t):
         nd = self.nd
@@ -1580,6 +1742,31 @@ class AffineMISolver:
     @property
     def best(self):
         return self._unpad(self.best_theta).clone()
+
+    @property
+    def scale(self):
+        """[nd, nd+1] fp32 on the solver's device: what the kernels multiply theta by (ones on one lattice)."""
+        if self.grid is None:
+            return torch.ones(self.nd, self.nd + 1, device=self.batch.device)
+        return self.batch.scale.to(self.batch.device)
+
+    def effective(self, theta):
+        """theta * scale in fp32, as the kernels form it: the theta of F.affine_grid(., target.shape) + F.grid_sample(moving, .)."""
+        return theta.to(torch.float32) * self.scale.to(theta.device)
+
+    def world_matrix(self, theta):
+        """[B, nd+1, nd+1] fp64, homogeneous, rows and columns in theta's order (x, y(, z)): moving_mm = M target_mm for the two volumes with
+        their centres at the origin, M = [theta[:, :nd] | e_moving * theta[:, nd]].  None without voxel sizes."""
+        e_m = getattr(self.batch, "half_extent_moving", None)
+        if e_m is None:
+            return None
+        nd = self.nd
+        th = theta.detach().to(torch.float64).reshape(-1, nd, nd + 1)
+        M = torch.zeros(th.shape[0], nd + 1, nd + 1, dtype=torch.float64, device=th.device)
+        M[:, :nd, :nd] = th[:, :, :nd]
+        M[:, :nd, nd] = th[:, :, nd] * e_m.to(th.device)
+        M[:, nd, nd] = 1.0
+        return M
 
 
 def local_ncc_loss_grad(target, warped, window=9, alpha=1.0, eps=1e-5, need_grad=True):

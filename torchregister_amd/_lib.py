@@ -76,6 +76,10 @@ class MICfg(ctypes.Structure):
                 ("mask", ctypes.c_void_p)]
 
 
+class MovingGrid(ctypes.Structure):
+    _fields_ = [("D", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("scale", ctypes.c_float * PSTRIDE)]
+
+
 # name -> (restype, argtypes); must list every symbol include/trx.h declares (tests check this)
 _P = ctypes.c_void_p
 SIGNATURES = {
@@ -162,6 +166,10 @@ SIGNATURES = {
     "trx_affine_mi_loss_grad": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MICfg), _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "trx_affine_mi_run": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MICfg), ctypes.POINTER(OptCfg), ctypes.POINTER(AffineState), ctypes.c_int, _P,
                                          ctypes.c_size_t, _P]),
+    "trx_affine_mi_loss_grad_grids": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), ctypes.POINTER(MICfg), _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "trx_affine_mi_run_grids": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), ctypes.POINTER(MICfg), ctypes.POINTER(OptCfg),
+                                               ctypes.POINTER(AffineState), ctypes.c_int, _P, ctypes.c_size_t, _P]),
+    "trx_affine_warp_grids": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), _P, ctypes.c_int, _P, _P]),
     "trx_svf_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
     "trx_svf_exp": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 7 + [_P, ctypes.c_size_t, _P]),
     "trx_svf_exp_backward": (ctypes.c_int, [_P, _P, _P] + [ctypes.c_int] * 7 + [_P, ctypes.c_size_t, _P]),

@@ -19,6 +19,10 @@
 // mask, 1 outside) and skips a voxel outside it before any coordinate is formed - nothing is sampled, nothing enters the LDS tables or the thread's
 // sums.  A block whose chunk lies wholly outside the mask still clears and flushes (adding nothing) and still writes its partial row (zeros): the
 // reduction reads a fixed number of rows.  The table kernel takes N_m from the counts; the update kernel zeroes all K x K cells, masked or not.
+// Two lattices (trx_moving_grid, DESIGN.md section 4.13: trx_affine_mi_loss_grad_grids, trx_affine_mi_run_grids, trx_affine_warp_grids): both passes, the
+// update kernel and the one-evaluation reduction have a cross-lattice sibling each (*_grids_kernel) -
+// the voxels walked, the mask and the base coordinates are the target lattice's, the sample is taken at theta (.) scale in a moving volume of its own
+// size, and the reduction multiplies the sums by the scales.  The one-lattice kernels keep their names, arguments and code.
 #include "affine_finalize.h"   // reduce_partials, fin_load / fin_update (the epilogue of the affine step), launch_bwd_finalize (affine_host.h)
 #include "mi_dev.h"
 
@@ -78,6 +82,17 @@ __device__ __forceinline__ AmiSample<ND> ami_sample(const trx_volumes &vol, cons
     return r;
 }
 
+// Two lattices (trx_moving_grid): the loop's voxels, the mask and the base coordinates stay on vol's (target) lattice, the sample is
+// taken in a moving volume of its own size at theta_eff = theta (.) scale.  theta_eff is formed here, once per block, from uniform values (theta's row
+// through scalar loads, the scales from the kernel arguments): the voxel loop sees ND (ND + 1) registers, as it does with one lattice.
+template <int ND>
+__device__ __forceinline__ void ami_theta_eff(const float *__restrict__ th, const trx_moving_grid &mg, float (&te)[ND * (ND + 1)])
+{
+#pragma unroll
+    for (int k = 0; k < ND * (ND + 1); k++)      // one fp32 rounding: (theta, scale) samples exactly where (fl(theta scale), 1) does; pinned to an SGPR like theta's own row
+        te[k] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(th[k] * mg.scale[k])));
+}
+
 // pass 1: warp and histogram
 template <int ND, bool MASKED>
 __global__ __launch_bounds__(TRX_BLOCK) void ami_hist_kernel(trx_volumes vol, const float *__restrict__ theta, unsigned N, int K, int T, const float *__restrict__ range,
@@ -97,6 +112,36 @@ __global__ __launch_bounds__(TRX_BLOCK) void ami_hist_kernel(trx_volumes vol, co
         if (!mi_counts<MASKED>(mk, vw.i)) continue;      // before any coordinate: a voxel outside the mask costs its mask byte and nothing else
         const float xn = base_coord(vol.xn, vw.x, vol.W), yn = base_coord(vol.yn, vw.y, vol.H), zn = ND == 3 ? base_coord(vol.zn, vw.z, vol.D) : 0.f;
         const AmiSample<ND> s = ami_sample<ND>(vol, th, mov, vw.x, vw.y, vw.z, xn, yn, zn);
+        mi_accumulate(mine, mi_voxel(__builtin_nontemporal_load(tgt + vw.i), s.v, m, K), K);
+    }
+    __syncthreads();
+    mi_flush(ami_lds, T, KK, counts + (size_t)b * KK);
+}
+
+// pass 1 on two lattices: ami_hist_kernel with theta_eff for theta and the moving sizes for the sampler's (mvol: vol with D, H, W replaced - the sampler
+// reads nothing else of it).  The mask test stays in front of any coordinate arithmetic.  A kernel of its own: the one-lattice instances keep their code.
+template <int ND, bool MASKED>
+__global__ __launch_bounds__(TRX_BLOCK) void ami_hist_grids_kernel(trx_volumes vol, trx_moving_grid mg, const float *__restrict__ theta, unsigned N, int K, int T,
+                                                                     const float *__restrict__ range, unsigned long long *__restrict__ counts,
+                                                                     const unsigned char *__restrict__ mask)
+{
+    extern __shared__ unsigned long long ami_lds[];           // [T][K][K]
+    const int b = blockIdx.y, tid = threadIdx.x, KK = K * K;
+    mi_lds_clear(ami_lds, T * KK);
+    const MiScale m = mi_scale(range, b, K);
+    float te[ND * (ND + 1)];
+    ami_theta_eff<ND>(theta + (size_t)b * TRX_PSTRIDE, mg, te);
+    trx_volumes mvol = vol;
+    mvol.D = mg.D; mvol.H = mg.H; mvol.W = mg.W;
+    const float *__restrict__ mov = vol.moving + (size_t)b * vol.moving_stride;
+    const float *__restrict__ tgt = vol.target + (size_t)b * vol.target_stride;
+    const unsigned char *mk = MASKED ? mask + (size_t)b * N : nullptr;
+    unsigned long long *mine = ami_lds + ((tid >> 6) % T) * KK;
+    const unsigned first = blockIdx.x * (unsigned)kMiChunk, last = min(N, first + (unsigned)kMiChunk);
+    for (VoxelWalk vw(first + tid, TRX_BLOCK, vol.H, vol.W); vw.i < last; vw.next(vol.H, vol.W)) {
+        if (!mi_counts<MASKED>(mk, vw.i)) continue;
+        const float xn = base_coord(vol.xn, vw.x, vol.W), yn = base_coord(vol.yn, vw.y, vol.H), zn = ND == 3 ? base_coord(vol.zn, vw.z, vol.D) : 0.f;
+        const AmiSample<ND> s = ami_sample<ND>(mvol, te, mov, vw.x, vw.y, vw.z, xn, yn, zn);
         mi_accumulate(mine, mi_voxel(__builtin_nontemporal_load(tgt + vw.i), s.v, m, K), K);
     }
     __syncthreads();
@@ -164,11 +209,55 @@ __global__ __launch_bounds__(TRX_BLOCK) void ami_grad_kernel(trx_volumes vol, co
     ami_block_sum_store<NT>(vals, partials + ((size_t)b * gridDim.x + blockIdx.x) * NT);
 }
 
+// pass 2 on two lattices: the rows are sums of gw * (sampler derivative in moving voxels) * (xn, yn, zn, 1) - dL/dtheta_eff up to the S / 2 of the MOVING
+// sizes; the reduction behind the pass applies that and the scales.
+template <int ND, bool MASKED>
+__global__ __launch_bounds__(TRX_BLOCK) void ami_grad_grids_kernel(trx_volumes vol, trx_moving_grid mg, const float *__restrict__ theta, unsigned N, int K,
+                                                                     const float *__restrict__ range, const float *__restrict__ G, float *__restrict__ partials,
+                                                                     const unsigned char *__restrict__ mask)
+{
+    constexpr int NT = ND * (ND + 1);
+    extern __shared__ float ami_g[];                // [K][K]
+    const int b = blockIdx.y, tid = threadIdx.x, KK = K * K;
+    for (int i = tid; i < KK; i += TRX_BLOCK) ami_g[i] = G[(size_t)b * KK + i];
+    __syncthreads();
+    const MiScale m = mi_scale(range, b, K);
+    float te[NT];
+    ami_theta_eff<ND>(theta + (size_t)b * TRX_PSTRIDE, mg, te);
+    trx_volumes mvol = vol;
+    mvol.D = mg.D; mvol.H = mg.H; mvol.W = mg.W;
+    const float *__restrict__ mov = vol.moving + (size_t)b * vol.moving_stride;
+    const float *__restrict__ tgt = vol.target + (size_t)b * vol.target_stride;
+    float vals[NT];
+#pragma unroll
+    for (int k = 0; k < NT; k++) vals[k] = 0.f;
+    const unsigned char *mk = MASKED ? mask + (size_t)b * N : nullptr;
+    const unsigned first = blockIdx.x * (unsigned)kMiChunk, last = min(N, first + (unsigned)kMiChunk);
+    for (VoxelWalk vw(first + tid, TRX_BLOCK, vol.H, vol.W); vw.i < last; vw.next(vol.H, vol.W)) {
+        if (!mi_counts<MASKED>(mk, vw.i)) continue;
+        const float xn = base_coord(vol.xn, vw.x, vol.W), yn = base_coord(vol.yn, vw.y, vol.H), zn = ND == 3 ? base_coord(vol.zn, vw.z, vol.D) : 0.f;
+        const AmiSample<ND> s = ami_sample<ND>(mvol, te, mov, vw.x, vw.y, vw.z, xn, yn, zn);
+        const float gw = mi_voxel_grad(ami_g, mi_voxel(__builtin_nontemporal_load(tgt + vw.i), s.v, m, K), K);
+#pragma unroll
+        for (int c = 0; c < ND; c++) {
+            const float q = gw * s.d[c];
+            float *row = vals + c * (ND + 1);
+            row[0] = fmaf(xn, q, row[0]);
+            row[1] = fmaf(yn, q, row[1]);
+            if constexpr (ND == 3) row[2] = fmaf(zn, q, row[2]);
+            row[ND] += q;
+        }
+    }
+    ami_block_sum_store<NT>(vals, partials + ((size_t)b * gridDim.x + blockIdx.x) * NT);
+}
+
 // The loop's epilogue, one block per pair: the pair's partial rows -> dL/dtheta, the loss of the table kernel, then the affine step's epilogue
 // (records, pose chain rule, optimiser, theta of the next forward); the pair's counts are zeroed for the next iteration's pass 1.
-template <int ND>
-__global__ __launch_bounds__(TRX_FIN_THREADS) void ami_update_kernel(const float *__restrict__ partials, int nblk, const float *__restrict__ loss, int D, int H, int W,
-                                                                     trx_opt_cfg oc, trx_affine_state st, unsigned long long *__restrict__ counts, int KK)
+// D, H, W: the sizes the sampler un-normalised with (the S / 2 per row of theta) - the moving lattice's in a cross-lattice run (XL), where the state's theta
+// is the unscaled one and lane i's dL/dtheta_i = dL/dtheta_eff_i * gscale[i], formed in fp64 in front of the epilogue (gscale == 1: the same bits).
+template <int ND, bool XL>
+__device__ __forceinline__ void ami_update_body(const float *__restrict__ partials, int nblk, const float *__restrict__ loss, int D, int H, int W, const trx_opt_cfg &oc,
+                                                const trx_affine_state &st, unsigned long long *__restrict__ counts, int KK, const float *gscale)
 {
     constexpr int NT = ND * (ND + 1);
     constexpr int NPOSE = (ND == 3) ? 6 : 3;
@@ -192,11 +281,76 @@ __global__ __launch_bounds__(TRX_FIN_THREADS) void ami_update_kernel(const float
     const int ic = min(i, NT - 1);
     double bc1, rsbc2;
     fin_bias(oc, r.t, bc1, rsbc2);
-    fin_update<ND>((double)lossf, scale[ic / (ND + 1)] * S[ic], bc1, rsbc2, r, b, i, oc, st, param, theta, am, av, st.step + b, true, nullptr, sh_dth, sh_pose);
+    double row_scale = scale[ic / (ND + 1)];
+    if constexpr (XL) {
+        float gs = 1.f;
+#pragma unroll
+        for (int k = 0; k < NT; k++) gs = (k == ic) ? gscale[k] : gs;      // (selects: a lane-indexed read of a kernel argument would go through scratch)
+        row_scale *= (double)gs;
+    }
+    fin_update<ND>((double)lossf, row_scale * S[ic], bc1, rsbc2, r, b, i, oc, st, param, theta, am, av, st.step + b, true, nullptr, sh_dth, sh_pose);
+}
+template <int ND>
+__global__ __launch_bounds__(TRX_FIN_THREADS) void ami_update_kernel(const float *__restrict__ partials, int nblk, const float *__restrict__ loss, int D, int H, int W,
+                                                                     trx_opt_cfg oc, trx_affine_state st, unsigned long long *__restrict__ counts, int KK)
+{
+    ami_update_body<ND, false>(partials, nblk, loss, D, H, W, oc, st, counts, KK, nullptr);
+}
+template <int ND>
+__global__ __launch_bounds__(TRX_FIN_THREADS) void ami_update_grids_kernel(const float *__restrict__ partials, int nblk, const float *__restrict__ loss, trx_moving_grid mg,
+                                                                           trx_opt_cfg oc, trx_affine_state st, unsigned long long *__restrict__ counts, int KK)
+{
+    ami_update_body<ND, true>(partials, nblk, loss, mg.D, mg.H, mg.W, oc, st, counts, KK, mg.scale);
 }
 
-// pass 1 -> table -> (need_grad) pass 2 of one evaluation at `theta`; the counts must be zero
-static int ami_evaluate(const trx_volumes *vol, const trx_mi_cfg *cfg, const AmiGeom &g, const float *theta, float *loss, bool need_grad, void *workspace, hipStream_t s)
+// Behind one cross-lattice evaluation: launch_bwd_finalize's reduction (reduce_partials' fixed order) with the moving sizes in S / 2 and the scales on top,
+// dtheta[k] = (S_row / 2 * scale[k]) * sum - one rounding to fp32, as there.
+template <int ND>
+__global__ __launch_bounds__(TRX_FIN_THREADS) void ami_grids_finalize_kernel(const float *__restrict__ partials, int nblk, trx_moving_grid mg, float *__restrict__ dtheta)
+{
+    constexpr int NT = ND * (ND + 1);
+    __shared__ double S[64];
+    const int b = blockIdx.x, i = threadIdx.x;
+    reduce_partials<NT>(partials + (size_t)b * nblk * NT, nblk, S);
+    if (i >= NT) return;
+    const double scale[3] = {0.5 * mg.W, 0.5 * mg.H, 0.5 * mg.D};
+    float gs = 1.f;
+#pragma unroll
+    for (int k = 0; k < NT; k++) gs = (k == i) ? mg.scale[k] : gs;
+    dtheta[(size_t)b * TRX_PSTRIDE + i] = (float)(scale[i / (ND + 1)] * (double)gs * S[i]);
+}
+
+// The cross-lattice forward warp (trx_affine_warp_grids): affine_warp_kernel's walk over the TARGET lattice (vol's sizes and tables), every channel sampled in
+// a moving volume of mg's sizes at theta_eff (formed once per block, as in the two passes).  chan_stride: moving voxels between channels.
+template <int ND>
+__global__ __launch_bounds__(TRX_BLOCK) void affine_warp_grids_kernel(trx_volumes vol, trx_moving_grid mg, const float *__restrict__ theta, int channels,
+                                                                      size_t chan_stride, float *__restrict__ out)
+{
+    const int b = blockIdx.y;
+    const int Dm = mg.D, Hm = mg.H, Wm = mg.W;
+    const size_t nvox = (size_t)vol.D * vol.H * vol.W;
+    const float *__restrict__ mov = vol.moving + (size_t)b * vol.moving_stride;
+    float *__restrict__ o = out + (size_t)b * channels * nvox;
+    float th[ND * (ND + 1)];
+    ami_theta_eff<ND>(theta + (size_t)b * TRX_PSTRIDE, mg, th);
+    for (VoxelWalk vw(blockIdx.x * TRX_BLOCK + threadIdx.x, gridDim.x * TRX_BLOCK, vol.H, vol.W); vw.i < nvox; vw.next(vol.H, vol.W)) {
+        const float xn = base_coord(vol.xn, vw.x, vol.W), yn = base_coord(vol.yn, vw.y, vol.H), zn = ND == 3 ? base_coord(vol.zn, vw.z, vol.D) : 0.f;
+        if constexpr (ND == 3) {
+            const float ix = unnorm<3>(fmaf(th[1], yn, fmaf(th[0], xn, fmaf(th[2], zn, th[3]))), (float)Wm);
+            const float iy = unnorm<3>(fmaf(th[5], yn, fmaf(th[4], xn, fmaf(th[6], zn, th[7]))), (float)Hm);
+            const float iz = unnorm<3>(fmaf(th[9], yn, fmaf(th[8], xn, fmaf(th[10], zn, th[11]))), (float)Dm);
+            for (int ch = 0; ch < channels; ch++) o[ch * nvox + vw.i] = sample3(mov + ch * chan_stride, Dm, Hm, Wm, ix, iy, iz).v;
+        } else {
+            const float ix = unnorm<2>(fmaf(th[1], yn, fmaf(th[0], xn, th[2])), (float)Wm);
+            const float iy = unnorm<2>(fmaf(th[4], yn, fmaf(th[3], xn, th[5])), (float)Hm);
+            for (int ch = 0; ch < channels; ch++) o[ch * nvox + vw.i] = sample2(mov + ch * chan_stride, Hm, Wm, ix, iy).v;
+        }
+    }
+}
+
+// pass 1 -> table -> (need_grad) pass 2 of one evaluation at `theta`; the counts must be zero.  mg != nullptr: the cross-lattice instances
+static int ami_evaluate(const trx_volumes *vol, const trx_moving_grid *mg, const trx_mi_cfg *cfg, const AmiGeom &g, const float *theta, float *loss, bool need_grad,
+                        void *workspace, hipStream_t s)
 {
     const int K = cfg->bins, T = mi_tables(K);
     unsigned long long *counts = (unsigned long long *)workspace;
@@ -206,29 +360,103 @@ static int ami_evaluate(const trx_volumes *vol, const trx_mi_cfg *cfg, const Ami
     const size_t lds = (size_t)T * K * K * sizeof(unsigned long long);
     with_ndim(vol->ndim, [&](auto nd) {
         constexpr int ND = decltype(nd)::value;
-        if (mask) hipLaunchKernelGGL((ami_hist_kernel<ND, true>), grid, block, lds, s, *vol, theta, g.N, K, T, cfg->range, counts, mask);
+        if (mg) {
+            if (mask) hipLaunchKernelGGL((ami_hist_grids_kernel<ND, true>), grid, block, lds, s, *vol, *mg, theta, g.N, K, T, cfg->range, counts, mask);
+            else hipLaunchKernelGGL((ami_hist_grids_kernel<ND, false>), grid, block, lds, s, *vol, *mg, theta, g.N, K, T, cfg->range, counts, mask);
+        } else if (mask) hipLaunchKernelGGL((ami_hist_kernel<ND, true>), grid, block, lds, s, *vol, theta, g.N, K, T, cfg->range, counts, mask);
         else hipLaunchKernelGGL((ami_hist_kernel<ND, false>), grid, block, lds, s, *vol, theta, g.N, K, T, cfg->range, counts, mask);
     });
     TRX_CHECK_LAUNCH();
     const int rc = launch_mi_table(counts, g.N, vol->B, cfg, loss, need_grad ? G : (float *)nullptr, s);
     if (rc != TRX_OK || !need_grad) return rc;
+    const size_t glds = (size_t)K * K * sizeof(float);
     with_ndim(vol->ndim, [&](auto nd) {
         constexpr int ND = decltype(nd)::value;
-        if (mask) hipLaunchKernelGGL((ami_grad_kernel<ND, true>), grid, block, (size_t)K * K * sizeof(float), s, *vol, theta, g.N, K, cfg->range, (const float *)G, partials, mask);
-        else hipLaunchKernelGGL((ami_grad_kernel<ND, false>), grid, block, (size_t)K * K * sizeof(float), s, *vol, theta, g.N, K, cfg->range, (const float *)G, partials, mask);
+        if (mg) {
+            if (mask) hipLaunchKernelGGL((ami_grad_grids_kernel<ND, true>), grid, block, glds, s, *vol, *mg, theta, g.N, K, cfg->range, (const float *)G, partials, mask);
+            else hipLaunchKernelGGL((ami_grad_grids_kernel<ND, false>), grid, block, glds, s, *vol, *mg, theta, g.N, K, cfg->range, (const float *)G, partials, mask);
+        } else if (mask) hipLaunchKernelGGL((ami_grad_kernel<ND, true>), grid, block, glds, s, *vol, theta, g.N, K, cfg->range, (const float *)G, partials, mask);
+        else hipLaunchKernelGGL((ami_grad_kernel<ND, false>), grid, block, glds, s, *vol, theta, g.N, K, cfg->range, (const float *)G, partials, mask);
     });
     TRX_CHECK_LAUNCH();
     return TRX_OK;
 }
 
-// what both entry points refuse, before any HIP call
-static int ami_check(const trx_volumes *vol, const trx_mi_cfg *cfg, const void *workspace, size_t workspace_bytes, AmiGeom *g)
+// what the cross-lattice entry points refuse on top of the others (ndim: 2 or 3, already checked)
+static int ami_grid_check(int ndim, const trx_moving_grid *mg)
 {
-    if (!vol || !cfg || !cfg->range || !workspace || !vol->moving || !vol->target) return TRX_ERR_ARG;
-    const int rc = ami_geom(vol, cfg->bins, g);
+    if (!mg) return TRX_ERR_ARG;
+    if (mg->D < 1 || mg->H < 1 || mg->W < 1 || (double)mg->D * mg->H * mg->W >= 2147483648.0) return TRX_ERR_ARG;
+    if (ndim == 2 && mg->D != 1) return TRX_ERR_NDIM;
+    for (int k = 0; k < ndim * (ndim + 1); k++) {
+        if (!std::isfinite(mg->scale[k])) return TRX_ERR_ARG;
+        if (k % (ndim + 1) < ndim && !(mg->scale[k] > 0.f)) return TRX_ERR_ARG;      // the matrix part: a ratio of extents
+    }
+    return TRX_OK;
+}
+
+// what the entry points refuse, before any HIP call (grids: a cross-lattice entry point, mg its moving lattice); the workspace size comes last
+static int ami_check(const trx_volumes *vol, const trx_moving_grid *mg, bool grids, const trx_mi_cfg *cfg, const void *workspace, size_t workspace_bytes, AmiGeom *g)
+{
+    if (!vol || !cfg || !cfg->range || !workspace || !vol->moving || !vol->target || (grids && !mg)) return TRX_ERR_ARG;
+    int rc = ami_geom(vol, cfg->bins, g);
+    if (rc == TRX_OK && grids) rc = ami_grid_check(vol->ndim, mg);
     if (rc != TRX_OK) return rc;
     if (!std::isfinite(cfg->alpha)) return TRX_ERR_ARG;
     if (workspace_bytes < g->ws_bytes) return TRX_ERR_WORKSPACE;
+    return TRX_OK;
+}
+
+// the entry points proper; mg == nullptr: one lattice, the launches of before
+static int ami_loss_grad(const trx_volumes *vol, const trx_moving_grid *mg, const trx_mi_cfg *cfg, const float *theta, float *loss, float *dtheta, void *workspace,
+                         size_t workspace_bytes, bool grids, void *stream)
+{
+    if (!theta || !loss) return TRX_ERR_ARG;
+    AmiGeom g;
+    int rc = ami_check(vol, mg, grids, cfg, workspace, workspace_bytes, &g);
+    if (rc != TRX_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(workspace, 0, (size_t)vol->B * cfg->bins * cfg->bins * sizeof(unsigned long long), s) != hipSuccess) return TRX_ERR_HIP;
+    rc = ami_evaluate(vol, mg, cfg, g, theta, loss, dtheta != nullptr, workspace, s);
+    if (rc != TRX_OK || !dtheta) return rc;
+    const float *partials = (const float *)((char *)workspace + g.o_part);
+    if (!mg) return launch_bwd_finalize(vol, partials, (int)g.nchunk, dtheta, s);
+    with_ndim(vol->ndim, [&](auto nd) {
+        hipLaunchKernelGGL((ami_grids_finalize_kernel<decltype(nd)::value>), dim3((unsigned)vol->B), dim3(TRX_FIN_THREADS), 0, s, partials, (int)g.nchunk, *mg, dtheta);
+    });
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
+
+static int ami_run(const trx_volumes *vol, const trx_moving_grid *mg, const trx_mi_cfg *cfg, const trx_opt_cfg *opt, const trx_affine_state *st, int iters,
+                   void *workspace, size_t workspace_bytes, bool grids, void *stream)
+{
+    if (iters < 0 || !st || !opt) return TRX_ERR_ARG;
+    if (st->losses && iters > st->losses_capacity) return TRX_ERR_CAPACITY;
+    AmiGeom g;
+    int rc = ami_check(vol, mg, grids, cfg, workspace, workspace_bytes, &g);
+    if (rc != TRX_OK) return rc;
+    if (!st->param || !st->theta || !st->best_theta || !st->best_loss || !st->best_idx || !st->step) return TRX_ERR_ARG;
+    if (opt->kind != TRX_OPT_SGD && opt->kind != TRX_OPT_ADAM) return TRX_ERR_ARG;
+    if (opt->kind == TRX_OPT_ADAM && (!st->adam_m || !st->adam_v)) return TRX_ERR_ARG;
+    if (st->mode != TRX_PARAM_AFFINE && st->mode != TRX_PARAM_RIGID) return TRX_ERR_ARG;
+    if (iters == 0) return TRX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const int KK = cfg->bins * cfg->bins;
+    unsigned long long *counts = (unsigned long long *)workspace;
+    float *loss = (float *)((char *)workspace + g.o_loss);
+    const float *partials = (const float *)((char *)workspace + g.o_part);
+    if (hipMemsetAsync(counts, 0, (size_t)vol->B * KK * sizeof(unsigned long long), s) != hipSuccess) return TRX_ERR_HIP;
+    for (int k = 0; k < iters; k++) {
+        const int r = ami_evaluate(vol, mg, cfg, g, st->theta, loss, true, workspace, s);
+        if (r != TRX_OK) return r;
+        with_ndim(vol->ndim, [&](auto nd) {
+            constexpr int ND = decltype(nd)::value;
+            if (mg) hipLaunchKernelGGL((ami_update_grids_kernel<ND>), dim3((unsigned)vol->B), dim3(TRX_FIN_THREADS), 0, s, partials, (int)g.nchunk, (const float *)loss, *mg, *opt, *st, counts, KK);
+            else hipLaunchKernelGGL((ami_update_kernel<ND>), dim3((unsigned)vol->B), dim3(TRX_FIN_THREADS), 0, s, partials, (int)g.nchunk, (const float *)loss, vol->D, vol->H, vol->W, *opt, *st, counts, KK);
+        });
+        TRX_CHECK_LAUNCH();
+    }
     return TRX_OK;
 }
 
@@ -246,44 +474,46 @@ extern "C" size_t trx_affine_mi_workspace_bytes(const trx_volumes *vol, int bins
 extern "C" int trx_affine_mi_loss_grad(const trx_volumes *vol, const trx_mi_cfg *cfg, const float *theta, float *loss, float *dtheta, void *workspace,
                                        size_t workspace_bytes, void *stream)
 {
-    if (!theta || !loss) return TRX_ERR_ARG;
-    AmiGeom g;
-    int rc = ami_check(vol, cfg, workspace, workspace_bytes, &g);
-    if (rc != TRX_OK) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(workspace, 0, (size_t)vol->B * cfg->bins * cfg->bins * sizeof(unsigned long long), s) != hipSuccess) return TRX_ERR_HIP;
-    rc = ami_evaluate(vol, cfg, g, theta, loss, dtheta != nullptr, workspace, s);
-    if (rc != TRX_OK || !dtheta) return rc;
-    return launch_bwd_finalize(vol, (const float *)((char *)workspace + g.o_part), (int)g.nchunk, dtheta, s);
+    return ami_loss_grad(vol, nullptr, cfg, theta, loss, dtheta, workspace, workspace_bytes, false, stream);
 }
 
 extern "C" int trx_affine_mi_run(const trx_volumes *vol, const trx_mi_cfg *cfg, const trx_opt_cfg *opt, const trx_affine_state *st, int iters, void *workspace,
                                  size_t workspace_bytes, void *stream)
 {
-    if (iters < 0 || !st || !opt) return TRX_ERR_ARG;
-    if (st->losses && iters > st->losses_capacity) return TRX_ERR_CAPACITY;
-    AmiGeom g;
-    const int rc = ami_check(vol, cfg, workspace, workspace_bytes, &g);
+    return ami_run(vol, nullptr, cfg, opt, st, iters, workspace, workspace_bytes, false, stream);
+}
+
+extern "C" int trx_affine_mi_loss_grad_grids(const trx_volumes *vol, const trx_moving_grid *mg, const trx_mi_cfg *cfg, const float *theta, float *loss, float *dtheta,
+                                             void *workspace, size_t workspace_bytes, void *stream)
+{
+    return ami_loss_grad(vol, mg, cfg, theta, loss, dtheta, workspace, workspace_bytes, true, stream);
+}
+
+extern "C" int trx_affine_mi_run_grids(const trx_volumes *vol, const trx_moving_grid *mg, const trx_mi_cfg *cfg, const trx_opt_cfg *opt, const trx_affine_state *st,
+                                       int iters, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return ami_run(vol, mg, cfg, opt, st, iters, workspace, workspace_bytes, true, stream);
+}
+
+extern "C" int trx_affine_warp_grids(const trx_volumes *vol, const trx_moving_grid *mg, const float *theta, int channels, float *out, void *stream)
+{
+    if (!mg) return TRX_ERR_ARG;
+    int rc = check_vol(vol, false);
+    if (rc == TRX_OK) rc = ami_grid_check(vol->ndim, mg);
     if (rc != TRX_OK) return rc;
-    if (!st->param || !st->theta || !st->best_theta || !st->best_loss || !st->best_idx || !st->step) return TRX_ERR_ARG;
-    if (opt->kind != TRX_OPT_SGD && opt->kind != TRX_OPT_ADAM) return TRX_ERR_ARG;
-    if (opt->kind == TRX_OPT_ADAM && (!st->adam_m || !st->adam_v)) return TRX_ERR_ARG;
-    if (st->mode != TRX_PARAM_AFFINE && st->mode != TRX_PARAM_RIGID) return TRX_ERR_ARG;
-    if (iters == 0) return TRX_OK;
+    if (!theta || !out || channels < 1) return TRX_ERR_ARG;
+    const int nt = vol->ndim * (vol->ndim + 1);
+    bool same = mg->D == vol->D && mg->H == vol->H && mg->W == vol->W;
+    for (int k = 0; k < nt; k++) same = same && mg->scale[k] == 1.0f;
+    if (same) return trx_affine_warp(vol, theta, channels, out, stream);      // one lattice: the warp of before (its tiled kernels in 3-D), the same bits
     hipStream_t s = (hipStream_t)stream;
-    const int KK = cfg->bins * cfg->bins;
-    unsigned long long *counts = (unsigned long long *)workspace;
-    float *loss = (float *)((char *)workspace + g.o_loss);
-    const float *partials = (const float *)((char *)workspace + g.o_part);
-    if (hipMemsetAsync(counts, 0, (size_t)vol->B * KK * sizeof(unsigned long long), s) != hipSuccess) return TRX_ERR_HIP;
-    for (int k = 0; k < iters; k++) {
-        const int r = ami_evaluate(vol, cfg, g, st->theta, loss, true, workspace, s);
-        if (r != TRX_OK) return r;
-        with_ndim(vol->ndim, [&](auto nd) {
-            hipLaunchKernelGGL((ami_update_kernel<decltype(nd)::value>), dim3((unsigned)vol->B), dim3(TRX_FIN_THREADS), 0, s, partials, (int)g.nchunk, (const float *)loss, vol->D,
-                               vol->H, vol->W, *opt, *st, counts, KK);
-        });
-        TRX_CHECK_LAUNCH();
-    }
+    const size_t nvox = (size_t)vol->D * vol->H * vol->W, nmov = (size_t)mg->D * mg->H * mg->W;
+    size_t nb = (nvox + TRX_BLOCK - 1) / TRX_BLOCK;
+    if (nb > 8192) nb = 8192;
+    const dim3 grid((unsigned)nb, (unsigned)vol->B), block(TRX_BLOCK);
+    with_ndim(vol->ndim, [&](auto nd) {
+        hipLaunchKernelGGL((affine_warp_grids_kernel<decltype(nd)::value>), grid, block, 0, s, *vol, *mg, theta, channels, nmov, out);
+    });
+    TRX_CHECK_LAUNCH();
     return TRX_OK;
 }

@@ -9,9 +9,9 @@ U-Net-generated flow, 'direct' = the flow field itself is the parameter), levels
 import torch
 from torch import cat
 
-from ._engine import _bending_weight, _mask_u8, _squarings
+from ._engine import _bending_weight, _mask_u8, _squarings, affine_warp, grid_scale
 from .pyramid import pyramid, pyramid_masks, pyramid_shapes, upsample_flow
-from .warpings import MASK_SUPPORT, affine_register, device_loop_settings, flow_register, get_affine_warp, rigid_register
+from .warpings import GRIDS_SUPPORT, MASK_SUPPORT, affine_register, device_loop_settings, flow_register, get_affine_warp, rigid_register, two_lattices
 
 
 def _per_level(value, levels, name):
@@ -119,6 +119,8 @@ class Register():
         self.final_pose = None      # mode='rigid' on the device paths: the pose [B,6] (3-D) / [B,3] (2-D) behind final_theta
         self.level_losses = None
         self.level_shapes = None
+        self.world_matrix = None    # device_loop with voxel sizes: [B,nd+1,nd+1], the best theta as moving_mm = M target_mm (rows / columns x, y(, z))
+        self.target_shape = None    # the spatial shape of the lattice optim registered onto: what reg(x) returns
 
     def _flow_kw(self, n, lr, max_epochs):
         kw = dict(mode='bilinear', n=n, lr=lr, max_epochs=max_epochs, optimizer=self.optimizer, smooth_weight=self.smooth_weight,
@@ -143,7 +145,24 @@ class Register():
             raise ValueError(MASK_SUPPORT)
         return _mask_u8(mask, target)
 
-    def optim(self, moving, target, lr=1E-5, max_epochs=1000, n=32, per=0.1, *, mask=None):
+    def _check_grids(self, moving, target, moving_voxel, target_voxel):
+        '''Differing spatial shapes / voxel sizes of optim: ValueError unless the loop is the fused mutual-information loop of mode 'rigid' /
+        'affine' (device_loop=True), before any device work.  Returns whether the pair takes the cross-lattice path.'''
+        if not two_lattices(moving, target, moving_voxel, target_voxel):
+            return False
+        if self.mode == 'flow' or not self.device_loop or moving.dim() != target.dim():
+            raise ValueError(GRIDS_SUPPORT)
+        grid_scale(moving.shape[2:], target.shape[2:], moving_voxel, target_voxel)      # exactly one voxel size, a non-positive one: ValueError
+        return True
+
+    def _set_grids(self, grids, target, info):
+        '''After a rigid / affine optim: the warp behind __call__ (two lattices: onto the target lattice, forward only) and the new attributes.'''
+        self.target_shape = tuple(target.shape[2:])
+        self.world_matrix = info.get('world_matrix')
+        size = self.target_shape
+        self.warp = (lambda theta, x: affine_warp(theta, x, size=size)) if grids else get_affine_warp
+
+    def optim(self, moving, target, lr=1E-5, max_epochs=1000, n=32, per=0.1, *, mask=None, moving_voxel=None, target_voxel=None):
         '''
         Optimisation loop: moving, target [1,1,x,y(,z)] float32 GPU tensors (a leading batch > 1 of
         independent pairs is an extension).  Sets self.theta (best theta [B,nd,nd+1], or the flow
@@ -157,11 +176,20 @@ class Register():
             device-side mutual-information loops: mode 'rigid' / 'affine' with device_loop=True, or mode 'flow' with flow_model 'direct' (3-D) or
             'bspline' and MILoss alone; ValueError anywhere else, before any device work.  With levels > 1 a level's mask is the float mask sent
             through the pyramid call of the target and thresholded at >= 0.5; a pair whose mask is empty at some level raises ValueError.
+        moving_voxel, target_voxel : (keyword-only extension) voxel sizes in mm, in the tensors' axis order (dz, dy, dx) / (dy, dx), both or
+            neither.  With them theta acts between the two volumes in millimetres (their centres coinciding, their axes aligned): mode='rigid' is
+            rigid in the world whatever the voxel sizes.  moving may also have a spatial shape of its own - a CT and an MR on their own grids.
+            Honoured by mode 'rigid' / 'affine' with device_loop=True; ValueError anywhere else, before any device work.  Then .theta /
+            .final_theta are the EFFECTIVE thetas - F.grid_sample(moving, F.affine_grid(reg.theta, target.shape), align_corners=False) is
+            reg(moving) -, reg(x) warps any [B,c,*moving spatial] onto the target lattice, .world_matrix is the best theta in mm (None without
+            voxel sizes), .target_shape the lattice, .final_pose keeps its meaning and mask= stays on the target lattice.  With levels > 1 each
+            image gets its own pyramid, so both fields of view and the scale are the same at every level; .level_shapes are the target's.
         '''
+        grids = self._check_grids(moving, target, moving_voxel, target_voxel)
         if mask is not None:
             mask = self._check_mask(mask, target)
         if self.levels > 1:
-            return self._optim_levels(moving, target, lr, max_epochs, n, per, mask)
+            return self._optim_levels(moving, target, lr, max_epochs, n, per, mask, moving_voxel, target_voxel)
         if self.mode == 'flow':
             flowreg = flow_register(target.shape[2:], **self._flow_kw(n, lr, max_epochs)).to(moving.device)
             flowreg.optimize(moving, target, self.device, self.debug, mask=mask)
@@ -183,22 +211,28 @@ class Register():
             kw.update(weights=self.weight)
         if mask is not None:
             kw.update(mask=mask)
+        if grids:
+            kw.update(moving_voxel=moving_voxel, target_voxel=target_voxel)
         _, theta = fn(moving, target, **kw)
         self.theta = theta[-1]                                                # best theta (Q8)
         self.final_theta = theta[0]
         self.losses = info.get('losses')
         self.best_idx = info.get('best_idx')
         self.final_pose = info.get('final_pose')
+        self._set_grids(grids, target, info)
 
-    def _optim_levels(self, moving, target, lr, max_epochs, n, per, mask=None):
+    def _optim_levels(self, moving, target, lr, max_epochs, n, per, mask=None, moving_voxel=None, target_voxel=None):
         '''Coarse-to-fine: the single-level machinery (flow_register / _affine_family) on each level of pyramid(moving) and
         pyramid(target), coarsest first; each level starts from the previous level's FINAL parameters (rigid: the pose, drawn by
         torch.rand for the coarsest level as a single-level run draws it; affine: theta; flow: upsample_flow of the flow).  Optimiser
-        state starts fresh at every level.  .theta / .warp / .losses / .best_idx / .final_theta are the finest level's.'''
+        state starts fresh at every level.  .theta / .warp / .losses / .best_idx / .final_theta are the finest level's.
+        Two lattices (rigid / affine, device_loop): moving and target each get their own pyramid, so a level halves both lattices and doubles both
+        voxel sizes - the half extents, and with them the scale, are the same at every level; the theta handed up is the unscaled one.'''
+        grids = two_lattices(moving, target, moving_voxel, target_voxel)      # (refused by optim unless the loop is the fused mutual-information one)
         L = self.levels
         lrs, epochs = _per_level(lr, L, 'lr'), _per_level(max_epochs, L, 'max_epochs')
         shapes = pyramid_shapes(target.shape[2:], L)
-        if tuple(moving.shape[2:]) != tuple(target.shape[2:]):
+        if tuple(moving.shape[2:]) != tuple(target.shape[2:]) and not grids:
             raise ValueError(f"moving {tuple(moving.shape)} and target {tuple(target.shape)} differ in spatial size")
         flow = self.mode == 'flow'
         movs, tgts = pyramid(moving, L, align_corners=flow), pyramid(target, L, align_corners=flow)
@@ -230,11 +264,17 @@ class Register():
                     kw.update(weights=self.weight)
                 if masks[k] is not None:
                     kw.update(mask=masks[k])
+                if grids:
+                    # align_corners=False keeps an image's field of view: a level's voxel is the full one times (full size / level size), per axis
+                    lvl = lambda voxel, full, x: None if voxel is None else tuple(v * s / sl for v, s, sl in zip(voxel, full.shape[2:], x.shape[2:]))  # noqa: E731
+                    kw.update(moving_voxel=lvl(moving_voxel, moving, movs[k]), target_voxel=lvl(target_voxel, target, tgts[k]))
                 _, theta = fn(movs[k], tgts[k], **kw)
-                init = info['final_pose'] if self.mode == 'rigid' else theta[0]
+                # (a level whose two shapes happen to coincide, without voxel sizes, is a one-lattice run: its theta is unscaled as it is)
+                init = info['final_pose'] if self.mode == 'rigid' else info.get('final_unscaled_theta', theta[0])
                 self.theta, self.final_theta = theta[-1], theta[0]
                 self.losses, self.best_idx = info.get('losses'), info.get('best_idx')
                 self.final_pose = info.get('final_pose')
+                self._set_grids(grids, tgts[k], info)
             self.level_losses.append(self.losses)
             if self.debug:
                 ls = self.losses.detach().flatten().cpu()

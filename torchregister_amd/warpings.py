@@ -284,6 +284,16 @@ MASK_SUPPORT = ("mask is the region of interest of the device-side mutual-inform
                 "the other criteria and loops have no mask")
 
 
+GRIDS_SUPPORT = ("a moving image on a lattice of its own (another spatial shape) and voxel sizes (moving_voxel=, target_voxel=) are honoured by the "
+                 "fused mutual-information loop: mode='rigid' / 'affine' with device_loop=True and criterion=[MILoss()]; for the other criteria and "
+                 "loops resample moving onto the target lattice first (reg(moving) of such a registration does it)")
+
+
+def two_lattices(moving, target, moving_voxel=None, target_voxel=None):
+    """Whether the pair asks for the cross-lattice path: differing spatial shapes or any voxel size.  Looks at shapes only."""
+    return moving_voxel is not None or target_voxel is not None or tuple(moving.shape[2:]) != tuple(target.shape[2:])
+
+
 def device_loop_settings(criterions, weights):
     """device_loop=True (rigid / affine): the criterion list must be exactly one MILoss with a non-zero weight - returns its settings dict
     (MILoss.settings(weight)), raises ValueError for anything else.  Looks at the list only, never at a tensor."""
@@ -296,8 +306,15 @@ def device_loop_settings(criterions, weights):
 
 
 def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, weights, grad_edges, honor_criterion,
-                   optimizer, init, info, device_loop=False, mask=None):
+                   optimizer, init, info, device_loop=False, mask=None, moving_voxel=None, target_voxel=None):
     mi = device_loop_settings(criterions, weights) if device_loop else None      # (before anything else: a refused list touches no tensor)
+    grids = two_lattices(moving, target, moving_voxel, target_voxel)
+    if grids:
+        if mi is None:
+            raise ValueError(GRIDS_SUPPORT)
+        if moving.dim() != target.dim():
+            raise ValueError(f"moving {tuple(moving.shape)} and target {tuple(target.shape)} differ in their number of dimensions")
+        _engine.grid_scale(moving.shape[2:], target.shape[2:], moving_voxel, target_voxel)      # its ValueErrors, before any device work
     if mask is not None:
         if mi is None:
             raise ValueError(MASK_SUPPORT)
@@ -316,14 +333,24 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
         # once to (target, moving); a batch is B independent pairs, each with its own parameters - the same returns as the fused branch below
         B = moving.shape[0]
         init_b = None if init is None else (init.reshape(-1, npose).expand(B, -1) if mode == "rigid" else init.reshape(-1, nd, nd + 1).expand(B, nd, nd + 1))
-        solver = AffineMISolver(moving, target, mode=mode, mi=mi, optimizer=optimizer, lr=lr, init=init_b, capacity=max(1, epochs), mask=mask)
+        solver = AffineMISolver(moving, target, mode=mode, mi=mi, optimizer=optimizer, lr=lr, init=init_b, capacity=max(1, epochs), mask=mask,
+                                moving_voxel=moving_voxel, target_voxel=target_voxel)
         solver.run(epochs)
         final_theta, best_theta = solver.current_theta, solver.best
         if epochs == 0:
             best_theta = final_theta.clone()
-        warped = [get_affine_warp(final_theta, moving), get_affine_warp(best_theta, moving)]
+        if grids:
+            # two lattices: the thetas handed out are the EFFECTIVE ones - grid_sample(moving, affine_grid(theta, target.shape)) is the warp - and
+            # the warps land on the target lattice; the unscaled theta of the last forward goes along for a coarse-to-fine hand-over
+            final_unscaled, world = final_theta, solver.world_matrix(best_theta)
+            final_theta, best_theta = solver.effective(final_theta), solver.effective(best_theta)
+            warped = [_engine.affine_warp(t, moving, size=target.shape[2:]) for t in (final_theta, best_theta)]
+        else:
+            warped = [get_affine_warp(final_theta, moving), get_affine_warp(best_theta, moving)]
         theta = [final_theta, best_theta]
         res = dict(losses=solver.losses[:, :epochs], final_theta=final_theta, best_theta=best_theta, best_idx=solver.best_idx, solver=solver)
+        if grids:
+            res.update(final_unscaled_theta=final_unscaled, world_matrix=world)
         if mode == "rigid":
             res["final_pose"] = solver.param[:, :npose].clone()
     elif spec is None:
@@ -355,7 +382,7 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
 
 def affine_register(moving, target, lr=1E-5, epochs=1000, per=0.1, device="cpu", debug=True, criterions=None,
                     weights=[0.33, 0.33, 0.33], grad_edges=True, *, honor_criterion=False, optimizer="sgd", init=None, info=None,
-                    device_loop=False, mask=None):
+                    device_loop=False, mask=None, moving_voxel=None, target_voxel=None):
     """ref:warpings.py:30-113.  Returns ([final_warped, best_warped], [final_theta, best_theta]).
 
     NOTE: like the reference, grad_edges defaults to True here when called directly (and then
@@ -364,17 +391,23 @@ def affine_register(moving, target, lr=1E-5, epochs=1000, per=0.1, device="cpu",
     otherwise) and the whole loop runs on the device in trx_affine_mi_run (AffineMISolver): honor_criterion is implied, the pairs of a batch are
     independent, info gets the keys of the fused MSE / NCC / SSD branch.  The default False changes no existing route.
     mask (keyword-only extension, with device_loop=True only; ValueError otherwise, before any device work; also on rigid_register): a region of
-    interest on the target lattice, [B,1,*spatial] or [B,*spatial], non-zero = the voxel counts - only those voxels enter the mutual information."""
+    interest on the target lattice, [B,1,*spatial] or [B,*spatial], non-zero = the voxel counts - only those voxels enter the mutual information.
+    moving_voxel, target_voxel (keyword-only extension, with device_loop=True only; also on rigid_register): voxel sizes in mm in the tensors' axis
+    order, (dz, dy, dx) / (dy, dx), both or neither; moving may then also have a spatial shape of its own.  theta acts between the two volumes in
+    millimetres (centres coinciding, axes aligned; _engine.grid_scale), the returned thetas are the effective ones of F.affine_grid(theta,
+    target.shape), the returned warps lie on the target lattice, and info gains world_matrix (best theta, mm) and final_unscaled_theta.  Differing
+    shapes or voxel sizes anywhere else: ValueError(GRIDS_SUPPORT) before any device work."""
     return _affine_family("affine", moving, target, lr, epochs, device, debug, criterions, weights, grad_edges,
-                          honor_criterion, optimizer, init, info, device_loop, mask)
+                          honor_criterion, optimizer, init, info, device_loop, mask, moving_voxel, target_voxel)
 
 
 def rigid_register(moving, target, lr=1E-5, epochs=1000, per=0.1, device="cpu", debug=True, criterions=None,
                    weights=[0.33, 0.33, 0.33], grad_edges=True, *, honor_criterion=False, optimizer="sgd", init=None, info=None,
-                   device_loop=False, mask=None):
-    """ref:warpings.py:117-174.  `init` = initial pose (default torch.rand on the tensors' device)."""
+                   device_loop=False, mask=None, moving_voxel=None, target_voxel=None):
+    """ref:warpings.py:117-174.  `init` = initial pose (default torch.rand on the tensors' device).  moving_voxel / target_voxel: see
+    affine_register - with them Theta(pose) is a rigid motion in millimetres whatever the voxel sizes."""
     return _affine_family("rigid", moving, target, lr, epochs, device, debug, criterions, weights, grad_edges,
-                          honor_criterion, optimizer, init, info, device_loop, mask)
+                          honor_criterion, optimizer, init, info, device_loop, mask, moving_voxel, target_voxel)
 
 
 class _FlowLossFn(torch.autograd.Function):
