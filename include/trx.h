@@ -55,7 +55,9 @@ extern "C" {
  *        mutual-information entry point; NULL = every voxel, the launches and bits of before) - no entry point changed its signature.
  *        Later addition under the same number: trx_moving_grid, trx_affine_mi_loss_grad_grids, trx_affine_mi_run_grids, trx_affine_warp_grids (rigid /
  *        affine mutual information and the forward warp for a moving image on a lattice and voxel size of its own) - new entry points and one new
- *        struct only. */
+ *        struct only.
+ *        Later addition under the same number: trx_affine_flow_warp, trx_affine_flow_warp_backward, trx_bspline_mi_run_grids (a flow composed with an
+ *        initial affine and sampled once in a moving image on its own lattice; the B-spline mutual-information loop over it) - new entry points only. */
 #define TRX_VERSION 240
 #define TRX_PSTRIDE 12  /* floats per pair in theta / param / adam / best_theta arrays */
 
@@ -625,6 +627,38 @@ int trx_affine_mi_run_grids(const trx_volumes *vol, const trx_moving_grid *mg /*
  * layout: vol->moving_stride between batch items).  vol->target is not read.  Equal sizes and scale == 1: trx_affine_warp itself, the same bits.  No
  * backward and no nearest-neighbour form. */
 int trx_affine_warp_grids(const trx_volumes *vol, const trx_moving_grid *mg /*[host]*/, const float *theta, int channels, float *out, void *stream);
+
+/* ---- A deformation composed with an initial affine, sampled ONCE (what elastix, NiftyReg and ANTs do with the transform of the
+ * stage before).  Extension.  Later addition under TRX_VERSION 240.  vol describes the TARGET lattice S_t = (D, H, W); vol->moving holds
+ * [B][channels][mg->D][mg->H][mg->W] with vol->moving_stride moving elements between batch items (trx_affine_warp_grids' layout); theta [B][TRX_PSTRIDE],
+ * theta_eff[k] = theta[k] * mg->scale[k] (one fp32 multiply); flow [B][ndim][*S_t] in TARGET voxels, channel i along spatial dim i (trx_flow_warp's
+ * convention).  For target voxel x:
+ *   p   = x + flow(x)                        one fp32 add per axis, as trx_flow_warp
+ *   n_c = (2 p_c + 1) / S_t,c - 1            closed form (xn / yn / zn are not used: p is not an integer)
+ *   m   = theta_eff . (n_x, n_y, n_z, 1)     theta's row order x, y, z
+ *   i_r = ((m_r + 1) S_m,r - 1) / 2          with the MOVING sizes
+ *   out = bi- / trilinear sample of moving at i, zero padding
+ * = grid_sample(moving, composed grid, align_corners=False).  flow == 0: trx_affine_warp_grids on closed-form coordinates; theta_eff = I on equal
+ * lattices: trx_flow_warp up to the rounding of the coordinate's round trip through the normalised cube.
+ * Backward: dflow_c(x) = sum_ch grad_out_ch(x) sum_r (dsample_ch / di_r) (S_m,r / 2) theta_eff[r][c] (2 / S_t,c), c converted between the flow's
+ * z, y, x channel order and theta's x, y, z column order.  A gather per target voxel like the forward: no scatter, no atomics, no workspace, the same
+ * bits on every call.  No gradient with respect to theta or the moving image, and no nearest-neighbour form.  vol->target is not read.  2-D and 3-D.
+ * Per voxel in 3-D the forward moves 12 B flow + 4 B out per channel + the gather, the backward 12 B flow + 4 B grad_out per channel + 12 B dflow +
+ * the gather.  Refusals before any HIP call: those of trx_flow_warp / trx_flow_warp_backward, those of trx_moving_grid above, theta NULL, channels < 1.
+ * CPU restatement: tests/affine_flow_ref.py. */
+int trx_affine_flow_warp(const trx_volumes *vol, const trx_moving_grid *mg /*[host]*/, const float *theta, const float *flow, int channels,
+                         float *out /*[B][channels][*S_t]*/, void *stream);
+int trx_affine_flow_warp_backward(const trx_volumes *vol, const trx_moving_grid *mg /*[host]*/, const float *theta, const float *flow, int channels,
+                                  const float *grad_out, float *dflow /*[B][ndim][*S_t]*/, void *stream);
+/* trx_bspline_mi_run with the two composed kernels where trx_flow_warp / trx_flow_warp_backward stand: the deformable stage behind a rigid / affine one,
+ * the moving image on its own lattice and never resampled in between.  The same loop (expand, trx_mi_loss_grad, reduce, bending, decide, update are the
+ * existing launches) and the same workspace: trx_bspline_mi_workspace_bytes is the query, it depends on the target lattice alone.  cfg->mask,
+ * bending_weight, base, stop_crit and flow_last keep their meaning; st->flow / ctrl are on the target lattice, in target voxels.  theta
+ * [B][TRX_PSTRIDE] is read on the device on every iteration and never written.  Refusals before any HIP call: trx_bspline_mi_run's, trx_moving_grid's,
+ * theta NULL.  Arbiter: tests/affine_flow_ref.py (bspline_ref.expand + the composed warp + mi_ref / mi_mask_ref under torch autograd and torch.optim). */
+int trx_bspline_mi_run_grids(const trx_volumes *vol, const trx_moving_grid *mg /*[host]*/, const float *theta, const trx_mi_cfg *cfg,
+                             const trx_opt_cfg *opt, const trx_bspline_state *st, const int *spacing /*[host]*/, int iters, void *workspace,
+                             size_t workspace_bytes, void *stream);
 
 /* ---- Stationary velocity field (Arsigny et al. 2006; NiftyReg's -vel, VoxelMorph-diff's VecInt; extension: the reference has no such model, its flows
  * are displacements, ref:warpings.py:178-242).  Fields are [B][ndim][D][H][W] fp32 contiguous (2-D: [B][2][H][W], D = 1), voxel units and channel order

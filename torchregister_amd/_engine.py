@@ -629,10 +629,19 @@ class BSplineSolver:
     squarings = None: the above, launch for launch.  squarings = K (an int in 0 .. 12): diffeomorphic - base + expand(ctrl) is a stationary
     VELOCITY, the deformation is its exponential (svf_exp, K squarings) and the loop runs in trx_bspline_svf_run.  Then `velocity` is the
     expanded lattice (+ base), `flow` = svf_exp(velocity), `flow_last` the exponential of the last forward's velocity (`velocity_last`),
-    inverse_flow() = svf_exp(velocity, inverse=True); `base` is a velocity.  Not with `mi`."""
+    inverse_flow() = svf_exp(velocity, inverse=True); `base` is a velocity.  Not with `mi`.
+    initial (with mi only, not with squarings; ValueError otherwise) = an affine theta [B,nd,nd+1] the deformation is composed with: the warp of
+    the loop is affine_flow_warp(moving, initial, flow, initial_scale) and the loop runs in trx_bspline_mi_run_grids.  `moving` may then have a
+    spatial shape of its own; ctrl, flow and mask stay on the target lattice, in target voxels; initial_scale [nd,nd+1] (grid_scale; None = ones:
+    `initial` is the effective theta).  theta is read on the device on every iteration (kept as `.initial`) and never written."""
 
     def __init__(self, moving, target, spacing, loss=None, optimizer="sgd", lr=1e-3, init=None, base=None, capacity=1000, stop_crit=None,
-                 keep_last=False, betas=(0.9, 0.999), eps=1e-8, bending_weight=0.0, mi=None, squarings=None, mask=None):
+                 keep_last=False, betas=(0.9, 0.999), eps=1e-8, bending_weight=0.0, mi=None, squarings=None, mask=None, initial=None,
+                 initial_scale=None):
+        if initial is not None and (mi is None or squarings is not None):
+            raise ValueError("initial (an affine composed into the deformation) runs the mutual-information loop only: give it with `mi` and without `squarings`")
+        if initial is None and initial_scale is not None:
+            raise ValueError("initial_scale is the scale of `initial`: give it with `initial`")
         if mask is not None:
             if mi is None:
                 raise ValueError("mask is the region of interest of the mutual-information data term: give it with `mi`")
@@ -647,10 +656,13 @@ class BSplineSolver:
             raise ValueError("mi is a data term of its own: give it without `loss`")
         self.lib = _lib.load()
         self.bending_weight = _bending_weight(bending_weight)
-        self.batch = _Batch(moving, target, tables=False)
+        self.batch = _Batch(moving, target, tables=False) if initial is None else _GridPair(moving, target, scale=initial_scale)
         if self.batch.C != 1:
             raise ValueError("the optimiser path takes single-channel volumes [B,1,...]")
         b, nd, dev = self.batch.B, self.batch.nd, self.batch.device
+        self.initial = self.moving_grid = None
+        if initial is not None:
+            self.initial, self.moving_grid = _initial_theta(initial, b, nd, dev), self.batch.grid()
         self.nd = nd
         self.spacing = _spacing3(spacing, nd)[3 - nd:]
         self.sp3 = (ctypes.c_int * 3)(*_spacing3(spacing, nd))
@@ -744,13 +756,18 @@ class BSplineSolver:
                 rc = self.lib.trx_bspline_svf_run(ctypes.byref(self.vol), ctypes.byref(self.loss_c), ctypes.byref(self.opt), ctypes.byref(self.state),
                                                   self.sp3, self.squarings, iters, _lib.ptr(self.workspace), self.ws_bytes,
                                                   _lib.current_stream(self.batch.device))
+            elif self.initial is not None:
+                rc = self.lib.trx_bspline_mi_run_grids(ctypes.byref(self.vol), ctypes.byref(self.moving_grid), _lib.ptr(self.initial), ctypes.byref(self.mi),
+                                                       ctypes.byref(self.opt), ctypes.byref(self.state), self.sp3, iters, _lib.ptr(self.workspace),
+                                                       self.ws_bytes, _lib.current_stream(self.batch.device))
             elif self.mi is not None:
                 rc = self.lib.trx_bspline_mi_run(ctypes.byref(self.vol), ctypes.byref(self.mi), ctypes.byref(self.opt), ctypes.byref(self.state),
                                                  self.sp3, iters, _lib.ptr(self.workspace), self.ws_bytes, _lib.current_stream(self.batch.device))
             else:
                 rc = self.lib.trx_bspline_run(ctypes.byref(self.vol), ctypes.byref(self.loss_c), ctypes.byref(self.opt), ctypes.byref(self.state),
                                               self.sp3, iters, _lib.ptr(self.workspace), self.ws_bytes, _lib.current_stream(self.batch.device))
-        _lib.check(rc, "trx_bspline_svf_run" if self.squarings is not None else "trx_bspline_mi_run" if self.mi is not None else "trx_bspline_run")
+        _lib.check(rc, "trx_bspline_svf_run" if self.squarings is not None else "trx_bspline_mi_run_grids" if self.initial is not None else
+                   "trx_bspline_mi_run" if self.mi is not None else "trx_bspline_run")
         self._expand()
 
 
@@ -1579,6 +1596,90 @@ def _affine_warp_grids(lib, theta, moving, size):
         rc = lib.trx_affine_warp_grids(ctypes.byref(v), ctypes.byref(mg), _lib.ptr(th), C, _lib.ptr(out), _lib.current_stream(dev))
     _lib.check(rc, "trx_affine_warp_grids")
     return out
+
+
+def _initial_theta(theta, B, nd, device=None):
+    """An initial affine for the composed warp: [B,nd,nd+1] (or one [nd,nd+1] / [1,nd,nd+1] for every pair) -> [B, PSTRIDE] fp32 (on `device`)."""
+    if not isinstance(theta, torch.Tensor) or theta.numel() % (nd * (nd + 1)) != 0 or theta.numel() // (nd * (nd + 1)) not in (1, B) or \
+            tuple(theta.shape[-2:]) != (nd, nd + 1):
+        raise ValueError(f"expected an initial theta of shape {(B, nd, nd + 1)}, got {tuple(theta.shape) if isinstance(theta, torch.Tensor) else type(theta).__name__}")
+    th = theta.detach().reshape(-1, nd, nd + 1).expand(B, nd, nd + 1)
+    return pad_theta(th if device is None else th.to(device), nd)
+
+
+def _affine_flow_call(x, theta, flow, scale):
+    """The arguments the two composed-warp entry points share: (Volumes of the TARGET lattice = flow's, MovingGrid, theta [B,PSTRIDE], flow, x), all
+    contiguous and kept alive by the caller."""
+    _require_gpu(x, "x")
+    _require_gpu(flow, "flow")
+    if x.dim() not in (4, 5) or flow.dim() != x.dim():
+        raise ValueError(f"expected x [B,C,*moving spatial] and flow [B,nd,*target spatial] of 2 or 3 spatial dims, got {tuple(x.shape)} and {tuple(flow.shape)}")
+    nd, B = x.dim() - 2, x.shape[0]
+    if flow.shape[0] != B or flow.shape[1] != nd:
+        raise ValueError(f"flow shape {tuple(flow.shape)} is not [{B},{nd},*target spatial]")
+    mov, fl = x.contiguous(), flow.detach().contiguous()
+    th = _initial_theta(theta, B, nd, x.device)
+    if scale is not None:
+        scale = torch.as_tensor(scale).detach().to("cpu", torch.float32)
+        if tuple(scale.shape) != (nd, nd + 1):
+            raise ValueError(f"expected a scale of shape {(nd, nd + 1)}, got {tuple(scale.shape)}")
+    v = _lib.Volumes()
+    v.moving, v.target = mov.data_ptr(), None
+    v.moving_stride, v.target_stride = mov[0].numel(), 0
+    v.ndim, v.B = nd, B
+    v.D, v.H, v.W = _dhw(fl.shape[2:])
+    v.flags = 0
+    v.xn = v.yn = v.zn = None      # the composed position is not an integer: the closed form, never the tables
+    return v, _moving_grid(tuple(mov.shape[2:]), scale), th, fl, mov
+
+
+def _affine_flow_forward(x, theta, flow, scale):
+    lib = _lib.load()
+    v, mg, th, fl, mov = _affine_flow_call(x, theta, flow, scale)
+    out = torch.empty((mov.shape[0], mov.shape[1]) + tuple(fl.shape[2:]), dtype=torch.float32, device=mov.device)
+    with torch.cuda.device(mov.device):
+        rc = lib.trx_affine_flow_warp(ctypes.byref(v), ctypes.byref(mg), _lib.ptr(th), _lib.ptr(fl), mov.shape[1], _lib.ptr(out), _lib.current_stream(mov.device))
+    _lib.check(rc, "trx_affine_flow_warp")
+    return out
+
+
+def affine_flow_warp_backward(x, theta, flow, grad_out, scale=None):
+    """dL/dflow [B,nd,*target spatial] of affine_flow_warp for dL/dout = grad_out [B,C,*target spatial] (trx_affine_flow_warp_backward): a gather per
+    target voxel, the same bits on every call.  No gradient with respect to theta or x."""
+    lib = _lib.load()
+    v, mg, th, fl, mov = _affine_flow_call(x, theta, flow, scale)
+    _require_gpu(grad_out, "grad_out")
+    if tuple(grad_out.shape) != (mov.shape[0], mov.shape[1]) + tuple(fl.shape[2:]):
+        raise ValueError(f"grad_out shape {tuple(grad_out.shape)} is not the warp's {(mov.shape[0], mov.shape[1]) + tuple(fl.shape[2:])}")
+    go = grad_out.detach().contiguous()
+    dfl = torch.empty_like(fl)
+    with torch.cuda.device(mov.device):
+        rc = lib.trx_affine_flow_warp_backward(ctypes.byref(v), ctypes.byref(mg), _lib.ptr(th), _lib.ptr(fl), mov.shape[1], _lib.ptr(go), _lib.ptr(dfl),
+                                               _lib.current_stream(mov.device))
+    _lib.check(rc, "trx_affine_flow_warp_backward")
+    return dfl
+
+
+class _AffineFlowWarpFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, theta, flow, scale):
+        ctx.save_for_backward(x, theta, flow)
+        ctx.scale = scale
+        return _affine_flow_forward(x, theta, flow, scale)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, theta, flow = ctx.saved_tensors
+        dflow = affine_flow_warp_backward(x, theta, flow, grad_out, ctx.scale) if ctx.needs_input_grad[2] else None
+        return None, None, dflow, None      # no gradient flows to the moving image or to theta on this path
+
+
+def affine_flow_warp(x, theta, flow, scale=None):
+    """A deformation composed with an initial affine, sampled once (extension, include/trx.h: trx_affine_flow_warp): x [B,C,*moving spatial], theta
+    [B,nd,nd+1], flow [B,nd,*target spatial] in target voxels (channel i along spatial dim i), scale [nd,nd+1] (grid_scale; None = ones:
+    theta is the effective one) -> [B,C,*target spatial] = grid_sample(x, theta_eff applied to the normalised positions voxel + flow,
+    align_corners=False).  Differentiable with respect to flow (trx_affine_flow_warp_backward)."""
+    return _AffineFlowWarpFn.apply(x, theta, flow, scale)
 
 
 def affine_mi_loss_grad(moving, target, theta, rng, bins=32, alpha=1.0, normalized=False, need_grad=True, mask=None, scale=None):

@@ -82,16 +82,7 @@ __device__ __forceinline__ AmiSample<ND> ami_sample(const trx_volumes &vol, cons
     return r;
 }
 
-// Two lattices (trx_moving_grid): the loop's voxels, the mask and the base coordinates stay on vol's (target) lattice, the sample is
-// taken in a moving volume of its own size at theta_eff = theta (.) scale.  theta_eff is formed here, once per block, from uniform values (theta's row
-// through scalar loads, the scales from the kernel arguments): the voxel loop sees ND (ND + 1) registers, as it does with one lattice.
-template <int ND>
-__device__ __forceinline__ void ami_theta_eff(const float *__restrict__ th, const trx_moving_grid &mg, float (&te)[ND * (ND + 1)])
-{
-#pragma unroll
-    for (int k = 0; k < ND * (ND + 1); k++)      // one fp32 rounding: (theta, scale) samples exactly where (fl(theta scale), 1) does; pinned to an SGPR like theta's own row
-        te[k] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(th[k] * mg.scale[k])));
-}
+// Two lattices (trx_moving_grid): theta_eff = theta (.) scale is formed once per block by ami_theta_eff (trx_common.h).
 
 // pass 1: warp and histogram
 template <int ND, bool MASKED>
@@ -382,19 +373,7 @@ static int ami_evaluate(const trx_volumes *vol, const trx_moving_grid *mg, const
     return TRX_OK;
 }
 
-// what the cross-lattice entry points refuse on top of the others (ndim: 2 or 3, already checked)
-static int ami_grid_check(int ndim, const trx_moving_grid *mg)
-{
-    if (!mg) return TRX_ERR_ARG;
-    if (mg->D < 1 || mg->H < 1 || mg->W < 1 || (double)mg->D * mg->H * mg->W >= 2147483648.0) return TRX_ERR_ARG;
-    if (ndim == 2 && mg->D != 1) return TRX_ERR_NDIM;
-    for (int k = 0; k < ndim * (ndim + 1); k++) {
-        if (!std::isfinite(mg->scale[k])) return TRX_ERR_ARG;
-        if (k % (ndim + 1) < ndim && !(mg->scale[k] > 0.f)) return TRX_ERR_ARG;      // the matrix part: a ratio of extents
-    }
-    return TRX_OK;
-}
-
+// (what the cross-lattice entry points refuse on top of the others: ami_grid_check, affine_host.h)
 // what the entry points refuse, before any HIP call (grids: a cross-lattice entry point, mg its moving lattice); the workspace size comes last
 static int ami_check(const trx_volumes *vol, const trx_moving_grid *mg, bool grids, const trx_mi_cfg *cfg, const void *workspace, size_t workspace_bytes, AmiGeom *g)
 {

@@ -196,6 +196,17 @@ __device__ __forceinline__ float base_coord(const float *__restrict__ tab, int i
     return tab ? tab[i] : (float)(2 * i + 1) / (float)S - 1.0f;
 }
 
+// Two lattices (trx_moving_grid): the loop's voxels, the mask and the base coordinates stay on vol's (target) lattice, the sample is
+// taken in a moving volume of its own size at theta_eff = theta (.) scale.  theta_eff is formed here, once per block, from uniform values (theta's row
+// through scalar loads, the scales from the kernel arguments): the voxel loop sees ND (ND + 1) registers, as it does with one lattice.
+template <int ND>
+__device__ __forceinline__ void ami_theta_eff(const float *__restrict__ th, const trx_moving_grid &mg, float (&te)[ND * (ND + 1)])
+{
+#pragma unroll
+    for (int k = 0; k < ND * (ND + 1); k++)      // one fp32 rounding: (theta, scale) samples exactly where (fl(theta scale), 1) does; pinned to an SGPR like theta's own row
+        te[k] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(th[k] * mg.scale[k])));
+}
+
 // ------------------------------------------------------------------------------------------
 // Block reduction of NV per-thread floats -> out[NV] (written by the first NV threads).
 // Deterministic (fixed order).  Staged through LDS in chunks of CH values so the footprint

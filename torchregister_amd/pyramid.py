@@ -34,6 +34,24 @@ def pyramid_shapes(spatial, levels):
     return shapes[::-1]
 
 
+def level_theta(theta, target_full, target_level, moving_full, moving_level):
+    """The theta between two LEVEL lattices of align_corners=True pyramids, from the theta between the full ones (pure host arithmetic, fp64,
+    returned in theta's dtype; shapes in the tensors' axis order).  A level's voxel j sits at the full voxel j (S - 1) / (S_l - 1), so in
+    affine_grid's normalised coordinates n_full = a n_level with a = S_l (S - 1) / (S (S_l - 1)) per axis (1 where the axis keeps its size):
+    theta_level[r][c] = theta[r][c] a_t[c] / a_m[r] and theta_level[r][nd] = theta[r][nd] / a_m[r] (rows / columns x, y(, z))."""
+    nd = len(target_full)
+    if tuple(theta.shape[-2:]) != (nd, nd + 1) or not len(target_level) == len(moving_full) == len(moving_level) == nd:
+        raise ValueError(f"expected a theta [..., {nd}, {nd + 1}] and four shapes of {nd} sizes, got {tuple(theta.shape)}, {tuple(target_full)}, "
+                         f"{tuple(target_level)}, {tuple(moving_full)}, {tuple(moving_level)}")
+
+    def growth(full, level):      # a per axis, in theta's x, y(, z) order
+        return [1.0 if int(S) == int(Sl) else int(Sl) * (int(S) - 1) / (int(S) * (int(Sl) - 1)) for S, Sl in zip(full[::-1], level[::-1])]
+
+    a_t = torch.tensor(growth(tuple(target_full), tuple(target_level)) + [1.0], dtype=torch.float64, device=theta.device)
+    a_m = torch.tensor(growth(tuple(moving_full), tuple(moving_level)), dtype=torch.float64, device=theta.device)
+    return (theta.double() * a_t / a_m[:, None]).to(theta.dtype)
+
+
 def resample(x, size, align_corners=False, channel_scale=None):
     """trx_resample of x [B, C, *sp] (fp32, GPU) to [B, C, *size]: per axis a [1,4,6,4,1]/16 blur before a shrink, then linear
     interpolation at F.interpolate's positions; channel_scale: C floats, channel c multiplied by channel_scale[c]."""

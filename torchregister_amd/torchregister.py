@@ -10,8 +10,9 @@ import torch
 from torch import cat
 
 from ._engine import _bending_weight, _mask_u8, _squarings, affine_warp, grid_scale
-from .pyramid import pyramid, pyramid_masks, pyramid_shapes, upsample_flow
-from .warpings import GRIDS_SUPPORT, MASK_SUPPORT, affine_register, device_loop_settings, flow_register, get_affine_warp, rigid_register, two_lattices
+from .pyramid import level_theta, pyramid, pyramid_masks, pyramid_shapes, upsample_flow
+from .warpings import (GRIDS_SUPPORT, INITIAL_SUPPORT, MASK_SUPPORT, affine_register, device_loop_settings, flow_register, get_affine_warp, resolve_initial, rigid_register,
+                       two_lattices)
 
 
 def _per_level(value, levels, name):
@@ -121,6 +122,7 @@ class Register():
         self.level_shapes = None
         self.world_matrix = None    # device_loop with voxel sizes: [B,nd+1,nd+1], the best theta as moving_mm = M target_mm (rows / columns x, y(, z))
         self.target_shape = None    # the spatial shape of the lattice optim registered onto: what reg(x) returns
+        self.initial = None         # optim(initial=...): the effective theta [B,nd,nd+1] the deformation is composed with
 
     def _flow_kw(self, n, lr, max_epochs):
         kw = dict(mode='bilinear', n=n, lr=lr, max_epochs=max_epochs, optimizer=self.optimizer, smooth_weight=self.smooth_weight,
@@ -155,6 +157,15 @@ class Register():
         grid_scale(moving.shape[2:], target.shape[2:], moving_voxel, target_voxel)      # exactly one voxel size, a non-positive one: ValueError
         return True
 
+    def _check_initial(self, initial, moving, target, moving_voxel, target_voxel):
+        '''initial=... of optim: ValueError unless the loop is the B-spline mutual-information loop (mode 'flow', flow_model 'bspline', MILoss
+        alone, not diffeomorphic, no voxel sizes), before any device work.  Returns the effective theta [B,nd,nd+1].'''
+        from .utils import MILoss
+        alone = self.criterion is not None and self.weight is not None and len(self.criterion) == 1 and isinstance(self.criterion[0], MILoss)
+        if not (self.mode == 'flow' and self.flow_model == 'bspline' and alone and not self.diffeomorphic) or moving_voxel is not None or target_voxel is not None:
+            raise ValueError(INITIAL_SUPPORT)
+        return resolve_initial(initial, moving, target)
+
     def _set_grids(self, grids, target, info):
         '''After a rigid / affine optim: the warp behind __call__ (two lattices: onto the target lattice, forward only) and the new attributes.'''
         self.target_shape = tuple(target.shape[2:])
@@ -162,7 +173,7 @@ class Register():
         size = self.target_shape
         self.warp = (lambda theta, x: affine_warp(theta, x, size=size)) if grids else get_affine_warp
 
-    def optim(self, moving, target, lr=1E-5, max_epochs=1000, n=32, per=0.1, *, mask=None, moving_voxel=None, target_voxel=None):
+    def optim(self, moving, target, lr=1E-5, max_epochs=1000, n=32, per=0.1, *, mask=None, moving_voxel=None, target_voxel=None, initial=None):
         '''
         Optimisation loop: moving, target [1,1,x,y(,z)] float32 GPU tensors (a leading batch > 1 of
         independent pairs is an extension).  Sets self.theta (best theta [B,nd,nd+1], or the flow
@@ -184,15 +195,29 @@ class Register():
             reg(moving) -, reg(x) warps any [B,c,*moving spatial] onto the target lattice, .world_matrix is the best theta in mm (None without
             voxel sizes), .target_shape the lattice, .final_pose keeps its meaning and mask= stays on the target lattice.  With levels > 1 each
             image gets its own pyramid, so both fields of view and the scale are the same at every level; .level_shapes are the target's.
+        initial : (keyword-only extension, mode 'flow' with flow_model='bspline' and MILoss alone; ValueError anywhere else, before any device work)
+            the result of the rigid / affine stage before - an effective theta [B,nd,nd+1], or a Register of mode 'rigid' / 'affine' that has run
+            onto this target lattice (its .theta is used).  The deformation is composed with it and the ORIGINAL moving image, on its own lattice,
+            is sampled once (affine_flow_warp; the loop runs in trx_bspline_mi_run_grids) - no resampling in between, nothing lost outside the
+            target's field of view.  .theta / .final_theta / .control keep their meaning (the flow on the target lattice, in target voxels),
+            reg(x) warps any [B,c,*moving spatial] onto the target lattice by one composed interpolation, .initial holds the theta used.  With
+            levels > 1 moving and target get their own pyramids (align_corners=True, as flow mode does) and a level runs with
+            pyramid.level_theta of the theta; .level_shapes are the target's.
         '''
-        grids = self._check_grids(moving, target, moving_voxel, target_voxel)
+        if initial is not None:
+            initial, grids = self._check_initial(initial, moving, target, moving_voxel, target_voxel), False
+        else:
+            grids = self._check_grids(moving, target, moving_voxel, target_voxel)
+        self.initial = initial
         if mask is not None:
             mask = self._check_mask(mask, target)
         if self.levels > 1:
-            return self._optim_levels(moving, target, lr, max_epochs, n, per, mask, moving_voxel, target_voxel)
+            return self._optim_levels(moving, target, lr, max_epochs, n, per, mask, moving_voxel, target_voxel, initial)
         if self.mode == 'flow':
             flowreg = flow_register(target.shape[2:], **self._flow_kw(n, lr, max_epochs)).to(moving.device)
-            flowreg.optimize(moving, target, self.device, self.debug, mask=mask)
+            flowreg.optimize(moving, target, self.device, self.debug, mask=mask, initial=initial)
+            if initial is not None:
+                self.target_shape = tuple(target.shape[2:])
             self.theta = flowreg.flow
             self.warp = flowreg.deform
             self.losses = flowreg.losses
@@ -221,23 +246,26 @@ class Register():
         self.final_pose = info.get('final_pose')
         self._set_grids(grids, target, info)
 
-    def _optim_levels(self, moving, target, lr, max_epochs, n, per, mask=None, moving_voxel=None, target_voxel=None):
+    def _optim_levels(self, moving, target, lr, max_epochs, n, per, mask=None, moving_voxel=None, target_voxel=None, initial=None):
         '''Coarse-to-fine: the single-level machinery (flow_register / _affine_family) on each level of pyramid(moving) and
         pyramid(target), coarsest first; each level starts from the previous level's FINAL parameters (rigid: the pose, drawn by
         torch.rand for the coarsest level as a single-level run draws it; affine: theta; flow: upsample_flow of the flow).  Optimiser
         state starts fresh at every level.  .theta / .warp / .losses / .best_idx / .final_theta are the finest level's.
         Two lattices (rigid / affine, device_loop): moving and target each get their own pyramid, so a level halves both lattices and doubles both
-        voxel sizes - the half extents, and with them the scale, are the same at every level; the theta handed up is the unscaled one.'''
+        voxel sizes - the half extents, and with them the scale, are the same at every level; the theta handed up is the unscaled one.
+        initial (flow, B-spline mutual information): moving and target get their own pyramids (align_corners=True) and level k runs with
+        level_theta(initial, ...), the theta between the two level lattices; the flow is handed up by upsample_flow as without it.'''
         grids = two_lattices(moving, target, moving_voxel, target_voxel)      # (refused by optim unless the loop is the fused mutual-information one)
         L = self.levels
         lrs, epochs = _per_level(lr, L, 'lr'), _per_level(max_epochs, L, 'max_epochs')
         shapes = pyramid_shapes(target.shape[2:], L)
-        if tuple(moving.shape[2:]) != tuple(target.shape[2:]) and not grids:
+        if tuple(moving.shape[2:]) != tuple(target.shape[2:]) and not grids and initial is None:
             raise ValueError(f"moving {tuple(moving.shape)} and target {tuple(target.shape)} differ in spatial size")
         flow = self.mode == 'flow'
         movs, tgts = pyramid(moving, L, align_corners=flow), pyramid(target, L, align_corners=flow)
         masks = [None] * L if mask is None else pyramid_masks(mask, L, align_corners=flow)      # raises for a pair whose mask empties at some level
         init = None if flow else self.init
+        mshapes = None if initial is None else pyramid_shapes(moving.shape[2:], L)
         self.level_losses, self.level_shapes = [], shapes
         for k in range(L):
             if flow:
@@ -247,7 +275,10 @@ class Register():
                     reg.base_flow = up       # the level's lattice starts from zero and adds to what the coarser levels found
                 else:
                     reg.init_flow = up
-                reg.optimize(movs[k], tgts[k], self.device, False, mask=masks[k])
+                lvl_initial = None if initial is None else level_theta(initial, target.shape[2:], shapes[k], moving.shape[2:], mshapes[k])
+                reg.optimize(movs[k], tgts[k], self.device, False, mask=masks[k], initial=lvl_initial)
+                if initial is not None:
+                    self.target_shape = tuple(shapes[k])
                 init = reg.final_velocity if self.diffeomorphic else reg.final_flow      # diffeomorphic: the levels add up as velocities
                 self.velocity, self.inverse_flow, self._inverse_warp = reg.velocity, reg.inverse_flow, reg.inverse
                 self.theta, self.warp, self.final_theta = reg.flow, reg.deform, reg.final_flow

@@ -289,6 +289,30 @@ GRIDS_SUPPORT = ("a moving image on a lattice of its own (another spatial shape)
                  "loops resample moving onto the target lattice first (reg(moving) of such a registration does it)")
 
 
+INITIAL_SUPPORT = ("initial= (the rigid / affine result of the stage before, composed into the deformation so that the moving image is sampled once, on "
+                   "its own lattice) is honoured by the B-spline mutual-information loop: mode='flow' with flow_model='bspline' and criterion=[MILoss()] "
+                   "alone, without diffeomorphic=True and without voxel sizes (the effective theta carries them); `initial` is an effective theta "
+                   "[B,nd,nd+1] or a Register of mode 'rigid' / 'affine' that has run onto the same target lattice")
+
+
+def resolve_initial(initial, moving, target):
+    """`initial` of the flow path -> the effective theta [B,nd,nd+1] (a tensor wherever the caller keeps it): a tensor of that shape (or one
+    [nd,nd+1] for every pair), or a Register of mode 'rigid' / 'affine' that has run - its .theta, which is already the effective one, and its
+    .target_shape must be target's.  ValueError(INITIAL_SUPPORT + the reason) otherwise; looks at shapes only, never at a device."""
+    if moving.dim() not in (4, 5) or target.dim() != moving.dim() or moving.shape[0] != target.shape[0]:
+        raise ValueError(f"{INITIAL_SUPPORT}; got moving {tuple(moving.shape)} and target {tuple(target.shape)}")
+    nd, B = target.dim() - 2, target.shape[0]
+    if not isinstance(initial, torch.Tensor):
+        if getattr(initial, "mode", None) not in ("rigid", "affine") or getattr(initial, "theta", None) is None:
+            raise ValueError(f"{INITIAL_SUPPORT}; got {type(initial).__name__}" + (" that has not run" if getattr(initial, "mode", None) in ("rigid", "affine") else ""))
+        if tuple(initial.target_shape or ()) != tuple(target.shape[2:]):
+            raise ValueError(f"{INITIAL_SUPPORT}; the initial registration ran onto {initial.target_shape}, this target is {tuple(target.shape[2:])}")
+        initial = initial.theta
+    if tuple(initial.shape[-2:]) != (nd, nd + 1) or initial.dim() not in (2, 3) or (initial.dim() == 3 and initial.shape[0] not in (1, B)):
+        raise ValueError(f"{INITIAL_SUPPORT}; got a theta of shape {tuple(initial.shape)} for {B} pairs in {nd}-D")
+    return initial.detach().reshape(-1, nd, nd + 1).expand(B, nd, nd + 1)
+
+
 def two_lattices(moving, target, moving_voxel=None, target_voxel=None):
     """Whether the pair asks for the cross-lattice path: differing spatial shapes or any voxel size.  Looks at shapes only."""
     return moving_voxel is not None or target_voxel is not None or tuple(moving.shape[2:]) != tuple(target.shape[2:])
@@ -461,7 +485,11 @@ class flow_register(nn.Module):
     base_flow + expand(control) is a stationary VELOCITY and the deformation is its exponential by `squarings` (0 .. 12) steps of scaling and
     squaring (_engine.svf_exp; the loop runs in trx_bspline_svf_run) - free of folds up to the discretisation, with exp(-velocity) as its
     inverse.  Then `.flow` / `.final_flow` are the exponentials of `.velocity` (the last forward's) / `.final_velocity`, `.inverse_flow` =
-    exp(-velocity), `.inverse(x)` warps x with it, and `base_flow` is a velocity."""
+    exp(-velocity), `.inverse(x)` warps x with it, and `base_flow` is a velocity.
+    optimize(..., initial=theta) (keyword-only extension, flow_model='bspline' with MILoss alone; ValueError(INITIAL_SUPPORT) otherwise): the
+    deformation is composed with the effective theta of a rigid / affine stage and the moving image - on a lattice of its own - is sampled ONCE,
+    at theta applied to voxel + flow (_engine.affine_flow_warp; the loop runs in trx_bspline_mi_run_grids).  `.flow`, `.control` and mask stay on
+    the target lattice, in target voxels; `.deform(x)` warps any [B,c,*moving spatial] onto it; `.initial` keeps the theta."""
 
     def __init__(self, img_size, mode="bilinear", in_c=1, n=1, criterions=None, weights=[0.33, 0.33, 0.33], lr=1E-3,
                  max_epochs=2000, stop_crit=1E-4, *, flow_model="unet", optimizer="sgd", smooth_weight=0.0, spacing=None,
@@ -513,23 +541,39 @@ class flow_register(nn.Module):
         self.init_control = None   # flow_model='bspline': the control tensor the optimisation starts from (None = zero)
         self.base_flow = None      # flow_model='bspline': a fixed dense flow the lattice adds to (None = none; Register's coarse-to-fine loop)
         self.velocity = self.final_velocity = self.inverse_flow = None   # diffeomorphic=True: see the class docstring
+        self.initial = None        # optimize(initial=...): the effective theta [B,nd,nd+1] the deformation is composed with
+
+    def _deform(self, x, flow):
+        if self.initial is not None:
+            return _engine.affine_flow_warp(x, self.initial.to(x.device), flow if flow.shape[0] == x.shape[0] else flow.expand(x.shape[0], *flow.shape[1:]))
+        return self.warp(x, flow)
 
     def forward(self, x, device=None):
         if self.model is not None:
             y, self.flow = self.model(x, device)
             return y
-        return self.warp(x, self.flow)
+        return self._deform(x, self.flow)
 
     def mask_supported(self, ndim):
         """Whether optimize() on `ndim`-dimensional images runs one of the device-side mutual-information loops, the ones that take a mask."""
         alone = len(self.criterions) == 1 and isinstance(self.criterions[0], MILoss)
         return alone and not self.diffeomorphic and (self.flow_model == "bspline" or (self.flow_model == "direct" and ndim == 3))
 
-    def optimize(self, moving, target, device=None, debug=True, grad_edges=False, *, mask=None):
+    def initial_supported(self):
+        """Whether optimize() takes initial=: the B-spline mutual-information loop (MILoss alone, not diffeomorphic)."""
+        return self.flow_model == "bspline" and not self.diffeomorphic and len(self.criterions) == 1 and isinstance(self.criterions[0], MILoss)
+
+    def optimize(self, moving, target, device=None, debug=True, grad_edges=False, *, mask=None, initial=None):
         """mask (keyword-only extension): a region of interest on the target lattice, [B,1,*spatial] or [B,*spatial], non-zero = the voxel counts,
-        for MILoss alone with flow_model='direct' (3-D) or 'bspline'; ValueError anywhere else, before any device work."""
+        for MILoss alone with flow_model='direct' (3-D) or 'bspline'; ValueError anywhere else, before any device work.
+        initial (keyword-only extension): see the class docstring; ValueError(INITIAL_SUPPORT) anywhere else, before any device work."""
         if grad_edges:
             raise NotImplementedError("grad_edges=True is not supported (SURVEY Q6)")
+        self.initial = None
+        if initial is not None:
+            if not self.initial_supported():
+                raise ValueError(INITIAL_SUPPORT)
+            initial = resolve_initial(initial, moving, target)
         if mask is not None:
             if not self.mask_supported(target.dim() - 2):
                 raise ValueError(MASK_SUPPORT)
@@ -546,7 +590,7 @@ class flow_register(nn.Module):
                     return self._optimize_unet(moving, target, spec, debug)
             return self._optimize_unet(moving, target, spec, debug)
         if self.flow_model == "bspline":
-            return self._optimize_bspline(moving, target, spec, debug, mask)
+            return self._optimize_bspline(moving, target, spec, debug, mask, initial)
         lncc = mi = None
         if spec is None and moving.dim() == 5 and len(self.criterions) == 1 and isinstance(self.criterions[0], MILoss):
             # direct flow + mutual information (+ smoothness) as ONE device-side loop (trx_flow_mi_run); ranges fitted once to (target, moving)
@@ -575,13 +619,14 @@ class flow_register(nn.Module):
         if debug:
             print("Optimization ended with status: %s" % message)
 
-    def _optimize_bspline(self, moving, target, spec, debug, mask=None):
+    def _optimize_bspline(self, moving, target, spec, debug, mask=None, initial=None):
         """The 'direct' loop with a control lattice as the parameter: one trx_bspline_run call, per-pair early stop on the device, one host sync."""
         from ._engine import BSplineSolver
         mi = self.criterions[0].settings(self.weights[0]) if spec is None else None     # __init__ admits MILoss alone beside the fused criteria
         solver = BSplineSolver(moving, target, self.spacing, loss=spec, mi=mi, optimizer=self.optimizer_kind, lr=self.lr, init=self.init_control,
                                base=self.base_flow, capacity=max(1, self.max_epochs), stop_crit=self.stop_crit, keep_last=True,
-                               bending_weight=self.bending_weight, squarings=self.squarings if self.diffeomorphic else None, mask=mask)
+                               bending_weight=self.bending_weight, squarings=self.squarings if self.diffeomorphic else None, mask=mask, initial=initial)
+        self.initial = initial
         solver.run(self.max_epochs)
         done = solver.step.cpu()
         n = int(done.max()) if self.max_epochs > 0 else 0
@@ -653,7 +698,7 @@ class flow_register(nn.Module):
             print("Optimization ended with status: %s" % message)
 
     def deform(self, x):
-        return self.warp(x, self.flow)
+        return self._deform(x, self.flow)
 
     def inverse(self, x):
         """x warped with exp(-velocity), the inverse of the deformation `deform` applies (diffeomorphic=True only)."""
