@@ -32,6 +32,16 @@ def opt_cfg(optimizer, lr, betas=(0.9, 0.999), eps=1e-8):
     return _lib.OptCfg(kind, float(lr), float(betas[0]), float(betas[1]), float(eps))
 
 
+def _reserve(solver, iters):
+    """Book `iters` more iterations on a solver's loss curve (`enqueued`: the host-side mirror of the device counter `step`) -> int(iters)."""
+    iters = int(iters)
+    if solver.enqueued + iters > solver.capacity:
+        raise _lib.TrxError(f"loss-curve capacity exceeded: {solver.enqueued} iterations enqueued + {iters} requested > capacity "
+                            f"{solver.capacity} (create the solver with a larger `capacity`)")
+    solver.enqueued += iters
+    return iters
+
+
 def _require_gpu(t, name):
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
@@ -55,6 +65,21 @@ def base_tables(spatial, device):
             _TABLES[key] = (torch.linspace(-1, 1, int(s), dtype=torch.float32) * (int(s) - 1) / int(s)).to(device)
         out.append(_TABLES[key])
     return out
+
+
+def _volumes(moving, target, moving_stride, target_stride, spatial, flags=0, tables=None):
+    """trx_volumes of B = moving.shape[0] pairs on the lattice `spatial` (the sizes the kernels walk and, on one lattice, sample in): moving / target
+    tensors (target None: NULL), their per-pair strides in elements, the flags, and the lattice's base-coordinate tables ((z,) y, x as base_tables
+    gives them) or None = the closed form.  The tensors are kept alive by the caller."""
+    v = _lib.Volumes()
+    v.moving, v.target = moving.data_ptr(), None if target is None else target.data_ptr()
+    v.moving_stride, v.target_stride = moving_stride, target_stride
+    v.ndim, v.B = len(spatial), moving.shape[0]
+    v.D, v.H, v.W = _dhw(spatial)
+    v.flags = flags
+    if tables is not None:
+        v.zn, v.yn, v.xn = (None,) * (3 - len(tables)) + tuple(t.data_ptr() for t in tables)
+    return v
 
 
 class _Batch:
@@ -82,21 +107,11 @@ class _Batch:
         self.tables = base_tables(self.spatial, self.device) if tables else None
 
     def vol(self, moving_stride=None, target_stride=None):
-        D, H, W = ((1,) + self.spatial) if self.nd == 2 else self.spatial
-        v = _lib.Volumes()
-        v.moving = self.moving.data_ptr()
-        v.target = self.target.data_ptr() if self.target is not None else None
-        v.moving_stride = self.C * self.nvox if moving_stride is None else moving_stride
-        v.target_stride = (self.target.shape[1] * self.nvox if self.target is not None else 0) if target_stride is None else target_stride
-        v.ndim, v.B, v.D, v.H, v.W = self.nd, self.B, D, H, W
-        v.flags = self.flags
-        if self.tables is not None:
-            if self.nd == 3:
-                v.zn, v.yn, v.xn = (t.data_ptr() for t in self.tables)
-            else:
-                v.zn = None
-                v.yn, v.xn = (t.data_ptr() for t in self.tables)
-        return v
+        if moving_stride is None:
+            moving_stride = self.C * self.nvox
+        if target_stride is None:
+            target_stride = self.target.shape[1] * self.nvox if self.target is not None else 0
+        return _volumes(self.moving, self.target, moving_stride, target_stride, self.spatial, self.flags, self.tables)
 
 
 def pad_theta(theta, nd):
@@ -121,7 +136,61 @@ def pose_to_theta(pose):
     return torch.stack([torch.cos(a), -torch.sin(a), pose[..., 1], torch.sin(a), torch.cos(a), pose[..., 2]], dim=-1)
 
 
-class AffineSolver:
+class _AffineParams:
+    """The parameter state of the rigid / affine loops (AffineSolver, AffineMISolver; include/trx.h: trx_affine_state), living on the GPU."""
+
+    def _init_params(self, b, nd, dev, mode, init, capacity):
+        """param / theta from the mode and `init`, the optimiser's moments, the records (best_*, losses, step, grad) and `state`, which points at them."""
+        self.nd, self.mode = nd, mode
+        if mode == "affine":
+            th0 = torch.eye(nd, nd + 1, device=dev).repeat(b, 1, 1) if init is None else init.to(dev).reshape(b, nd, nd + 1)
+            self.param = pad_theta(th0, nd)
+            self.theta = self.param.clone()
+        elif mode == "rigid":
+            npose = 6 if nd == 3 else 3
+            if init is None:
+                raise ValueError("rigid mode needs an initial pose (init=[B,%d])" % npose)
+            pose = init.to(device=dev, dtype=torch.float32).reshape(b, npose)
+            self.param = torch.zeros(b, PSTRIDE, device=dev)
+            self.param[:, :npose] = pose
+            self.theta = torch.zeros(b, PSTRIDE, device=dev)
+            # same fp32 -> fp64 -> fp32 chain as the device finalise / update kernel
+            self.theta[:, : nd * (nd + 1)] = pose_to_theta(pose.double()).float()
+        else:
+            raise ValueError(f"mode must be 'affine' or 'rigid', got {mode!r}")
+        self.capacity = int(capacity)
+        self.adam_m = torch.zeros(b, PSTRIDE, device=dev)
+        self.adam_v = torch.zeros(b, PSTRIDE, device=dev)
+        self.best_theta = torch.zeros(b, PSTRIDE, device=dev)
+        self.best_loss = torch.full((b,), float("inf"), device=dev)
+        self.best_idx = torch.full((b,), -1, dtype=torch.int32, device=dev)
+        self.losses = torch.full((b, self.capacity), float("nan"), device=dev)
+        self.step = torch.zeros(b, dtype=torch.int32, device=dev)
+        self.grad = torch.zeros(b, PSTRIDE, device=dev)
+        st = _lib.AffineState()
+        st.mode = _lib.PARAM_AFFINE if mode == "affine" else _lib.PARAM_RIGID
+        st.param, st.theta = self.param.data_ptr(), self.theta.data_ptr()
+        st.adam_m, st.adam_v = self.adam_m.data_ptr(), self.adam_v.data_ptr()
+        st.best_theta, st.best_loss, st.best_idx = self.best_theta.data_ptr(), self.best_loss.data_ptr(), self.best_idx.data_ptr()
+        st.losses, st.losses_capacity = self.losses.data_ptr(), self.capacity
+        st.step, st.grad = self.step.data_ptr(), self.grad.data_ptr()
+        self.state = st
+        self.enqueued = 0   # iterations enqueued so far (host-side mirror of the device counter `step`)
+
+    def _unpad(self, t):
+        nd = self.nd
+        return t[:, : nd * (nd + 1)].reshape(-1, nd, nd + 1)
+
+    @property
+    def current_theta(self):
+        return self._unpad(self.theta).clone()
+
+    @property
+    def best(self):
+        return self._unpad(self.best_theta).clone()
+
+
+class AffineSolver(_AffineParams):
     """Batched rigid/affine registration state living on the GPU.
 
     moving, target: [B,1,*spatial] fp32 on the GPU (B independent pairs).
@@ -138,50 +207,15 @@ class AffineSolver:
         if self.batch.target.shape[0] != self.batch.B:
             raise ValueError("moving and target batch sizes differ")
         b, nd, dev = self.batch.B, self.batch.nd, self.batch.device
-        self.nd, self.mode = nd, mode
         self.loss = loss or LossSpec(w_mse=1.0)
         self.opt = opt_cfg(optimizer, lr, betas, eps)
-        nt = nd * (nd + 1)
-        if mode == "affine":
-            th0 = torch.eye(nd, nd + 1, device=dev).repeat(b, 1, 1) if init is None else init.to(dev).reshape(b, nd, nd + 1)
-            self.param = pad_theta(th0, nd)
-            self.theta = self.param.clone()
-        elif mode == "rigid":
-            npose = 6 if nd == 3 else 3
-            if init is None:
-                raise ValueError("rigid mode needs an initial pose (init=[B,%d])" % npose)
-            pose = init.to(device=dev, dtype=torch.float32).reshape(b, npose)
-            self.param = torch.zeros(b, PSTRIDE, device=dev)
-            self.param[:, :npose] = pose
-            self.theta = torch.zeros(b, PSTRIDE, device=dev)
-            # same fp32 -> fp64 -> fp32 chain as the device finalise kernel
-            self.theta[:, :nt] = pose_to_theta(pose.double()).float()
-        else:
-            raise ValueError(f"mode must be 'affine' or 'rigid', got {mode!r}")
-        self.capacity = int(capacity)
-        self.adam_m = torch.zeros(b, PSTRIDE, device=dev)
-        self.adam_v = torch.zeros(b, PSTRIDE, device=dev)
-        self.best_theta = torch.zeros(b, PSTRIDE, device=dev)
-        self.best_loss = torch.full((b,), float("inf"), device=dev)
-        self.best_idx = torch.full((b,), -1, dtype=torch.int32, device=dev)
-        self.losses = torch.full((b, self.capacity), float("nan"), device=dev)
-        self.step = torch.zeros(b, dtype=torch.int32, device=dev)
-        self.grad = torch.zeros(b, PSTRIDE, device=dev)
+        self._init_params(b, nd, dev, mode, init, capacity)
         self.vol = self.batch.vol()
         self.ws_bytes = self.lib.trx_affine_workspace_bytes(ctypes.byref(self.vol))
         if self.ws_bytes == 0:
             raise _lib.TrxError("trx_affine_workspace_bytes rejected the batch geometry")
         self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
-        st = _lib.AffineState()
-        st.mode = _lib.PARAM_AFFINE if mode == "affine" else _lib.PARAM_RIGID
-        st.param, st.theta = self.param.data_ptr(), self.theta.data_ptr()
-        st.adam_m, st.adam_v = self.adam_m.data_ptr(), self.adam_v.data_ptr()
-        st.best_theta, st.best_loss, st.best_idx = self.best_theta.data_ptr(), self.best_loss.data_ptr(), self.best_idx.data_ptr()
-        st.losses, st.losses_capacity = self.losses.data_ptr(), self.capacity
-        st.step, st.grad = self.step.data_ptr(), self.grad.data_ptr()
-        self.state = st
         self.loss_c = self.loss.c()
-        self.enqueued = 0   # iterations enqueued so far (host-side mirror of the device counter `step`)
         # TRX_FLAG_ONE_KERNEL (include/trx.h): next to the identity a step of a chip-filling 3-D launch is the z-streaming kernel alone.  A hint about
         # speed only (the kernel runs stray pairs itself, slower), so it is set from what the HOST knows without waiting for the device: the
         # initial thetas (trx_affine_near_identity, the kernel's own window test) and, from the second run() call on, the kernel bodies the previous
@@ -218,11 +252,7 @@ class AffineSolver:
 
     def run(self, iters):
         """Enqueue `iters` iterations on the current stream (no host sync)."""
-        iters = int(iters)
-        if self.enqueued + iters > self.capacity:
-            raise _lib.TrxError(f"loss-curve capacity exceeded: {self.enqueued} iterations enqueued + {iters} requested > capacity "
-                                f"{self.capacity} (create the solver with a larger `capacity`)")
-        self.enqueued += iters
+        iters = _reserve(self, iters)
         policy = self._note_host is not None and not torch.cuda.is_current_stream_capturing()   # (a captured run records kernels only: no event, no copy to the host)
         if policy:
             self._refresh_one_kernel()
@@ -282,18 +312,6 @@ class AffineSolver:
                                           _lib.ptr(self.workspace), self.ws_bytes, _lib.current_stream(self.batch.device))
         _lib.check(rc, "trx_affine_loss")
         return terms
-
-    def _unpad(self, t):
-        nd = self.nd
-        return t[:, : nd * (nd + 1)].reshape(-1, nd, nd + 1)
-
-    @property
-    def current_theta(self):
-        return self._unpad(self.theta).clone()
-
-    @property
-    def best(self):
-        return self._unpad(self.best_theta).clone()
 
 
 def affine_warp(theta, moving, *, size=None):
@@ -406,11 +424,7 @@ class FlowSolver:
         self.enqueued = 0
 
     def run(self, iters):
-        iters = int(iters)
-        if self.enqueued + iters > self.capacity:
-            raise _lib.TrxError(f"loss-curve capacity exceeded: {self.enqueued} iterations enqueued + {iters} requested > capacity "
-                                f"{self.capacity} (create the solver with a larger `capacity`)")
-        self.enqueued += iters
+        iters = _reserve(self, iters)
         with torch.cuda.device(self.batch.device):
             if self.lncc is not None:
                 rc = self.lib.trx_flow_lncc_run(ctypes.byref(self.vol), self.lncc[0], self.lncc[1], self.lncc[2], ctypes.byref(self.opt),
@@ -746,11 +760,7 @@ class BSplineSolver:
         return svf_exp(self.velocity, self.squarings, inverse=True)
 
     def run(self, iters):
-        iters = int(iters)
-        if self.enqueued + iters > self.capacity:
-            raise _lib.TrxError(f"loss-curve capacity exceeded: {self.enqueued} iterations enqueued + {iters} requested > capacity "
-                                f"{self.capacity} (create the solver with a larger `capacity`)")
-        self.enqueued += iters
+        iters = _reserve(self, iters)
         with torch.cuda.device(self.batch.device):
             if self.squarings is not None:
                 rc = self.lib.trx_bspline_svf_run(ctypes.byref(self.vol), ctypes.byref(self.loss_c), ctypes.byref(self.opt), ctypes.byref(self.state),
@@ -1404,6 +1414,14 @@ def _mask_u8(mask, like):
     return (mask.detach().reshape(want) != 0).to(device=like.device, dtype=torch.uint8).contiguous()
 
 
+def _mi_cfg_c(bins, alpha, normalized, rng, mask):
+    """trx_mi_cfg over the range tensor [B,4] and the uint8 mask (or None) it points to: the caller keeps both alive."""
+    cfg = _lib.MICfg()
+    cfg.bins, cfg.alpha, cfg.normalized, cfg.range = _mi_bins(bins), float(alpha), int(bool(normalized)), rng.data_ptr()
+    cfg.mask = None if mask is None else mask.data_ptr()
+    return cfg
+
+
 def mi_range(target, moving, target_range=None, moving_range=None, mask=None):
     """[B,4] fp32 on the tensors' device: (lo_t, hi_t, lo_w, hi_w) per pair.  None: the target's min / max, the moving (or warped) image's min /
     max widened to contain 0 - the value of a zero-padded warp outside the field of view.  A (lo, hi) pair of numbers serves every pair of the
@@ -1435,10 +1453,7 @@ def _mi_cfg(mi, target, moving, mask=None):
         raise ValueError(f"unknown mutual-information settings {sorted(unknown)}")
     m8 = None if mask is None else _mask_u8(mask, target)
     rng = mi_range(target, moving, mi.get("target_range"), mi.get("moving_range"), m8)
-    cfg = _lib.MICfg()
-    cfg.bins, cfg.alpha, cfg.normalized, cfg.range = _mi_bins(mi.get("bins", 32)), float(mi.get("alpha", 1.0)), int(bool(mi.get("normalized", False))), rng.data_ptr()
-    cfg.mask = None if m8 is None else m8.data_ptr()
-    return cfg, rng, m8
+    return _mi_cfg_c(mi.get("bins", 32), mi.get("alpha", 1.0), mi.get("normalized", False), rng, m8), rng, m8
 
 
 def mi_loss_grad(target, warped, rng, bins=32, alpha=1.0, normalized=False, need_grad=True, mask=None):
@@ -1459,9 +1474,7 @@ def mi_loss_grad(target, warped, rng, bins=32, alpha=1.0, normalized=False, need
         raise ValueError(f"expected a range tensor [{B}, 4], got {tuple(rng.shape)}")
     rng = rng.detach().to(device=y.device, dtype=torch.float32).contiguous()
     D, H, W = (1, *y.shape[2:]) if nd == 2 else y.shape[2:]
-    cfg = _lib.MICfg()
-    cfg.bins, cfg.alpha, cfg.normalized, cfg.range = _mi_bins(bins), float(alpha), int(bool(normalized)), rng.data_ptr()
-    cfg.mask = None if mask is None else mask.data_ptr()
+    cfg = _mi_cfg_c(bins, alpha, normalized, rng, mask)
     loss = torch.empty(B, device=y.device)
     grad = torch.empty_like(w) if need_grad else None
     ws_bytes = lib.trx_mi_workspace_bytes(nd, B, D, H, W, cfg.bins)
@@ -1542,18 +1555,7 @@ class _GridPair:
         self.tables = base_tables(self.spatial, self.device)
 
     def vol(self):
-        v = _lib.Volumes()
-        v.moving, v.target = self.moving.data_ptr(), self.target.data_ptr()
-        v.moving_stride, v.target_stride = self.moving[0].numel(), self.target[0].numel()      # moving elements, target elements
-        v.ndim, v.B = self.nd, self.B
-        v.D, v.H, v.W = _dhw(self.spatial)
-        v.flags = 0
-        v.zn = None
-        if self.nd == 3:
-            v.zn, v.yn, v.xn = (t.data_ptr() for t in self.tables)
-        else:
-            v.yn, v.xn = (t.data_ptr() for t in self.tables)
-        return v
+        return _volumes(self.moving, self.target, self.moving[0].numel(), self.target[0].numel(), self.spatial, tables=self.tables)
 
     def grid(self):
         return _moving_grid(self.moving_spatial, self.scale)
@@ -1579,18 +1581,7 @@ def _affine_warp_grids(lib, theta, moving, size):
     B, C, nd, dev = mov.shape[0], mov.shape[1], mov.dim() - 2, mov.device
     th = pad_theta(theta.detach().to(dev).reshape(B, -1), nd)
     out = torch.empty((B, C) + size, dtype=torch.float32, device=dev)
-    tables = base_tables(size, dev)
-    v = _lib.Volumes()
-    v.moving, v.target = mov.data_ptr(), None
-    v.moving_stride, v.target_stride = mov[0].numel(), 0
-    v.ndim, v.B = nd, B
-    v.D, v.H, v.W = _dhw(size)
-    v.flags = 0
-    v.zn = None
-    if nd == 3:
-        v.zn, v.yn, v.xn = (t.data_ptr() for t in tables)
-    else:
-        v.yn, v.xn = (t.data_ptr() for t in tables)
+    v = _volumes(mov, None, mov[0].numel(), 0, size, tables=base_tables(size, dev))
     mg = _moving_grid(tuple(mov.shape[2:]))
     with torch.cuda.device(dev):
         rc = lib.trx_affine_warp_grids(ctypes.byref(v), ctypes.byref(mg), _lib.ptr(th), C, _lib.ptr(out), _lib.current_stream(dev))
@@ -1623,13 +1614,7 @@ def _affine_flow_call(x, theta, flow, scale):
         scale = torch.as_tensor(scale).detach().to("cpu", torch.float32)
         if tuple(scale.shape) != (nd, nd + 1):
             raise ValueError(f"expected a scale of shape {(nd, nd + 1)}, got {tuple(scale.shape)}")
-    v = _lib.Volumes()
-    v.moving, v.target = mov.data_ptr(), None
-    v.moving_stride, v.target_stride = mov[0].numel(), 0
-    v.ndim, v.B = nd, B
-    v.D, v.H, v.W = _dhw(fl.shape[2:])
-    v.flags = 0
-    v.xn = v.yn = v.zn = None      # the composed position is not an integer: the closed form, never the tables
+    v = _volumes(mov, None, mov[0].numel(), 0, fl.shape[2:])      # no tables: the composed position is not an integer, the closed form serves it
     return v, _moving_grid(tuple(mov.shape[2:]), scale), th, fl, mov
 
 
@@ -1693,60 +1678,34 @@ def affine_mi_loss_grad(moving, target, theta, rng, bins=32, alpha=1.0, normaliz
     if mask is not None:
         mask = _mask_u8(mask, target)
     lib = _lib.load()
-    if scale is not None or (isinstance(moving, torch.Tensor) and isinstance(target, torch.Tensor) and moving.shape[2:] != target.shape[2:]):
-        return _affine_mi_loss_grad_grids(lib, _GridPair(moving, target, scale), theta, rng, bins, alpha, normalized, need_grad, mask)
-    batch = _mi_pair_batch(moving, target)
-    B, nd = batch.B, batch.nd
-    if tuple(rng.shape) != (B, 4):
-        raise ValueError(f"expected a range tensor [{B}, 4], got {tuple(rng.shape)}")
-    rng = rng.detach().to(device=batch.device, dtype=torch.float32).contiguous()
-    th = pad_theta(theta.detach().to(batch.device).reshape(B, -1), nd)
-    cfg = _lib.MICfg()
-    cfg.bins, cfg.alpha, cfg.normalized, cfg.range = _mi_bins(bins), float(alpha), int(bool(normalized)), rng.data_ptr()
-    if mask is not None:
-        mask = mask.to(batch.device)
-        cfg.mask = mask.data_ptr()
-    vol = batch.vol()
-    ws_bytes = lib.trx_affine_mi_workspace_bytes(ctypes.byref(vol), cfg.bins)
-    if ws_bytes == 0:
-        raise _lib.TrxError(f"trx_affine_mi_workspace_bytes rejected {B} x {batch.spatial} with {bins} bins")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=batch.device)
-    loss = torch.empty(B, device=batch.device)
-    dth = torch.zeros(B, PSTRIDE, device=batch.device) if need_grad else None
-    with torch.cuda.device(batch.device):
-        rc = lib.trx_affine_mi_loss_grad(ctypes.byref(vol), ctypes.byref(cfg), _lib.ptr(th), _lib.ptr(loss), _lib.ptr(dth), _lib.ptr(ws), ws_bytes,
-                                         _lib.current_stream(batch.device))
-    _lib.check(rc, "trx_affine_mi_loss_grad")
-    return loss, (dth[:, : nd * (nd + 1)].reshape(B, nd, nd + 1) if need_grad else None)
-
-
-def _affine_mi_loss_grad_grids(lib, pair, theta, rng, bins, alpha, normalized, need_grad, mask):
-    """affine_mi_loss_grad on two lattices (pair: _GridPair; mask: uint8 on the target lattice or None)."""
+    two = scale is not None or (isinstance(moving, torch.Tensor) and isinstance(target, torch.Tensor) and moving.shape[2:] != target.shape[2:])
+    pair = _GridPair(moving, target, scale) if two else _mi_pair_batch(moving, target)
     B, nd, dev = pair.B, pair.nd, pair.device
     if tuple(rng.shape) != (B, 4):
         raise ValueError(f"expected a range tensor [{B}, 4], got {tuple(rng.shape)}")
     rng = rng.detach().to(device=dev, dtype=torch.float32).contiguous()
     th = pad_theta(theta.detach().to(dev).reshape(B, -1), nd)
-    cfg = _lib.MICfg()
-    cfg.bins, cfg.alpha, cfg.normalized, cfg.range = _mi_bins(bins), float(alpha), int(bool(normalized)), rng.data_ptr()
-    if mask is not None:
-        mask = mask.to(dev)
-        cfg.mask = mask.data_ptr()
-    vol, mg = pair.vol(), pair.grid()
+    mask = None if mask is None else mask.to(dev)
+    cfg = _mi_cfg_c(bins, alpha, normalized, rng, mask)
+    vol = pair.vol()
     ws_bytes = lib.trx_affine_mi_workspace_bytes(ctypes.byref(vol), cfg.bins)
     if ws_bytes == 0:
         raise _lib.TrxError(f"trx_affine_mi_workspace_bytes rejected {B} x {pair.spatial} with {bins} bins")
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     loss = torch.empty(B, device=dev)
     dth = torch.zeros(B, PSTRIDE, device=dev) if need_grad else None
+    tail = (_lib.ptr(th), _lib.ptr(loss), _lib.ptr(dth), _lib.ptr(ws), ws_bytes, _lib.current_stream(dev))
     with torch.cuda.device(dev):
-        rc = lib.trx_affine_mi_loss_grad_grids(ctypes.byref(vol), ctypes.byref(mg), ctypes.byref(cfg), _lib.ptr(th), _lib.ptr(loss), _lib.ptr(dth), _lib.ptr(ws),
-                                               ws_bytes, _lib.current_stream(dev))
-    _lib.check(rc, "trx_affine_mi_loss_grad_grids")
+        if two:
+            mg = pair.grid()
+            rc = lib.trx_affine_mi_loss_grad_grids(ctypes.byref(vol), ctypes.byref(mg), ctypes.byref(cfg), *tail)
+        else:
+            rc = lib.trx_affine_mi_loss_grad(ctypes.byref(vol), ctypes.byref(cfg), *tail)
+    _lib.check(rc, "trx_affine_mi_loss_grad_grids" if two else "trx_affine_mi_loss_grad")
     return loss, (dth[:, : nd * (nd + 1)].reshape(B, nd, nd + 1) if need_grad else None)
 
 
-class AffineMISolver:
+class AffineMISolver(_AffineParams):
     """Batched rigid / affine registration under the Parzen joint-histogram mutual information, the whole loop on the GPU (extension, include/trx.h:
     trx_affine_mi_run): per iteration the warp is fused into the histogram pass and into the gradient pass - no warped volume, no autograd, no
     torch optimiser, no host sync.  The B pairs are independent: each has its own parameters and its own intensity range.
@@ -1772,56 +1731,18 @@ class AffineMISolver:
         self.batch = _GridPair(moving, target, None, moving_voxel, target_voxel) if two else _mi_pair_batch(moving, target)
         self.grid = self.batch.grid() if two else None      # trx_moving_grid, or None: one lattice
         b, nd, dev = self.batch.B, self.batch.nd, self.batch.device
-        self.nd, self.mode = nd, mode
         self.opt = opt_cfg(optimizer, lr, betas, eps)
-        nt = nd * (nd + 1)
-        if mode == "affine":
-            th0 = torch.eye(nd, nd + 1, device=dev).repeat(b, 1, 1) if init is None else init.to(dev).reshape(b, nd, nd + 1)
-            self.param = pad_theta(th0, nd)
-            self.theta = self.param.clone()
-        elif mode == "rigid":
-            npose = 6 if nd == 3 else 3
-            if init is None:
-                raise ValueError("rigid mode needs an initial pose (init=[B,%d])" % npose)
-            pose = init.to(device=dev, dtype=torch.float32).reshape(b, npose)
-            self.param = torch.zeros(b, PSTRIDE, device=dev)
-            self.param[:, :npose] = pose
-            self.theta = torch.zeros(b, PSTRIDE, device=dev)
-            self.theta[:, :nt] = pose_to_theta(pose.double()).float()      # the update kernel's fp32 -> fp64 -> fp32 chain
-        else:
-            raise ValueError(f"mode must be 'affine' or 'rigid', got {mode!r}")
+        self._init_params(b, nd, dev, mode, init, capacity)
         self.mi, self.mi_range, self.mask = _mi_cfg({} if mi is None else mi, self.batch.target, self.batch.moving, mask)
-        self.capacity = int(capacity)
-        self.adam_m = torch.zeros(b, PSTRIDE, device=dev)
-        self.adam_v = torch.zeros(b, PSTRIDE, device=dev)
-        self.best_theta = torch.zeros(b, PSTRIDE, device=dev)
-        self.best_loss = torch.full((b,), float("inf"), device=dev)
-        self.best_idx = torch.full((b,), -1, dtype=torch.int32, device=dev)
-        self.losses = torch.full((b, self.capacity), float("nan"), device=dev)
-        self.step = torch.zeros(b, dtype=torch.int32, device=dev)
-        self.grad = torch.zeros(b, PSTRIDE, device=dev)
         self.vol = self.batch.vol()
         self.ws_bytes = self.lib.trx_affine_mi_workspace_bytes(ctypes.byref(self.vol), self.mi.bins)
         if self.ws_bytes == 0:
             raise _lib.TrxError("trx_affine_mi_workspace_bytes rejected the batch geometry")
         self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
-        st = _lib.AffineState()
-        st.mode = _lib.PARAM_AFFINE if mode == "affine" else _lib.PARAM_RIGID
-        st.param, st.theta = self.param.data_ptr(), self.theta.data_ptr()
-        st.adam_m, st.adam_v = self.adam_m.data_ptr(), self.adam_v.data_ptr()
-        st.best_theta, st.best_loss, st.best_idx = self.best_theta.data_ptr(), self.best_loss.data_ptr(), self.best_idx.data_ptr()
-        st.losses, st.losses_capacity = self.losses.data_ptr(), self.capacity
-        st.step, st.grad = self.step.data_ptr(), self.grad.data_ptr()
-        self.state = st
-        self.enqueued = 0   # iterations enqueued so far (host-side mirror of the device counter `step`)
 
     def run(self, iters):
         """Enqueue `iters` iterations on the current stream (no host sync)."""
-        iters = int(iters)
-        if self.enqueued + iters > self.capacity:
-            raise _lib.TrxError(f"loss-curve capacity exceeded: {self.enqueued} iterations enqueued + {iters} requested > capacity "
-                                f"{self.capacity} (create the solver with a larger `capacity`)")
-        self.enqueued += iters
+        iters = _reserve(self, iters)
         with torch.cuda.device(self.batch.device):
             if self.grid is None:
                 rc = self.lib.trx_affine_mi_run(ctypes.byref(self.vol), ctypes.byref(self.mi), ctypes.byref(self.opt), ctypes.byref(self.state), iters,
@@ -1831,18 +1752,6 @@ class AffineMISolver:
                                                       ctypes.byref(self.state), iters, _lib.ptr(self.workspace), self.ws_bytes,
                                                       _lib.current_stream(self.batch.device))
         _lib.check(rc, "trx_affine_mi_run" if self.grid is None else "trx_affine_mi_run_grids")
-
-    def _unpad(self, t):
-        nd = self.nd
-        return t[:, : nd * (nd + 1)].reshape(-1, nd, nd + 1)
-
-    @property
-    def current_theta(self):
-        return self._unpad(self.theta).clone()
-
-    @property
-    def best(self):
-        return self._unpad(self.best_theta).clone()
 
     @property
     def scale(self):

@@ -2,8 +2,8 @@
 // The moving image keeps its own lattice (trx_moving_grid); the flow lives on the target lattice, in target voxels.  For target voxel x:
 //   p = x + flow(x)                       one fp32 add per axis (trx_flow_warp's position)
 //   n_c = (2 p_c + 1) / S_t,c - 1         closed form of affine_grid's base coordinate at a non-integer position (vol's xn / yn / zn tables are not used)
-//   m = theta_eff . (n_x, n_y, n_z, 1)    theta_eff = theta (.) scale (ami_theta_eff), the fma order of affine_warp_grids_kernel
-//   i_r = unnorm<ND>(m_r, S_m,r)          with the MOVING sizes
+//   m = theta_eff . (n_x, n_y, n_z, 1)    theta_eff = theta (.) scale (ami_theta_eff); this line and the next are affine_coord (trx_common.h),
+//   i_r = unnorm<ND>(m_r, S_m,r)          with the MOVING sizes - the call affine_warp_grids_kernel makes
 //   out = sample3 / sample2 of moving at i (zero padding)
 // With flow == 0 every operation is affine_warp_grids_kernel's on the closed-form coordinates: the same bits.  Backward, per target voxel (a gather like
 // the forward: no scatter, no atomics, no workspace, the same bits on every call):
@@ -27,15 +27,9 @@ __device__ __forceinline__ void af_coord(const float (&te)[ND * (ND + 1)], const
 {
     const float xn = fmaf(2.0f, (float)x + f[ND - 1], 1.0f) / (float)W - 1.0f;
     const float yn = fmaf(2.0f, (float)y + f[ND - 2], 1.0f) / (float)H - 1.0f;
-    if constexpr (ND == 3) {
-        const float zn = fmaf(2.0f, (float)z + f[0], 1.0f) / (float)D - 1.0f;
-        ic[0] = unnorm<3>(fmaf(te[1], yn, fmaf(te[0], xn, fmaf(te[2], zn, te[3]))), (float)Wm);
-        ic[1] = unnorm<3>(fmaf(te[5], yn, fmaf(te[4], xn, fmaf(te[6], zn, te[7]))), (float)Hm);
-        ic[2] = unnorm<3>(fmaf(te[9], yn, fmaf(te[8], xn, fmaf(te[10], zn, te[11]))), (float)Dm);
-    } else {
-        ic[0] = unnorm<2>(fmaf(te[1], yn, fmaf(te[0], xn, te[2])), (float)Wm);
-        ic[1] = unnorm<2>(fmaf(te[4], yn, fmaf(te[3], xn, te[5])), (float)Hm);
-    }
+    float zn = 0.f;
+    if constexpr (ND == 3) zn = fmaf(2.0f, (float)z + f[0], 1.0f) / (float)D - 1.0f;
+    affine_coord<ND>(te, xn, yn, zn, Dm, Hm, Wm, ic);
 }
 
 // S_m,r / S_t,c in theta's [row r][column c] order (x, y, z), formed on the host in fp32

@@ -21,15 +21,11 @@ __device__ __forceinline__ void lattice_coords(const trx_volumes &vol, const flo
                                                float &zn, float &ix, float &iy, float &iz)
 {
     xn = base_coord(vol.xn, x, vol.W); yn = base_coord(vol.yn, y, vol.H); zn = 0.f; iz = 0.f;
-    if constexpr (ND == 3) {
-        zn = base_coord(vol.zn, z, vol.D);
-        ix = unnorm<3>(fmaf(th[1], yn, fmaf(th[0], xn, fmaf(th[2], zn, th[3]))), (float)vol.W);
-        iy = unnorm<3>(fmaf(th[5], yn, fmaf(th[4], xn, fmaf(th[6], zn, th[7]))), (float)vol.H);
-        iz = unnorm<3>(fmaf(th[9], yn, fmaf(th[8], xn, fmaf(th[10], zn, th[11]))), (float)vol.D);
-    } else {
-        ix = unnorm<2>(fmaf(th[1], yn, fmaf(th[0], xn, th[2])), (float)vol.W);
-        iy = unnorm<2>(fmaf(th[4], yn, fmaf(th[3], xn, th[5])), (float)vol.H);
-    }
+    if constexpr (ND == 3) zn = base_coord(vol.zn, z, vol.D);
+    float ic[ND];
+    affine_coord<ND>(th, xn, yn, zn, vol.D, vol.H, vol.W, ic);
+    ix = ic[0]; iy = ic[1];
+    if constexpr (ND == 3) iz = ic[2];
 }
 
 // One pass over the lattice, four points per thread and trip: the three dependent memory round trips of a point (index tables ->

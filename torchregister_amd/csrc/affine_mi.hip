@@ -19,10 +19,12 @@
 // mask, 1 outside) and skips a voxel outside it before any coordinate is formed - nothing is sampled, nothing enters the LDS tables or the thread's
 // sums.  A block whose chunk lies wholly outside the mask still clears and flushes (adding nothing) and still writes its partial row (zeros): the
 // reduction reads a fixed number of rows.  The table kernel takes N_m from the counts; the update kernel zeroes all K x K cells, masked or not.
-// Two lattices (trx_moving_grid, DESIGN.md section 4.13: trx_affine_mi_loss_grad_grids, trx_affine_mi_run_grids, trx_affine_warp_grids): both passes, the
-// update kernel and the one-evaluation reduction have a cross-lattice sibling each (*_grids_kernel) -
-// the voxels walked, the mask and the base coordinates are the target lattice's, the sample is taken at theta (.) scale in a moving volume of its own
-// size, and the reduction multiplies the sums by the scales.  The one-lattice kernels keep their names, arguments and code.
+// Two lattices (trx_moving_grid, DESIGN.md section 4.13: trx_affine_mi_loss_grad_grids, trx_affine_mi_run_grids, trx_affine_warp_grids): the voxels walked,
+// the mask and the base coordinates are the target lattice's, the sample is taken at theta (.) scale in a moving volume of its own size, and the
+// reduction multiplies the sums by the scales.  Each pass and the update have ONE body (ami_hist_body / ami_grad_body / ami_update_body<.., XL>): XL picks
+// theta_eff and the moving sizes (ami_pose) where the one-lattice instance reads theta in place and vol's sizes.  The __global__ kernels (*_kernel one lattice,
+// *_grids_kernel two: their names and arguments are the launch interface) only forward to the body.  The sampling coordinate is affine_coord (trx_common.h),
+// shared with the cross-lattice warp here, the composed warp (affine_flow.hip) and the lattice warp (affine_lattice.hip).
 #include "affine_finalize.h"   // reduce_partials, fin_load / fin_update (the epilogue of the affine step), launch_bwd_finalize (affine_host.h)
 #include "mi_dev.h"
 
@@ -56,44 +58,56 @@ static int ami_geom(const trx_volumes *v, int bins, AmiGeom *g)
     return TRX_OK;
 }
 
-// The sample of output voxel (x, y, z) of pair theta `th`: value and derivative with respect to the un-normalised source coordinate
+// The sample of the output voxel at normalised position (xn, yn, zn) under theta `th`, in a moving volume of D x H x W: value and derivative with respect
+// to the un-normalised source coordinate
 template <int ND>
 struct AmiSample {
     float v, d[ND];
 };
 template <int ND>
-__device__ __forceinline__ AmiSample<ND> ami_sample(const trx_volumes &vol, const float *__restrict__ th, const float *__restrict__ mov, int x, int y, int z, float xn,
-                                                    float yn, float zn)
+__device__ __forceinline__ AmiSample<ND> ami_sample(const float *__restrict__ th, const float *__restrict__ mov, int D, int H, int W, float xn, float yn, float zn)
 {
-    const int D = vol.D, H = vol.H, W = vol.W;
+    float ic[ND];
+    affine_coord<ND>(th, xn, yn, zn, D, H, W, ic);
     AmiSample<ND> r;
     if constexpr (ND == 3) {
-        const float ix = unnorm<3>(fmaf(th[1], yn, fmaf(th[0], xn, fmaf(th[2], zn, th[3]))), (float)W);
-        const float iy = unnorm<3>(fmaf(th[5], yn, fmaf(th[4], xn, fmaf(th[6], zn, th[7]))), (float)H);
-        const float iz = unnorm<3>(fmaf(th[9], yn, fmaf(th[8], xn, fmaf(th[10], zn, th[11]))), (float)D);
-        const Samp3 s = sample3(mov, D, H, W, ix, iy, iz);
+        const Samp3 s = sample3(mov, D, H, W, ic[0], ic[1], ic[2]);
         r.v = s.v; r.d[0] = s.dx; r.d[1] = s.dy; r.d[2] = s.dz;
     } else {
-        const float ix = unnorm<2>(fmaf(th[1], yn, fmaf(th[0], xn, th[2])), (float)W);
-        const float iy = unnorm<2>(fmaf(th[4], yn, fmaf(th[3], xn, th[5])), (float)H);
-        const Samp2 s = sample2(mov, H, W, ix, iy);
+        const Samp2 s = sample2(mov, H, W, ic[0], ic[1]);
         r.v = s.v; r.d[0] = s.dx; r.d[1] = s.dy;
     }
     return r;
 }
 
-// Two lattices (trx_moving_grid): theta_eff = theta (.) scale is formed once per block by ami_theta_eff (trx_common.h).
+// What a block samples pair b with: theta's row in place and vol's sizes, or (XL, two lattices: trx_moving_grid) theta_eff = theta (.) scale,
+// formed once per block into `te` (ami_theta_eff, trx_common.h), and the moving lattice's sizes.  Returns the row the voxel loop reads.
+template <int ND, bool XL>
+__device__ __forceinline__ const float *ami_pose(const trx_volumes &vol, const trx_moving_grid *mg, const float *__restrict__ th, float (&te)[ND * (ND + 1)], int &D, int &H,
+                                                 int &W)
+{
+    if constexpr (XL) {
+        ami_theta_eff<ND>(th, *mg, te);
+        D = mg->D; H = mg->H; W = mg->W;
+        return te;
+    } else {
+        D = vol.D; H = vol.H; W = vol.W;
+        return th;
+    }
+}
 
-// pass 1: warp and histogram
-template <int ND, bool MASKED>
-__global__ __launch_bounds__(TRX_BLOCK) void ami_hist_kernel(trx_volumes vol, const float *__restrict__ theta, unsigned N, int K, int T, const float *__restrict__ range,
-                                                               unsigned long long *__restrict__ counts, const unsigned char *__restrict__ mask)
+// pass 1: warp and histogram.  mg: the moving lattice (XL) or unused
+template <int ND, bool MASKED, bool XL>
+__device__ __forceinline__ void ami_hist_body(const trx_volumes &vol, const trx_moving_grid *mg, const float *__restrict__ theta, unsigned N, int K, int T,
+                                              const float *__restrict__ range, unsigned long long *__restrict__ counts, const unsigned char *__restrict__ mask)
 {
     extern __shared__ unsigned long long ami_lds[];           // [T][K][K]
     const int b = blockIdx.y, tid = threadIdx.x, KK = K * K;
     mi_lds_clear(ami_lds, T * KK);
     const MiScale m = mi_scale(range, b, K);
-    const float *__restrict__ th = theta + (size_t)b * TRX_PSTRIDE;
+    float te[ND * (ND + 1)];
+    int Dm, Hm, Wm;
+    const float *__restrict__ th = ami_pose<ND, XL>(vol, mg, theta + (size_t)b * TRX_PSTRIDE, te, Dm, Hm, Wm);
     const float *__restrict__ mov = vol.moving + (size_t)b * vol.moving_stride;
     const float *__restrict__ tgt = vol.target + (size_t)b * vol.target_stride;
     const unsigned char *mk = MASKED ? mask + (size_t)b * N : nullptr;      // dense, whatever target_stride says
@@ -102,41 +116,24 @@ __global__ __launch_bounds__(TRX_BLOCK) void ami_hist_kernel(trx_volumes vol, co
     for (VoxelWalk vw(first + tid, TRX_BLOCK, vol.H, vol.W); vw.i < last; vw.next(vol.H, vol.W)) {
         if (!mi_counts<MASKED>(mk, vw.i)) continue;      // before any coordinate: a voxel outside the mask costs its mask byte and nothing else
         const float xn = base_coord(vol.xn, vw.x, vol.W), yn = base_coord(vol.yn, vw.y, vol.H), zn = ND == 3 ? base_coord(vol.zn, vw.z, vol.D) : 0.f;
-        const AmiSample<ND> s = ami_sample<ND>(vol, th, mov, vw.x, vw.y, vw.z, xn, yn, zn);
+        const AmiSample<ND> s = ami_sample<ND>(th, mov, Dm, Hm, Wm, xn, yn, zn);
         mi_accumulate(mine, mi_voxel(__builtin_nontemporal_load(tgt + vw.i), s.v, m, K), K);
     }
     __syncthreads();
     mi_flush(ami_lds, T, KK, counts + (size_t)b * KK);
 }
-
-// pass 1 on two lattices: ami_hist_kernel with theta_eff for theta and the moving sizes for the sampler's (mvol: vol with D, H, W replaced - the sampler
-// reads nothing else of it).  The mask test stays in front of any coordinate arithmetic.  A kernel of its own: the one-lattice instances keep their code.
+template <int ND, bool MASKED>
+__global__ __launch_bounds__(TRX_BLOCK) void ami_hist_kernel(trx_volumes vol, const float *__restrict__ theta, unsigned N, int K, int T, const float *__restrict__ range,
+                                                               unsigned long long *__restrict__ counts, const unsigned char *__restrict__ mask)
+{
+    ami_hist_body<ND, MASKED, false>(vol, nullptr, theta, N, K, T, range, counts, mask);
+}
 template <int ND, bool MASKED>
 __global__ __launch_bounds__(TRX_BLOCK) void ami_hist_grids_kernel(trx_volumes vol, trx_moving_grid mg, const float *__restrict__ theta, unsigned N, int K, int T,
                                                                      const float *__restrict__ range, unsigned long long *__restrict__ counts,
                                                                      const unsigned char *__restrict__ mask)
 {
-    extern __shared__ unsigned long long ami_lds[];           // [T][K][K]
-    const int b = blockIdx.y, tid = threadIdx.x, KK = K * K;
-    mi_lds_clear(ami_lds, T * KK);
-    const MiScale m = mi_scale(range, b, K);
-    float te[ND * (ND + 1)];
-    ami_theta_eff<ND>(theta + (size_t)b * TRX_PSTRIDE, mg, te);
-    trx_volumes mvol = vol;
-    mvol.D = mg.D; mvol.H = mg.H; mvol.W = mg.W;
-    const float *__restrict__ mov = vol.moving + (size_t)b * vol.moving_stride;
-    const float *__restrict__ tgt = vol.target + (size_t)b * vol.target_stride;
-    const unsigned char *mk = MASKED ? mask + (size_t)b * N : nullptr;
-    unsigned long long *mine = ami_lds + ((tid >> 6) % T) * KK;
-    const unsigned first = blockIdx.x * (unsigned)kMiChunk, last = min(N, first + (unsigned)kMiChunk);
-    for (VoxelWalk vw(first + tid, TRX_BLOCK, vol.H, vol.W); vw.i < last; vw.next(vol.H, vol.W)) {
-        if (!mi_counts<MASKED>(mk, vw.i)) continue;
-        const float xn = base_coord(vol.xn, vw.x, vol.W), yn = base_coord(vol.yn, vw.y, vol.H), zn = ND == 3 ? base_coord(vol.zn, vw.z, vol.D) : 0.f;
-        const AmiSample<ND> s = ami_sample<ND>(mvol, te, mov, vw.x, vw.y, vw.z, xn, yn, zn);
-        mi_accumulate(mine, mi_voxel(__builtin_nontemporal_load(tgt + vw.i), s.v, m, K), K);
-    }
-    __syncthreads();
-    mi_flush(ami_lds, T, KK, counts + (size_t)b * KK);
+    ami_hist_body<ND, MASKED, true>(vol, &mg, theta, N, K, T, range, counts, mask);
 }
 
 // The block's 256 x NV per-thread sums -> out[NV]: fp64 from here on (a voxel's terms cancel to a gradient orders of magnitude below them, and the
@@ -163,10 +160,12 @@ __device__ __forceinline__ void ami_block_sum_store(const float (&vals)[NV], flo
     }
 }
 
-// pass 2: gradient rows
-template <int ND, bool MASKED>
-__global__ __launch_bounds__(TRX_BLOCK) void ami_grad_kernel(trx_volumes vol, const float *__restrict__ theta, unsigned N, int K, const float *__restrict__ range,
-                                                               const float *__restrict__ G, float *__restrict__ partials, const unsigned char *__restrict__ mask)
+// pass 2: gradient rows.  XL: the rows are sums of gw * (sampler derivative in moving voxels) * (xn, yn, zn, 1) - dL/dtheta_eff up to the S / 2 of the MOVING
+// sizes; the reduction behind the pass applies that and the scales.
+template <int ND, bool MASKED, bool XL>
+__device__ __forceinline__ void ami_grad_body(const trx_volumes &vol, const trx_moving_grid *mg, const float *__restrict__ theta, unsigned N, int K,
+                                              const float *__restrict__ range, const float *__restrict__ G, float *__restrict__ partials,
+                                              const unsigned char *__restrict__ mask)
 {
     constexpr int NT = ND * (ND + 1);
     extern __shared__ float ami_g[];                // [K][K]
@@ -174,7 +173,9 @@ __global__ __launch_bounds__(TRX_BLOCK) void ami_grad_kernel(trx_volumes vol, co
     for (int i = tid; i < KK; i += TRX_BLOCK) ami_g[i] = G[(size_t)b * KK + i];
     __syncthreads();
     const MiScale m = mi_scale(range, b, K);
-    const float *__restrict__ th = theta + (size_t)b * TRX_PSTRIDE;
+    float te[NT];
+    int Dm, Hm, Wm;
+    const float *__restrict__ th = ami_pose<ND, XL>(vol, mg, theta + (size_t)b * TRX_PSTRIDE, te, Dm, Hm, Wm);
     const float *__restrict__ mov = vol.moving + (size_t)b * vol.moving_stride;
     const float *__restrict__ tgt = vol.target + (size_t)b * vol.target_stride;
     float vals[NT];
@@ -185,7 +186,7 @@ __global__ __launch_bounds__(TRX_BLOCK) void ami_grad_kernel(trx_volumes vol, co
     for (VoxelWalk vw(first + tid, TRX_BLOCK, vol.H, vol.W); vw.i < last; vw.next(vol.H, vol.W)) {
         if (!mi_counts<MASKED>(mk, vw.i)) continue;      // grad_warped is 0 there: nothing is sampled, the row below is still written (zeros if the chunk is empty)
         const float xn = base_coord(vol.xn, vw.x, vol.W), yn = base_coord(vol.yn, vw.y, vol.H), zn = ND == 3 ? base_coord(vol.zn, vw.z, vol.D) : 0.f;
-        const AmiSample<ND> s = ami_sample<ND>(vol, th, mov, vw.x, vw.y, vw.z, xn, yn, zn);
+        const AmiSample<ND> s = ami_sample<ND>(th, mov, Dm, Hm, Wm, xn, yn, zn);
         const float gw = mi_voxel_grad(ami_g, mi_voxel(__builtin_nontemporal_load(tgt + vw.i), s.v, m, K), K);
 #pragma unroll
         for (int c = 0; c < ND; c++) {      // row c of theta: d coordinate_c / d theta[c][.] = (xn, yn, zn, 1)
@@ -199,47 +200,18 @@ __global__ __launch_bounds__(TRX_BLOCK) void ami_grad_kernel(trx_volumes vol, co
     }
     ami_block_sum_store<NT>(vals, partials + ((size_t)b * gridDim.x + blockIdx.x) * NT);
 }
-
-// pass 2 on two lattices: the rows are sums of gw * (sampler derivative in moving voxels) * (xn, yn, zn, 1) - dL/dtheta_eff up to the S / 2 of the MOVING
-// sizes; the reduction behind the pass applies that and the scales.
+template <int ND, bool MASKED>
+__global__ __launch_bounds__(TRX_BLOCK) void ami_grad_kernel(trx_volumes vol, const float *__restrict__ theta, unsigned N, int K, const float *__restrict__ range,
+                                                               const float *__restrict__ G, float *__restrict__ partials, const unsigned char *__restrict__ mask)
+{
+    ami_grad_body<ND, MASKED, false>(vol, nullptr, theta, N, K, range, G, partials, mask);
+}
 template <int ND, bool MASKED>
 __global__ __launch_bounds__(TRX_BLOCK) void ami_grad_grids_kernel(trx_volumes vol, trx_moving_grid mg, const float *__restrict__ theta, unsigned N, int K,
                                                                      const float *__restrict__ range, const float *__restrict__ G, float *__restrict__ partials,
                                                                      const unsigned char *__restrict__ mask)
 {
-    constexpr int NT = ND * (ND + 1);
-    extern __shared__ float ami_g[];                // [K][K]
-    const int b = blockIdx.y, tid = threadIdx.x, KK = K * K;
-    for (int i = tid; i < KK; i += TRX_BLOCK) ami_g[i] = G[(size_t)b * KK + i];
-    __syncthreads();
-    const MiScale m = mi_scale(range, b, K);
-    float te[NT];
-    ami_theta_eff<ND>(theta + (size_t)b * TRX_PSTRIDE, mg, te);
-    trx_volumes mvol = vol;
-    mvol.D = mg.D; mvol.H = mg.H; mvol.W = mg.W;
-    const float *__restrict__ mov = vol.moving + (size_t)b * vol.moving_stride;
-    const float *__restrict__ tgt = vol.target + (size_t)b * vol.target_stride;
-    float vals[NT];
-#pragma unroll
-    for (int k = 0; k < NT; k++) vals[k] = 0.f;
-    const unsigned char *mk = MASKED ? mask + (size_t)b * N : nullptr;
-    const unsigned first = blockIdx.x * (unsigned)kMiChunk, last = min(N, first + (unsigned)kMiChunk);
-    for (VoxelWalk vw(first + tid, TRX_BLOCK, vol.H, vol.W); vw.i < last; vw.next(vol.H, vol.W)) {
-        if (!mi_counts<MASKED>(mk, vw.i)) continue;
-        const float xn = base_coord(vol.xn, vw.x, vol.W), yn = base_coord(vol.yn, vw.y, vol.H), zn = ND == 3 ? base_coord(vol.zn, vw.z, vol.D) : 0.f;
-        const AmiSample<ND> s = ami_sample<ND>(mvol, te, mov, vw.x, vw.y, vw.z, xn, yn, zn);
-        const float gw = mi_voxel_grad(ami_g, mi_voxel(__builtin_nontemporal_load(tgt + vw.i), s.v, m, K), K);
-#pragma unroll
-        for (int c = 0; c < ND; c++) {
-            const float q = gw * s.d[c];
-            float *row = vals + c * (ND + 1);
-            row[0] = fmaf(xn, q, row[0]);
-            row[1] = fmaf(yn, q, row[1]);
-            if constexpr (ND == 3) row[2] = fmaf(zn, q, row[2]);
-            row[ND] += q;
-        }
-    }
-    ami_block_sum_store<NT>(vals, partials + ((size_t)b * gridDim.x + blockIdx.x) * NT);
+    ami_grad_body<ND, MASKED, true>(vol, &mg, theta, N, K, range, G, partials, mask);
 }
 
 // The loop's epilogue, one block per pair: the pair's partial rows -> dL/dtheta, the loss of the table kernel, then the affine step's epilogue
@@ -326,15 +298,11 @@ __global__ __launch_bounds__(TRX_BLOCK) void affine_warp_grids_kernel(trx_volume
     ami_theta_eff<ND>(theta + (size_t)b * TRX_PSTRIDE, mg, th);
     for (VoxelWalk vw(blockIdx.x * TRX_BLOCK + threadIdx.x, gridDim.x * TRX_BLOCK, vol.H, vol.W); vw.i < nvox; vw.next(vol.H, vol.W)) {
         const float xn = base_coord(vol.xn, vw.x, vol.W), yn = base_coord(vol.yn, vw.y, vol.H), zn = ND == 3 ? base_coord(vol.zn, vw.z, vol.D) : 0.f;
-        if constexpr (ND == 3) {
-            const float ix = unnorm<3>(fmaf(th[1], yn, fmaf(th[0], xn, fmaf(th[2], zn, th[3]))), (float)Wm);
-            const float iy = unnorm<3>(fmaf(th[5], yn, fmaf(th[4], xn, fmaf(th[6], zn, th[7]))), (float)Hm);
-            const float iz = unnorm<3>(fmaf(th[9], yn, fmaf(th[8], xn, fmaf(th[10], zn, th[11]))), (float)Dm);
-            for (int ch = 0; ch < channels; ch++) o[ch * nvox + vw.i] = sample3(mov + ch * chan_stride, Dm, Hm, Wm, ix, iy, iz).v;
-        } else {
-            const float ix = unnorm<2>(fmaf(th[1], yn, fmaf(th[0], xn, th[2])), (float)Wm);
-            const float iy = unnorm<2>(fmaf(th[4], yn, fmaf(th[3], xn, th[5])), (float)Hm);
-            for (int ch = 0; ch < channels; ch++) o[ch * nvox + vw.i] = sample2(mov + ch * chan_stride, Hm, Wm, ix, iy).v;
+        float ic[ND];
+        affine_coord<ND>(th, xn, yn, zn, Dm, Hm, Wm, ic);
+        for (int ch = 0; ch < channels; ch++) {
+            if constexpr (ND == 3) o[ch * nvox + vw.i] = sample3(mov + ch * chan_stride, Dm, Hm, Wm, ic[0], ic[1], ic[2]).v;
+            else o[ch * nvox + vw.i] = sample2(mov + ch * chan_stride, Hm, Wm, ic[0], ic[1]).v;
         }
     }
 }

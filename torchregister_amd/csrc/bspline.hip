@@ -818,12 +818,16 @@ extern "C" size_t trx_bspline_mi_workspace_bytes(int ndim, int B, int D, int H, 
     return l.ws_bytes;
 }
 
-extern "C" int trx_bspline_mi_run(const trx_volumes *vol, const trx_mi_cfg *cfg, const trx_opt_cfg *opt, const trx_bspline_state *st, const int *spacing,
-                                  int iters, void *workspace, size_t workspace_bytes, void *stream)
+// Both mutual-information loops.  mg == nullptr: one lattice, the warp is trx_flow_warp.  Otherwise the deformation is composed with the initial affine
+// `theta`, the moving image on a lattice of its own (csrc/affine_flow.hip): the same checks, workspace and launches with the composed
+// warp and its backward where trx_flow_warp / trx_flow_warp_backward stand.  theta is read on the device on every iteration and never written.
+static int bspline_mi_run_impl(const trx_volumes *vol, const trx_moving_grid *mg, const float *theta, const trx_mi_cfg *cfg, const trx_opt_cfg *opt,
+                               const trx_bspline_state *st, const int *spacing, int iters, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!cfg || !cfg->range) return TRX_ERR_ARG;
     BsGeom g;
     int rc = bspline_run_checks(vol, opt, st, spacing, iters, workspace, &g);
+    if (rc == TRX_OK && mg) rc = ami_grid_check(vol->ndim, mg);
     if (rc != TRX_OK) return rc;
     BsMiLayout l;
     if ((rc = bspline_mi_layout(g, cfg->bins, &l)) != TRX_OK) return rc;
@@ -835,41 +839,25 @@ extern "C" int trx_bspline_mi_run(const trx_volumes *vol, const trx_mi_cfg *cfg,
     char *ws = (char *)workspace;
     float *mloss = (float *)(ws + g.terms_offset), *warped = (float *)(ws + l.o_warped), *go = (float *)(ws + l.o_go);
     return bspline_loop(g, vol, opt, st, iters, mloss, 1, workspace, (hipStream_t)stream, [&]() {
-        int r = trx_flow_warp(vol, st->flow, 1, warped, stream);
+        int r = mg ? trx_affine_flow_warp(vol, mg, theta, st->flow, 1, warped, stream) : trx_flow_warp(vol, st->flow, 1, warped, stream);
         if (r != TRX_OK) return r;
         r = trx_mi_loss_grad(vol->target, warped, vol->ndim, vol->B, vol->D, vol->H, vol->W, cfg, mloss, go, ws + l.o_mi, l.mi_bytes, stream);
         if (r != TRX_OK) return r;
-        return trx_flow_warp_backward(vol, st->flow, 1, go, st->dflow, stream);
+        return mg ? trx_affine_flow_warp_backward(vol, mg, theta, st->flow, 1, go, st->dflow, stream) : trx_flow_warp_backward(vol, st->flow, 1, go, st->dflow, stream);
     });
 }
 
-// trx_bspline_mi_run through an initial affine, the moving image on a lattice of its own (csrc/affine_flow.hip): the same loop,
-// workspace and launches with the composed warp and its backward where trx_flow_warp / trx_flow_warp_backward stand.  theta is read on the device on
-// every iteration and never written.
+extern "C" int trx_bspline_mi_run(const trx_volumes *vol, const trx_mi_cfg *cfg, const trx_opt_cfg *opt, const trx_bspline_state *st, const int *spacing,
+                                  int iters, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return bspline_mi_run_impl(vol, nullptr, nullptr, cfg, opt, st, spacing, iters, workspace, workspace_bytes, stream);
+}
+
 extern "C" int trx_bspline_mi_run_grids(const trx_volumes *vol, const trx_moving_grid *mg, const float *theta, const trx_mi_cfg *cfg, const trx_opt_cfg *opt,
                                         const trx_bspline_state *st, const int *spacing, int iters, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!cfg || !cfg->range || !mg || !theta) return TRX_ERR_ARG;
-    BsGeom g;
-    int rc = bspline_run_checks(vol, opt, st, spacing, iters, workspace, &g);
-    if (rc == TRX_OK) rc = ami_grid_check(vol->ndim, mg);
-    if (rc != TRX_OK) return rc;
-    BsMiLayout l;
-    if ((rc = bspline_mi_layout(g, cfg->bins, &l)) != TRX_OK) return rc;
-    if (!std::isfinite(cfg->alpha)) return TRX_ERR_ARG;
-    const size_t nvox = (size_t)vol->D * vol->H * vol->W;
-    if (vol->B > 1 && vol->target_stride != nvox) return TRX_ERR_ARG;   // the histogram kernels take a dense [B][D][H][W] target
-    if (workspace_bytes < l.ws_bytes) return TRX_ERR_WORKSPACE;
-    if (st->losses && iters > st->losses_capacity) return TRX_ERR_CAPACITY;
-    char *ws = (char *)workspace;
-    float *mloss = (float *)(ws + g.terms_offset), *warped = (float *)(ws + l.o_warped), *go = (float *)(ws + l.o_go);
-    return bspline_loop(g, vol, opt, st, iters, mloss, 1, workspace, (hipStream_t)stream, [&]() {
-        int r = trx_affine_flow_warp(vol, mg, theta, st->flow, 1, warped, stream);
-        if (r != TRX_OK) return r;
-        r = trx_mi_loss_grad(vol->target, warped, vol->ndim, vol->B, vol->D, vol->H, vol->W, cfg, mloss, go, ws + l.o_mi, l.mi_bytes, stream);
-        if (r != TRX_OK) return r;
-        return trx_affine_flow_warp_backward(vol, mg, theta, st->flow, 1, go, st->dflow, stream);
-    });
+    if (!mg || !theta) return TRX_ERR_ARG;      // (with the impl's first refusal: one return code, as before)
+    return bspline_mi_run_impl(vol, mg, theta, cfg, opt, st, spacing, iters, workspace, workspace_bytes, stream);
 }
 
 // Diffeomorphic free-form deformation (csrc/svf.hip): the expanded lattice is a stationary velocity field.  Behind the loop's workspace lie

@@ -190,6 +190,22 @@ __device__ __forceinline__ float unnorm(float c, float S)
     else return fmaf(c + 1.0f, 0.5f * S, -0.5f);
 }
 
+// The un-normalised source coordinate ic (x, y(, z) order) of the normalised position (xn, yn, zn) under theta `th` (2 x 3 or 3 x 4, row-major) in a
+// sampled volume of D x H x W.  The one statement of this fma nesting outside the F1 kernels of affine.hip: the fused mutual-information passes, the
+// cross-lattice warp, the composed warp and the lattice warp are bit-equal to each other because they all call it.
+template <int ND>
+__device__ __forceinline__ void affine_coord(const float *__restrict__ th, float xn, float yn, float zn, int D, int H, int W, float (&ic)[ND])
+{
+    if constexpr (ND == 3) {
+        ic[0] = unnorm<3>(fmaf(th[1], yn, fmaf(th[0], xn, fmaf(th[2], zn, th[3]))), (float)W);
+        ic[1] = unnorm<3>(fmaf(th[5], yn, fmaf(th[4], xn, fmaf(th[6], zn, th[7]))), (float)H);
+        ic[2] = unnorm<3>(fmaf(th[9], yn, fmaf(th[8], xn, fmaf(th[10], zn, th[11]))), (float)D);
+    } else {
+        ic[0] = unnorm<2>(fmaf(th[1], yn, fmaf(th[0], xn, th[2])), (float)W);
+        ic[1] = unnorm<2>(fmaf(th[4], yn, fmaf(th[3], xn, th[5])), (float)H);
+    }
+}
+
 // base coordinate of affine_grid(align_corners=False)
 __device__ __forceinline__ float base_coord(const float *__restrict__ tab, int i, int S)
 {
