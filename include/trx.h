@@ -57,7 +57,9 @@ extern "C" {
  *        affine mutual information and the forward warp for a moving image on a lattice and voxel size of its own) - new entry points and one new
  *        struct only.
  *        Later addition under the same number: trx_affine_flow_warp, trx_affine_flow_warp_backward, trx_bspline_mi_run_grids (a flow composed with an
- *        initial affine and sampled once in a moving image on its own lattice; the B-spline mutual-information loop over it) - new entry points only. */
+ *        initial affine and sampled once in a moving image on its own lattice; the B-spline mutual-information loop over it) - new entry points only.
+ *        Later addition under the same number: trx_spline_workspace_bytes, trx_spline_coefficients, trx_transform_resample (nearest-neighbour and cubic
+ *        B-spline resampling through the final transform) - new entry points only. */
 #define TRX_VERSION 240
 #define TRX_PSTRIDE 12  /* floats per pair in theta / param / adam / best_theta arrays */
 
@@ -625,7 +627,7 @@ int trx_affine_mi_run_grids(const trx_volumes *vol, const trx_moving_grid *mg /*
                             const trx_affine_state *st, int iters, void *workspace, size_t workspace_bytes, void *stream);
 /* out[B][channels][target lattice] = the sample of moving[B][channels][moving lattice] at theta_eff; channels share coordinates (trx_affine_warp's
  * layout: vol->moving_stride between batch items).  vol->target is not read.  Equal sizes and scale == 1: trx_affine_warp itself, the same bits.  No
- * backward and no nearest-neighbour form. */
+ * backward; the nearest-neighbour and cubic forms are trx_transform_resample. */
 int trx_affine_warp_grids(const trx_volumes *vol, const trx_moving_grid *mg /*[host]*/, const float *theta, int channels, float *out, void *stream);
 
 /* ---- A deformation composed with an initial affine, sampled ONCE (what elastix, NiftyReg and ANTs do with the transform of the
@@ -642,7 +644,7 @@ int trx_affine_warp_grids(const trx_volumes *vol, const trx_moving_grid *mg /*[h
  * lattices: trx_flow_warp up to the rounding of the coordinate's round trip through the normalised cube.
  * Backward: dflow_c(x) = sum_ch grad_out_ch(x) sum_r (dsample_ch / di_r) (S_m,r / 2) theta_eff[r][c] (2 / S_t,c), c converted between the flow's
  * z, y, x channel order and theta's x, y, z column order.  A gather per target voxel like the forward: no scatter, no atomics, no workspace, the same
- * bits on every call.  No gradient with respect to theta or the moving image, and no nearest-neighbour form.  vol->target is not read.  2-D and 3-D.
+ * bits on every call.  No gradient with respect to theta or the moving image; the nearest-neighbour and cubic forms are trx_transform_resample.  vol->target is not read.  2-D and 3-D.
  * Per voxel in 3-D the forward moves 12 B flow + 4 B out per channel + the gather, the backward 12 B flow + 4 B grad_out per channel + 12 B dflow +
  * the gather.  Refusals before any HIP call: those of trx_flow_warp / trx_flow_warp_backward, those of trx_moving_grid above, theta NULL, channels < 1.
  * CPU restatement: tests/affine_flow_ref.py. */
@@ -659,6 +661,39 @@ int trx_affine_flow_warp_backward(const trx_volumes *vol, const trx_moving_grid 
 int trx_bspline_mi_run_grids(const trx_volumes *vol, const trx_moving_grid *mg /*[host]*/, const float *theta, const trx_mi_cfg *cfg,
                              const trx_opt_cfg *opt, const trx_bspline_state *st, const int *spacing /*[host]*/, int iters, void *workspace,
                              size_t workspace_bytes, void *stream);
+
+/* ---- Nearest-neighbour and cubic B-spline resampling through the final transform (elastix FinalBSplineInterpolationOrder 3,
+ * NiftyReg -inter 3 / -inter 0, ANTs BSpline / NearestNeighbor).  Extension.  Later addition under TRX_VERSION 240: new entry points only.
+ * Coefficients: c = the coefficients of the interpolating cubic B-spline of s with whole-sample mirror boundaries (index i outside 0 .. n-1 reflects about
+ * 0 and n-1, period 2 (n-1)) - per axis of n > 1 voxels, with z = sqrt(3) - 2, the recursive filter
+ *   c+[0] = (s[0] + z^(n-1) s[n-1] + sum_{k=1..n-2} (z^k + z^(2n-2-k)) s[k]) / (1 - z^(2n-2)),  c+[k] = s[k] + z c+[k-1],
+ *   c-[n-1] = z / (z^2 - 1) (c+[n-1] + z c+[n-2]),  c-[k] = z (c-[k+1] - c+[k]),  c = 6 c-
+ * which the kernels evaluate as its impulse response, c[k] = sum_{|j| <= 16} sqrt(3) z^|j| s[mirror(k - j)] (the truncation: 4.5e-9 of the range; every
+ * output independent of the others).  An axis of one voxel is left alone.  src, coef: N volumes [D][H][W] fp32 contiguous (2-D: ndim 2, D = 1; N = batch x
+ * channels, at most 65535); they must not be the same buffer.  One launch per axis longer than one voxel (at least one), each reading and writing every
+ * voxel once; the workspace holds the intermediate volume when there is more than one pass, so trx_spline_workspace_bytes may answer 0; SIZE_MAX =
+ * arguments rejected (ndim outside 2 .. 3, a size < 1, N outside 1 .. 65535, D != 1 in 2-D, >= 2^31 voxels per volume).
+ * Refusals before any HIP call: TRX_ERR_ARG (src or coef NULL, src == coef, the sizes above), TRX_ERR_NDIM, TRX_ERR_WORKSPACE. */
+size_t trx_spline_workspace_bytes(int ndim, int N, int D, int H, int W);
+int trx_spline_coefficients(const float *src, float *coef, int ndim, int N, int D, int H, int W, void *workspace, size_t workspace_bytes, void *stream);
+/* out[B][channels][target lattice] = vol->moving [B][channels][sampled lattice] (vol->moving_stride elements between batch items) sampled at the
+ * positions of exactly one of the two existing chains; vol describes the TARGET lattice as for trx_affine_flow_warp, vol->target is not read.
+ *   theta == NULL: p = x + flow(x), one fp32 add per axis (trx_flow_warp); the sampled lattice is the target's; mg must be NULL.
+ *   theta != NULL: trx_affine_flow_warp's closed form p -> n -> m = theta_eff . (n, 1) -> i with the MOVING sizes, theta_eff = theta (.) mg->scale;
+ *                  flow == NULL: zero flow; mg == NULL: the moving lattice is the target's and the scale is 1.  (The plain affine, the two-lattice affine
+ *                  and the composed warp.)
+ * order 0: out = moving[rint(i)] per axis (half to even), 0 where a rounded index lies outside - trx_flow_warp's TRX_FLAG_NEAREST rule.
+ * order 3: vol->moving holds the COEFFICIENTS (trx_spline_coefficients; made once, reusable for any number of transforms).  Per axis i0 = floor(i),
+ *          r = i - i0, taps i0 - 1 .. i0 + 2 mirrored as above, weights ((1-r)^3, 3r^3 - 6r^2 + 4, -3r^3 + 3r^2 + 3r + 1, r^3) / 6; out = the
+ *          tensor-product sum over the 4^ndim taps; out = 0 where i_a < -0.5 or i_a > S_a - 0.5 on some axis (the zero padding of every other warp
+ *          here; a NaN position too).  The spline reproduces the samples at lattice points and overshoots their range near edges: no clamp.
+ * Order 1 is deliberately not an order of this entry point: trx_affine_warp / _grids, trx_flow_warp and trx_affine_flow_warp are the linear form.
+ * Channels share coordinates and weights.  A gather per target voxel: no atomics, no workspace, no host sync, the same bits on every call, and a
+ * pair's result does not depend on its batch.  Not differentiable.  Refusals before any HIP call: those of trx_affine_warp about vol, those of
+ * trx_moving_grid when mg is given, TRX_ERR_ARG for out NULL, theta and flow both NULL, mg without theta, channels < 1, order not 0 or 3.
+ * CPU restatement: tests/spline_ref.py. */
+int trx_transform_resample(const trx_volumes *vol, const trx_moving_grid *mg /*[host], nullable*/, const float *theta /*nullable*/,
+                           const float *flow /*nullable*/, int channels, int order, float *out /*[B][channels][*S_t]*/, void *stream);
 
 /* ---- Stationary velocity field (Arsigny et al. 2006; NiftyReg's -vel, VoxelMorph-diff's VecInt; extension: the reference has no such model, its flows
  * are displacements, ref:warpings.py:178-242).  Fields are [B][ndim][D][H][W] fp32 contiguous (2-D: [B][2][H][W], D = 1), voxel units and channel order

@@ -7,7 +7,7 @@ HIP kernels in lib/libtrx.so (C ABI: include/trx.h).  There is no CPU fallback.
 __version__ = "0.2.3"   # = the reference package version this host layer mirrors (ref:src/TorchRegister/__init__.py:4); C ABI: trx_version()
 
 from ._engine import (AffineMISolver, AffineSolver, BSplineSolver, FlowSolver, LossSpec, SlabFlowSolver, SlabPeers, bspline_bending, bspline_expand, bspline_grid, bspline_reduce, svf_exp, svf_exp_backward,  # noqa: F401
-                      affine_flow_warp, affine_flow_warp_backward, affine_mi_loss_grad, grid_scale, run_slabs_lockstep)
+                      affine_flow_warp, affine_flow_warp_backward, affine_mi_loss_grad, grid_scale, resample, run_slabs_lockstep, spline_coefficients)
 from .pyramid import pyramid, pyramid_shapes, upsample_flow  # noqa: F401
 from .sharding import register_sharded  # noqa: F401
 from .torchregister import Register  # noqa: F401

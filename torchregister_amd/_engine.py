@@ -1667,6 +1667,111 @@ def affine_flow_warp(x, theta, flow, scale=None):
     return _AffineFlowWarpFn.apply(x, theta, flow, scale)
 
 
+INTERPOLATIONS = ("nearest", "linear", "cubic")
+
+
+def check_interpolation(value):
+    """ValueError unless `value` is one of INTERPOLATIONS; host only."""
+    if value not in INTERPOLATIONS:
+        raise ValueError(f"interpolation must be 'nearest', 'linear' or 'cubic', got {value!r}")
+    return value
+
+
+def spline_coefficients(x):
+    """The coefficients of the interpolating cubic B-spline of x [B,C,*spatial] (fp32, GPU) with whole-sample mirror boundaries, the same shape
+    (extension, include/trx.h: trx_spline_coefficients; = scipy.ndimage.spline_filter(order=3, mode='mirror') per volume).  What resample(...,
+    interpolation='cubic') samples; an axis of one voxel is left alone.  Not differentiable."""
+    if not isinstance(x, torch.Tensor) or x.dim() not in (4, 5):
+        raise ValueError(f"expected [B,C,H,W] or [B,C,D,H,W], got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+    _require_gpu(x, "x")
+    lib = _lib.load()
+    src = x.detach().contiguous()
+    nd, n, dhw = src.dim() - 2, src.shape[0] * src.shape[1], _dhw(tuple(src.shape[2:]))
+    nbytes = lib.trx_spline_workspace_bytes(nd, n, *dhw)
+    if nbytes == ctypes.c_size_t(-1).value:
+        raise ValueError(f"spline_coefficients takes 1 .. 65535 volumes (batch x channels) of 1 .. 2^31 - 1 voxels, got {tuple(src.shape)}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=src.device)
+    out = torch.empty_like(src)
+    with torch.cuda.device(src.device):
+        rc = lib.trx_spline_coefficients(_lib.ptr(src), _lib.ptr(out), nd, n, *dhw, _lib.ptr(ws) if nbytes else None, nbytes, _lib.current_stream(src.device))
+    _lib.check(rc, "trx_spline_coefficients")
+    return out
+
+
+def _resample_args(x, theta, flow, size, scale, interpolation):
+    """What resample refuses, on the host, before any device work: returns (target spatial shape, scale as fp32 on the CPU or None)."""
+    check_interpolation(interpolation)
+    if not isinstance(x, torch.Tensor) or x.dim() not in (4, 5):
+        raise ValueError(f"expected x [B,C,H,W] or [B,C,D,H,W], got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+    if theta is None and flow is None:
+        raise ValueError("resample needs a transform: theta, flow or both")
+    nd, B = x.dim() - 2, x.shape[0]
+    if theta is not None and (not isinstance(theta, torch.Tensor) or theta.dim() != 3 or tuple(theta.shape[1:]) != (nd, nd + 1) or theta.shape[0] not in (1, B)):
+        raise ValueError(f"expected theta of shape {(B, nd, nd + 1)} or {(1, nd, nd + 1)}, got {tuple(theta.shape) if isinstance(theta, torch.Tensor) else type(theta).__name__}")
+    if scale is not None:
+        if theta is None:
+            raise ValueError("scale multiplies theta (grid_scale): it needs a theta")
+        scale = torch.as_tensor(scale).detach().to("cpu", torch.float32)
+        if tuple(scale.shape) != (nd, nd + 1):
+            raise ValueError(f"expected a scale of shape {(nd, nd + 1)}, got {tuple(scale.shape)}")
+    if size is not None:
+        size = tuple(int(s) for s in size)
+        if len(size) != nd or min(size) < 1:
+            raise ValueError(f"expected a size of {nd} positive entries, got {size}")
+    if flow is None:
+        return (tuple(x.shape[2:]) if size is None else size), scale
+    if not isinstance(flow, torch.Tensor) or flow.dim() != x.dim() or flow.shape[1] != nd or flow.shape[0] not in (1, B):
+        raise ValueError(f"expected flow [{B}|1,{nd},*target spatial], got {tuple(flow.shape) if isinstance(flow, torch.Tensor) else type(flow).__name__}")
+    target = tuple(flow.shape[2:])
+    if size is not None and size != target:
+        raise ValueError(f"size {size} is not the flow's lattice {target}")
+    if theta is None and target != tuple(x.shape[2:]):
+        raise ValueError(f"without theta the flow lives on x's own lattice {tuple(x.shape[2:])}, got a flow on {target}")
+    return target, scale
+
+
+def resample(x, *, theta=None, flow=None, size=None, scale=None, interpolation="cubic"):
+    """x [B,C,*spatial] (fp32, GPU) carried through a finished transform with the interpolation of the caller's choice (extension, include/trx.h:
+    trx_transform_resample) -> [B,C,*target spatial].  The transform is theta [B|1,nd,nd+1], flow [B|1,nd,*target spatial] (target voxels, channel i
+    along spatial dim i) or both - the positions are those of affine_warp / flow_warp / affine_flow_warp: with flow alone x lives on the flow's
+    lattice, with theta it may have a lattice of its own; size = the output lattice when only theta is given (default: x's own); scale as for
+    affine_flow_warp (grid_scale; None = theta is the effective one).
+    interpolation: 'nearest' - x[rint(position)], half to even, 0 where the rounded index lies outside: what carries a label map, an atlas or a
+    mask without inventing values; 'linear' - the existing warps themselves, bit for bit; 'cubic' (default) - the interpolating cubic B-spline
+    of x with mirror boundaries (spline_coefficients, made on every call), 0 where the position lies more than half a voxel outside x.  The cubic
+    form reproduces x at lattice points and overshoots x's range near edges; nothing is clamped.
+    Not differentiable ('linear' keeps what the warp it dispatches to offers).  ValueError before any device work for an unknown interpolation,
+    for neither theta nor flow, and for shapes that do not fit."""
+    target, scale = _resample_args(x, theta, flow, size, scale, interpolation)
+    B, C, nd, dev = x.shape[0], x.shape[1], x.dim() - 2, x.device
+    if flow is not None and flow.shape[0] != B:
+        flow = flow.expand(B, *flow.shape[1:])
+    if interpolation == "linear":
+        if theta is None:
+            return flow_warp(x, flow)
+        if flow is not None:
+            return affine_flow_warp(x, theta, flow, scale)
+        th = theta.detach().to(dev, torch.float32).expand(B, nd, nd + 1)
+        return affine_warp(th if scale is None else th * scale.to(dev), x, size=target)
+    _require_gpu(x, "x")
+    if flow is not None:
+        _require_gpu(flow, "flow")
+    lib = _lib.load()
+    src = x.detach().contiguous()
+    if interpolation == "cubic":
+        src = spline_coefficients(src)
+    th = None if theta is None else _initial_theta(theta, B, nd, dev)
+    fl = None if flow is None else flow.detach().contiguous()
+    v = _volumes(src, None, src[0].numel(), 0, target)
+    mg = None if theta is None else _moving_grid(tuple(src.shape[2:]), scale)
+    out = torch.empty((B, C) + target, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.trx_transform_resample(ctypes.byref(v), None if mg is None else ctypes.byref(mg), _lib.ptr(th), _lib.ptr(fl), C,
+                                        3 if interpolation == "cubic" else 0, _lib.ptr(out), _lib.current_stream(dev))
+    _lib.check(rc, "trx_transform_resample")
+    return out
+
+
 def affine_mi_loss_grad(moving, target, theta, rng, bins=32, alpha=1.0, normalized=False, need_grad=True, mask=None, scale=None):
     """Mutual information of (target, affine warp of moving by theta) and its gradient with respect to theta without a warped volume (extension,
     include/trx.h: trx_affine_mi_loss_grad): moving / target [B,1,*spatial] fp32 on the GPU, theta [B,nd,nd+1], rng [B,4] (mi_range), mask (see

@@ -174,6 +174,9 @@ SIGNATURES = {
     "trx_affine_flow_warp_backward": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), _P, _P, ctypes.c_int, _P, _P, _P]),
     "trx_bspline_mi_run_grids": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), _P, ctypes.POINTER(MICfg), ctypes.POINTER(OptCfg),
                                                 ctypes.POINTER(BSplineState), c_int_p, ctypes.c_int, _P, ctypes.c_size_t, _P]),
+    "trx_spline_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "trx_spline_coefficients": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 5 + [_P, ctypes.c_size_t, _P]),
+    "trx_transform_resample": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]),
     "trx_svf_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 6),
     "trx_svf_exp": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 7 + [_P, ctypes.c_size_t, _P]),
     "trx_svf_exp_backward": (ctypes.c_int, [_P, _P, _P] + [ctypes.c_int] * 7 + [_P, ctypes.c_size_t, _P]),

@@ -20,18 +20,6 @@
 
 namespace trx {
 
-// The sample coordinate (x, y, z order) of the voxel at (x, y, z) displaced by f (the flow's channel order: z, y, x; 2-D: y, x)
-template <int ND>
-__device__ __forceinline__ void af_coord(const float (&te)[ND * (ND + 1)], const float (&f)[ND], int x, int y, int z, int D, int H, int W, int Dm, int Hm,
-                                         int Wm, float (&ic)[ND])
-{
-    const float xn = fmaf(2.0f, (float)x + f[ND - 1], 1.0f) / (float)W - 1.0f;
-    const float yn = fmaf(2.0f, (float)y + f[ND - 2], 1.0f) / (float)H - 1.0f;
-    float zn = 0.f;
-    if constexpr (ND == 3) zn = fmaf(2.0f, (float)z + f[0], 1.0f) / (float)D - 1.0f;
-    affine_coord<ND>(te, xn, yn, zn, Dm, Hm, Wm, ic);
-}
-
 // S_m,r / S_t,c in theta's [row r][column c] order (x, y, z), formed on the host in fp32
 struct AfRatios {
     float v[3][3];

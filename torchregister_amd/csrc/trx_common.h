@@ -206,6 +206,20 @@ __device__ __forceinline__ void affine_coord(const float *__restrict__ th, float
     }
 }
 
+// The composed warp's sample coordinate (x, y, z order) of the target voxel at (x, y, z) displaced by f (the flow's channel order: z, y, x; 2-D: y, x):
+// the closed-form base coordinate at the non-integer position, then affine_coord with the MOVING sizes.  One statement for trx_affine_flow_warp, its
+// backward and trx_transform_resample, which are checked against each other.
+template <int ND>
+__device__ __forceinline__ void af_coord(const float (&te)[ND * (ND + 1)], const float (&f)[ND], int x, int y, int z, int D, int H, int W, int Dm, int Hm,
+                                         int Wm, float (&ic)[ND])
+{
+    const float xn = fmaf(2.0f, (float)x + f[ND - 1], 1.0f) / (float)W - 1.0f;
+    const float yn = fmaf(2.0f, (float)y + f[ND - 2], 1.0f) / (float)H - 1.0f;
+    float zn = 0.f;
+    if constexpr (ND == 3) zn = fmaf(2.0f, (float)z + f[0], 1.0f) / (float)D - 1.0f;
+    affine_coord<ND>(te, xn, yn, zn, Dm, Hm, Wm, ic);
+}
+
 // base coordinate of affine_grid(align_corners=False)
 __device__ __forceinline__ float base_coord(const float *__restrict__ tab, int i, int S)
 {

@@ -9,7 +9,7 @@ U-Net-generated flow, 'direct' = the flow field itself is the parameter), levels
 import torch
 from torch import cat
 
-from ._engine import _bending_weight, _mask_u8, _squarings, affine_warp, grid_scale
+from ._engine import _bending_weight, _mask_u8, _squarings, affine_warp, check_interpolation, grid_scale, resample
 from .pyramid import level_theta, pyramid, pyramid_masks, pyramid_shapes, upsample_flow
 from .warpings import (GRIDS_SUPPORT, INITIAL_SUPPORT, MASK_SUPPORT, affine_register, device_loop_settings, flow_register, get_affine_warp, resolve_initial, rigid_register,
                        two_lattices)
@@ -313,21 +313,29 @@ class Register():
                 print(f"[{self.mode}] level {k + 1}/{L} {tuple(shapes[k])}: {epochs[k]} iterations, lr {lrs[k]:g}, " +
                       (f"loss {ls[0].item():.6g} -> {ls[-1].item():.6g} (min {ls.min().item():.6g})" if len(ls) else "no iterations"))
 
-    def __call__(self, moving):
+    def __call__(self, moving, interpolation='linear'):
         '''
         Warp moving [B,c,x,y(,z)] with the deformation found by optim: one fused launch for all
         channels (the reference loops over channels, ref:torchregister.py:123-128).
+        interpolation (extension): 'linear' - the path above, unchanged; 'nearest' (label maps, atlases, masks) / 'cubic' (the final
+        resample of an image) - resample() with the registration's own transform: theta onto .target_shape for 'rigid' / 'affine', the
+        flow - composed with .initial when optim(initial=...) set one - for 'flow'.  Those two are not differentiable.
         '''
+        check_interpolation(interpolation)
         if self.theta is None:
             raise RuntimeError("call optim() first")
         if self.mode == 'flow':
-            return self.warp(moving)
-        return self.warp(self.theta.detach(), moving)
+            return self.warp(moving) if interpolation == 'linear' else self.warp(moving, interpolation=interpolation)
+        if interpolation == 'linear':
+            return self.warp(self.theta.detach(), moving)
+        return resample(moving, theta=self.theta.detach(), size=self.target_shape, interpolation=interpolation)
 
-    def inverse(self, x):
+    def inverse(self, x, interpolation='linear'):
         '''
         Warp x [B,c,x,y(,z)] with the inverse of the deformation found by optim, exp(-velocity) (diffeomorphic=True only).
+        interpolation: as for __call__.
         '''
+        check_interpolation(interpolation)
         if self.inverse_flow is None:
             raise RuntimeError("inverse() needs diffeomorphic=True and optim() first")
-        return self._inverse_warp(x)
+        return self._inverse_warp(x) if interpolation == 'linear' else self._inverse_warp(x, interpolation=interpolation)

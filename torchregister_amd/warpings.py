@@ -697,11 +697,18 @@ class flow_register(nn.Module):
         if debug:
             print("Optimization ended with status: %s" % message)
 
-    def deform(self, x):
-        return self._deform(x, self.flow)
+    def deform(self, x, interpolation="linear"):
+        """x warped with the flow of the last forward.  interpolation (extension): 'linear' - today's path; 'nearest' / 'cubic' -
+        _engine.resample with that flow, composed with `.initial` when optimize(initial=...) set one."""
+        if _engine.check_interpolation(interpolation) == "linear":
+            return self._deform(x, self.flow)
+        return _engine.resample(x, theta=None if self.initial is None else self.initial.to(x.device), flow=self.flow, interpolation=interpolation)
 
-    def inverse(self, x):
-        """x warped with exp(-velocity), the inverse of the deformation `deform` applies (diffeomorphic=True only)."""
+    def inverse(self, x, interpolation="linear"):
+        """x warped with exp(-velocity), the inverse of the deformation `deform` applies (diffeomorphic=True only).  interpolation: as for deform."""
+        _engine.check_interpolation(interpolation)
         if self.inverse_flow is None:
             raise RuntimeError("inverse() needs diffeomorphic=True and a finished optimize()")
-        return self.warp(x, self.inverse_flow)
+        if interpolation == "linear":
+            return self.warp(x, self.inverse_flow)
+        return _engine.resample(x, flow=self.inverse_flow, interpolation=interpolation)
