@@ -512,7 +512,7 @@ int trx_bspline_run(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_
  *             beta' = (-(1 - r)^2, 3r^2 - 4r, -3r^2 + 2r + 1, r^2) / 2.  The mask is inclusive (torch's clamp backward); at a voxel exactly on an
  *             end of the range the function is only one-sidedly differentiable.  The target receives no gradient.
  * Ranges are the caller's: the hot paths take the target's min / max and the moving image's min / max widened to contain 0 (the value of the
- * zero-padded warp outside the field of view) once per optimisation.  Values outside the range fall into the end bins with a zero gradient.
+ * zero-padded warp outside the field of view; not widened under the overlap rule of trx_moving_grid, which counts no padded sample) once per optimisation.  Values outside the range fall into the end bins with a zero gradient.
  * The histogram is accumulated in fixed point (2^31 units per voxel, the fp32 weights converted to units, the largest of the four as the remainder so
  * that every voxel adds exactly one) with 64-bit integer adds, LDS and global: beyond the fp32 rounding of the weights,
  * |P[a][k] - exact| <= 1.5 * 2^-31 n[a][k] / N for the n[a][k] voxels that touch the cell, at most 3 * 2^-31 summed over the table.  No float atomics; entropies in fp64 in a fixed order: the same bits on every call, and a pair's result does not depend on
@@ -620,7 +620,22 @@ int trx_affine_mi_run(const trx_volumes *vol, const trx_mi_cfg *cfg, const trx_o
 typedef struct {
     int D, H, W;                 /* the MOVING lattice (D = 1 for ndim 2) */
     float scale[TRX_PSTRIDE];    /* theta's own layout, row-major [ndim][ndim + 1]; entries past ndim (ndim + 1) are not read */
+    int overlap;                 /* 0: every target voxel counts, its sample zero-padded (the launches and bits of before).  Otherwise the overlap rule
+                                  * below.  Later addition under TRX_VERSION 240, like `mask`: a caller built against the shorter struct must zero both */
+    const unsigned char *mask;   /* device [B][D][H][W] of THIS (moving) lattice, dense, nullable; non-zero = the moving voxel counts.  Needs overlap != 0
+                                  * (TRX_ERR_ARG otherwise).  Read on the device on every evaluation: it must outlive the call / run */
 } trx_moving_grid;
+/* The overlap rule (elastix -mMask and its discarded samples, NiftyReg -fmask / NaN padding, ITK's Mattes metric): with
+ * mg->overlap != 0, target voxel v of pair b with un-normalised moving coordinate i (x, y(, z)), formed exactly as the sampling kernel forms it, is
+ *   valid(v) = (cfg->mask at v, if any)  and  0 <= i_a <= S_m,a - 1 on every axis a  and  (mg->mask at rint(i) != 0, if any)
+ * (rint per axis, half to even - in range by the second condition; a NaN coordinate is invalid).  All 2^ndim corners of a valid sample lie in the moving
+ * volume: no zero is blended into a counted sample.  Histogram, P, G and loss are trx_mi_loss_grad's masked definition with M_b = {v : valid(v)}:
+ * sum(counts[b]) = N_valid 2^31 exactly, N_valid = 0 gives loss 0 and gradient 0.  The gradient treats validity as constant (ITK, elastix): dtheta / dflow
+ * are the masked chain's with mask = valid at the current transform, so the loss is piecewise smooth and jumps by O(1 / N_valid) when a sample crosses
+ * a border plane.  Ranges are the caller's; with the rule on the hot paths take the moving image's own min / max (inside mg->mask), NOT widened to 0.
+ * Honoured by trx_affine_mi_loss_grad_grids and trx_affine_mi_run_grids (a third instance of the two fused passes: the sample is rejected after its
+ * coordinate is formed and before anything is gathered; the same launches, the same workspace) and by trx_bspline_mi_run_grids (below); every other
+ * entry point that takes a trx_moving_grid reads neither member. */
 int trx_affine_mi_loss_grad_grids(const trx_volumes *vol, const trx_moving_grid *mg /*[host]*/, const trx_mi_cfg *cfg, const float *theta, float *loss,
                                   float *dtheta /*nullable*/, void *workspace, size_t workspace_bytes, void *stream);
 int trx_affine_mi_run_grids(const trx_volumes *vol, const trx_moving_grid *mg /*[host]*/, const trx_mi_cfg *cfg, const trx_opt_cfg *opt,
@@ -661,6 +676,16 @@ int trx_affine_flow_warp_backward(const trx_volumes *vol, const trx_moving_grid 
 int trx_bspline_mi_run_grids(const trx_volumes *vol, const trx_moving_grid *mg /*[host]*/, const float *theta, const trx_mi_cfg *cfg,
                              const trx_opt_cfg *opt, const trx_bspline_state *st, const int *spacing /*[host]*/, int iters, void *workspace,
                              size_t workspace_bytes, void *stream);
+/* With mg->overlap != 0 each iteration of trx_bspline_mi_run_grids is: composed warp -> trx_affine_flow_valid -> trx_mi_loss_grad with a copy of cfg
+ * whose mask is the validity bytes -> composed warp backward (grad_warped is 0 outside a mask, so dflow is 0 at an invalid voxel).  The B N validity
+ * bytes lie behind the loop's workspace: trx_bspline_mi_grids_workspace_bytes is then the query (mg == NULL or overlap == 0: it equals
+ * trx_bspline_mi_workspace_bytes); one byte short is TRX_ERR_WORKSPACE.  0 = arguments rejected. */
+size_t trx_bspline_mi_grids_workspace_bytes(int ndim, int B, int D, int H, int W, int sz, int sy, int sx, int bins, const trx_moving_grid *mg /*[host]*/);
+/* valid [B][*S_t] bytes (1 / 0) of the overlap rule at the composed warp's coordinate: one thread per target voxel forms i with the warp's own statement
+ * (bit-identical to trx_affine_flow_warp's) and applies the rule above with target_mask (nullable, dense [B][*S_t]) and mg->mask (nullable); mg->overlap
+ * itself is not read.  No workspace, the same bits on every call.  Refusals before any HIP call: trx_affine_flow_warp's, valid NULL. */
+int trx_affine_flow_valid(const trx_volumes *vol, const trx_moving_grid *mg /*[host]*/, const float *theta, const float *flow,
+                          const unsigned char *target_mask /*nullable*/, unsigned char *valid /*[B][*S_t]*/, void *stream);
 
 /* ---- Nearest-neighbour and cubic B-spline resampling through the final transform (elastix FinalBSplineInterpolationOrder 3,
  * NiftyReg -inter 3 / -inter 0, ANTs BSpline / NearestNeighbor).  Extension.  Later addition under TRX_VERSION 240: new entry points only.

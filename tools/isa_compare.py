@@ -6,7 +6,9 @@ For every object: the gfx950 code object out of the .hip_fatbin section, its dis
 dropped) and the per-kernel metadata of its notes (register counts, spills, LDS / scratch / kernarg sizes, block size).  Kernels are paired
 BY NAME over all objects of a build, so one that moved to another translation unit is compared like any other; the same name in two
 objects of one build is an error.  Prints kernel counts and code-object sizes per object, the kernels that changed object, those that
-differ and those present in one build only; the exit status is 1 when a kernel present in both differs or one appears only in the new build."""
+differ and those present in one build only; the exit status is 1 when a kernel present in both differs or one appears only in the new build.
+--rename NEW=OLD (any number, after the directories): the substring NEW of a mangled name in the new build is read as OLD before pairing - for a change
+that renames an argument TYPE (the type is part of the symbol) and must leave the code alone."""
 import os, re, subprocess, sys, tempfile
 
 LLVM = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "llvm", "bin")
@@ -80,9 +82,13 @@ def build(build_dir, tmp):
     return found, sizes
 
 
-def main(old_dir, new_dir):
+def main(old_dir, new_dir, renames=()):
     with tempfile.TemporaryDirectory() as tmp:
         (a, sa), (b, sb) = build(old_dir, os.path.join(tmp, "old")), build(new_dir, os.path.join(tmp, "new"))
+    real = {k: k for k in b}                        # paired name -> the symbol as the new build has it (what is printed for a kernel only it has)
+    for new_part, old_part in renames:
+        real = {k.replace(new_part, old_part): v for k, v in real.items()}
+    b = {k: b[v] for k, v in real.items()}
     for f in sorted(set(sa) | set(sb)):
         print(f"{f}: {sum(v[2] == f for v in a.values())} -> {sum(v[2] == f for v in b.values())} kernels; code object {sa.get(f, 0)} -> {sb.get(f, 0)} bytes")
     both = [k for k in a if k in b]
@@ -99,13 +105,19 @@ def main(old_dir, new_dir):
     for k in gone:
         print(f"  removed {k} ({a[k][2]})")
     for k in new:
-        print(f"  NEW {k} ({b[k][2]})")
+        print(f"  NEW {real[k]} ({b[k][2]})")
     print(f"total: {len(both)} kernels compared, {len(both) - len(diff)} identical, {len(diff)} differ, {len(moved)} changed object, {len(gone)} removed, {len(new)} new; "
           f"code objects {sum(sa.values())} -> {sum(sb.values())} bytes")
     return 1 if diff or new else 0
 
 
 if __name__ == "__main__":
-    if len(sys.argv) != 3:
+    args = sys.argv[1:]
+    renames = []
+    while "--rename" in args:
+        i = args.index("--rename")
+        renames.append(tuple(args[i + 1].split("=", 1)))
+        del args[i:i + 2]
+    if len(args) != 2 or any(len(r) != 2 for r in renames):
         sys.exit(__doc__)
-    sys.exit(main(sys.argv[1], sys.argv[2]))
+    sys.exit(main(args[0], args[1], renames))

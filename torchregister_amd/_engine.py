@@ -4,6 +4,7 @@ PyTorch is used for device memory and streams only; all arithmetic of the hot pa
 libtrx.so.  Tensors must be fp32 CUDA(HIP) tensors; anything else raises.
 """
 import ctypes
+import math
 
 import torch
 import torch.nn.functional as F
@@ -651,9 +652,12 @@ class BSplineSolver:
 
     def __init__(self, moving, target, spacing, loss=None, optimizer="sgd", lr=1e-3, init=None, base=None, capacity=1000, stop_crit=None,
                  keep_last=False, betas=(0.9, 0.999), eps=1e-8, bending_weight=0.0, mi=None, squarings=None, mask=None, initial=None,
-                 initial_scale=None):
+                 initial_scale=None, overlap=None, moving_mask=None):
         if initial is not None and (mi is None or squarings is not None):
             raise ValueError("initial (an affine composed into the deformation) runs the mutual-information loop only: give it with `mi` and without `squarings`")
+        self.overlap, moving_mask = overlap_args(overlap, moving_mask, moving)
+        if self.overlap and initial is None:
+            raise ValueError("overlap / moving_mask (the overlap rule) run in the loop composed with an initial affine: give them with `mi` and `initial`")
         if initial is None and initial_scale is not None:
             raise ValueError("initial_scale is the scale of `initial`: give it with `initial`")
         if mask is not None:
@@ -675,8 +679,9 @@ class BSplineSolver:
             raise ValueError("the optimiser path takes single-channel volumes [B,1,...]")
         b, nd, dev = self.batch.B, self.batch.nd, self.batch.device
         self.initial = self.moving_grid = None
+        self.moving_mask = None if moving_mask is None else moving_mask.to(dev)
         if initial is not None:
-            self.initial, self.moving_grid = _initial_theta(initial, b, nd, dev), self.batch.grid()
+            self.initial, self.moving_grid = _initial_theta(initial, b, nd, dev), self.batch.grid(self.overlap, self.moving_mask)
         self.nd = nd
         self.spacing = _spacing3(spacing, nd)[3 - nd:]
         self.sp3 = (ctypes.c_int * 3)(*_spacing3(spacing, nd))
@@ -717,10 +722,11 @@ class BSplineSolver:
                 raise _lib.TrxError(f"trx_bspline_svf_workspace_bytes rejected {b} x {tuple(self.batch.spatial)} with spacing {self.spacing}")
             self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
         elif mi is not None:
-            self.mi, self.mi_range, self.mask = _mi_cfg(mi, self.batch.target, self.batch.moving, mask)
-            self.ws_bytes = self.lib.trx_bspline_mi_workspace_bytes(nd, b, *_dhw(self.batch.spatial), *self.sp3, self.mi.bins)
+            self.mi, self.mi_range, self.mask = _mi_cfg(mi, self.batch.target, self.batch.moving, mask, self.overlap, self.moving_mask)
+            self.ws_bytes = self.lib.trx_bspline_mi_grids_workspace_bytes(nd, b, *_dhw(self.batch.spatial), *self.sp3, self.mi.bins,
+                                                                          None if self.moving_grid is None else ctypes.byref(self.moving_grid))
             if self.ws_bytes == 0:
-                raise _lib.TrxError(f"trx_bspline_mi_workspace_bytes rejected {b} x {tuple(self.batch.spatial)} with spacing {self.spacing}")
+                raise _lib.TrxError(f"trx_bspline_mi_grids_workspace_bytes rejected {b} x {tuple(self.batch.spatial)} with spacing {self.spacing}")
             self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
         else:
             self.workspace, self.ws_bytes = _bspline_workspace(self.lib, nd, b, self.batch.spatial, tuple(self.sp3), dev)
@@ -752,6 +758,18 @@ class BSplineSolver:
             self.flow = svf_exp(self.velocity, self.squarings)
             if self.velocity_last is not None and self.enqueued > 0:
                 self.flow_last = svf_exp(self.velocity_last, self.squarings)
+
+    def valid_fraction(self, flow=None):
+        """[B] fp32: the voxels that enter the criterion at `flow` [B,nd,*target spatial] over the target-mask voxels (or N) - 1 without the
+        overlap rule.  flow None: `.flow`, the expansion of the CURRENT control points - after run() that is the flow of the updated lattice, one
+        step past the last forward whose loss was recorded; pass `.flow_last` for that one (what flow_register returns and reports).  One
+        trx_affine_flow_valid call whose bytes are summed."""
+        B, dev = self.batch.B, self.batch.device
+        total = torch.full((B,), float(math.prod(self.batch.spatial)), device=dev) if self.mask is None else self.mask.reshape(B, -1).sum(1).float()
+        if not self.overlap:
+            return (total > 0).float()
+        valid = affine_flow_valid(self.batch.moving.shape[2:], self.initial, self.flow if flow is None else flow, self.batch.scale, self.mask, self.moving_mask)
+        return valid.reshape(B, -1).sum(1).float() / total.clamp(min=1.0)
 
     def inverse_flow(self):
         """svf_exp(velocity, inverse=True): the inverse of `flow` (diffeomorphic model only)."""
@@ -1414,6 +1432,17 @@ def _mask_u8(mask, like):
     return (mask.detach().reshape(want) != 0).to(device=like.device, dtype=torch.uint8).contiguous()
 
 
+def overlap_args(overlap, moving_mask, moving):
+    """overlap= / moving_mask= of the mutual-information entry points -> (whether the overlap rule is on, the uint8 moving mask [B,1,*moving
+    spatial] or None).  overlap: None (off, unless a moving mask implies it), False or True.  moving_mask goes through _mask_u8 against `moving`
+    and implies the rule; together with an explicit overlap=False it is a ValueError.  Looks at shapes only."""
+    if moving_mask is None:
+        return bool(overlap), None
+    if overlap is not None and not overlap:
+        raise ValueError("moving_mask is part of the overlap rule (a sample outside the mask is dropped like one outside the moving image): it cannot go with overlap=False")
+    return True, _mask_u8(moving_mask, moving)
+
+
 def _mi_cfg_c(bins, alpha, normalized, rng, mask):
     """trx_mi_cfg over the range tensor [B,4] and the uint8 mask (or None) it points to: the caller keeps both alive."""
     cfg = _lib.MICfg()
@@ -1422,21 +1451,22 @@ def _mi_cfg_c(bins, alpha, normalized, rng, mask):
     return cfg
 
 
-def mi_range(target, moving, target_range=None, moving_range=None, mask=None):
+def mi_range(target, moving, target_range=None, moving_range=None, mask=None, overlap=False, moving_mask=None):
     """[B,4] fp32 on the tensors' device: (lo_t, hi_t, lo_w, hi_w) per pair.  None: the target's min / max, the moving (or warped) image's min /
     max widened to contain 0 - the value of a zero-padded warp outside the field of view.  A (lo, hi) pair of numbers serves every pair of the
     batch.  mask (see _mask_u8): the target's min / max are taken over the voxels that count - a pair whose mask is empty falls back to its whole
-    target; the moving side does not change.  No host sync."""
+    target; the moving side does not change.  overlap (the overlap rule, include/trx.h: trx_moving_grid - no padded sample is counted): the moving
+    image's own min / max, NOT widened, taken inside moving_mask (on the moving lattice) when there is one.  No host sync."""
     B = target.shape[0]
     cols = []
     for x, r, widen in ((target, target_range, False), (moving, moving_range, True)):
         if r is None:
             flat = x.detach().float().reshape(B, -1)
             lo, hi = flat.amin(1), flat.amax(1)
-            if widen:
+            if widen and not overlap:
                 lo, hi = lo.clamp(max=0.0), hi.clamp(min=0.0)
-            elif mask is not None:
-                m = _mask_u8(mask, target).reshape(B, -1) != 0
+            elif (moving_mask if widen else mask) is not None:
+                m = (_mask_u8(moving_mask, moving) if widen else _mask_u8(mask, target)).reshape(B, -1) != 0
                 inf = torch.full_like(flat, float("inf"))
                 some = m.any(1)
                 lo, hi = torch.where(some, torch.where(m, flat, inf).amin(1), lo), torch.where(some, torch.where(m, flat, -inf).amax(1), hi)
@@ -1446,13 +1476,14 @@ def mi_range(target, moving, target_range=None, moving_range=None, mask=None):
     return torch.stack(cols, dim=1).contiguous()
 
 
-def _mi_cfg(mi, target, moving, mask=None):
-    """dict -> (trx_mi_cfg, the range tensor it points to, the uint8 mask it points to or None: the caller keeps both alive)."""
+def _mi_cfg(mi, target, moving, mask=None, overlap=False, moving_mask=None):
+    """dict -> (trx_mi_cfg, the range tensor it points to, the uint8 mask it points to or None: the caller keeps both alive).  overlap,
+    moving_mask: how mi_range fits the moving side."""
     unknown = set(mi) - {"bins", "alpha", "normalized", "target_range", "moving_range"}
     if unknown:
         raise ValueError(f"unknown mutual-information settings {sorted(unknown)}")
     m8 = None if mask is None else _mask_u8(mask, target)
-    rng = mi_range(target, moving, mi.get("target_range"), mi.get("moving_range"), m8)
+    rng = mi_range(target, moving, mi.get("target_range"), mi.get("moving_range"), m8, overlap, moving_mask)
     return _mi_cfg_c(mi.get("bins", 32), mi.get("alpha", 1.0), mi.get("normalized", False), rng, m8), rng, m8
 
 
@@ -1557,13 +1588,15 @@ class _GridPair:
     def vol(self):
         return _volumes(self.moving, self.target, self.moving[0].numel(), self.target[0].numel(), self.spatial, tables=self.tables)
 
-    def grid(self):
-        return _moving_grid(self.moving_spatial, self.scale)
+    def grid(self, overlap=False, moving_mask=None):
+        return _moving_grid(self.moving_spatial, self.scale, overlap, moving_mask)
 
 
-def _moving_grid(moving_spatial, scale=None):
-    """trx_moving_grid of a moving lattice (the tensor's spatial shape) and a scale [nd, nd+1] (None: ones)."""
+def _moving_grid(moving_spatial, scale=None, overlap=False, moving_mask=None):
+    """trx_moving_grid of a moving lattice (the tensor's spatial shape) and a scale [nd, nd+1] (None: ones); overlap / moving_mask (uint8 on the
+    device, kept alive by the caller): the overlap rule and its mask on the moving lattice."""
     g = _lib.MovingGrid()
+    g.overlap, g.mask = int(bool(overlap)), None if moving_mask is None else moving_mask.data_ptr()
     g.D, g.H, g.W = _dhw(tuple(moving_spatial))
     nd = len(moving_spatial)
     flat = [1.0] * (nd * (nd + 1)) if scale is None else [float(s) for s in scale.reshape(-1)]
@@ -1670,6 +1703,36 @@ def affine_flow_warp(x, theta, flow, scale=None):
 INTERPOLATIONS = ("nearest", "linear", "cubic")
 
 
+def affine_flow_valid(moving_spatial, theta, flow, scale=None, mask=None, moving_mask=None):
+    """The overlap rule at the composed warp's coordinates (extension, include/trx.h: trx_affine_flow_valid): uint8 [B,1,*target spatial], 1 where
+    target voxel x counts - mask at x (target lattice, or None), the sample coordinate of affine_flow_warp(., theta, flow, scale) inside a moving
+    image of `moving_spatial`, moving_mask (moving lattice, or None) non-zero at the nearest moving voxel.  flow [B,nd,*target spatial] on the GPU."""
+    lib = _lib.load()
+    _require_gpu(flow, "flow")
+    nd, B, dev = flow.dim() - 2, flow.shape[0], flow.device
+    moving_spatial = tuple(int(s) for s in moving_spatial)
+    if nd not in (2, 3) or flow.shape[1] != nd or len(moving_spatial) != nd:
+        raise ValueError(f"expected a flow [B,nd,*target spatial] and a moving shape of nd sizes, got {tuple(flow.shape)} and {moving_spatial}")
+    spatial = tuple(flow.shape[2:])
+    like_t, like_m = torch.empty((B, 1) + spatial, device=dev), torch.empty((B, 1) + moving_spatial, device=dev)      # (shapes and device for _mask_u8)
+    m8 = None if mask is None else _mask_u8(mask, like_t)
+    mm8 = None if moving_mask is None else _mask_u8(moving_mask, like_m)
+    fl = flow.detach().contiguous().float()
+    if isinstance(theta, torch.Tensor) and tuple(theta.shape) == (B, PSTRIDE):      # a solver's padded rows
+        theta = theta[:, : nd * (nd + 1)].reshape(B, nd, nd + 1)
+    th = _initial_theta(theta, B, nd, dev)
+    v = _lib.Volumes()
+    v.moving = v.target = fl.data_ptr()      # (not read: the rule needs coordinates only; the checks want non-null images)
+    v.moving_stride, v.target_stride, v.ndim, v.B = math.prod(moving_spatial), math.prod(spatial), nd, B
+    v.D, v.H, v.W = _dhw(spatial)
+    mg = _moving_grid(moving_spatial, None if scale is None else torch.as_tensor(scale).float(), True, mm8)
+    out = torch.empty((B, 1) + spatial, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.trx_affine_flow_valid(ctypes.byref(v), ctypes.byref(mg), _lib.ptr(th), _lib.ptr(fl), _lib.ptr(m8), _lib.ptr(out), _lib.current_stream(dev))
+    _lib.check(rc, "trx_affine_flow_valid")
+    return out
+
+
 def check_interpolation(value):
     """ValueError unless `value` is one of INTERPOLATIONS; host only."""
     if value not in INTERPOLATIONS:
@@ -1772,18 +1835,23 @@ def resample(x, *, theta=None, flow=None, size=None, scale=None, interpolation="
     return out
 
 
-def affine_mi_loss_grad(moving, target, theta, rng, bins=32, alpha=1.0, normalized=False, need_grad=True, mask=None, scale=None):
+def affine_mi_loss_grad(moving, target, theta, rng, bins=32, alpha=1.0, normalized=False, need_grad=True, mask=None, scale=None, overlap=None,
+                        moving_mask=None, return_counts=False):
     """Mutual information of (target, affine warp of moving by theta) and its gradient with respect to theta without a warped volume (extension,
     include/trx.h: trx_affine_mi_loss_grad): moving / target [B,1,*spatial] fp32 on the GPU, theta [B,nd,nd+1], rng [B,4] (mi_range), mask (see
     _mask_u8) or None = every voxel.  Returns (loss [B], dtheta [B,nd,nd+1] or None) - what affine_warp -> mi_loss_grad -> affine_warp_backward
     give, in two passes over the pair.
     moving may live on a lattice of its own (another spatial shape), and scale [nd, nd+1] (grid_scale; None = ones) multiplies theta entry by
     entry in front of the sampler (trx_affine_mi_loss_grad_grids): theta and dtheta are the unscaled ones, the mask and the loop's voxels are
-    the target's.  With moving's shape equal to target's and scale None this is the one-lattice entry point, the bits of before."""
+    the target's.  With moving's shape equal to target's and scale None this is the one-lattice entry point, the bits of before.
+    overlap / moving_mask (overlap_args): only target voxels whose sample lies inside the moving image - and inside
+    moving_mask [B,1,*moving spatial], looked up at the nearest moving voxel - count; the call then goes through the cross-lattice entry point
+    whatever the shapes.  return_counts: a third result, the pairs' joint tables uint64-as-int64 [B,K,K] (2^31 units per counted voxel)."""
     if mask is not None:
         mask = _mask_u8(mask, target)
+    overlap, moving_mask = overlap_args(overlap, moving_mask, moving)
     lib = _lib.load()
-    two = scale is not None or (isinstance(moving, torch.Tensor) and isinstance(target, torch.Tensor) and moving.shape[2:] != target.shape[2:])
+    two = overlap or scale is not None or (isinstance(moving, torch.Tensor) and isinstance(target, torch.Tensor) and moving.shape[2:] != target.shape[2:])
     pair = _GridPair(moving, target, scale) if two else _mi_pair_batch(moving, target)
     B, nd, dev = pair.B, pair.nd, pair.device
     if tuple(rng.shape) != (B, 4):
@@ -1791,6 +1859,7 @@ def affine_mi_loss_grad(moving, target, theta, rng, bins=32, alpha=1.0, normaliz
     rng = rng.detach().to(device=dev, dtype=torch.float32).contiguous()
     th = pad_theta(theta.detach().to(dev).reshape(B, -1), nd)
     mask = None if mask is None else mask.to(dev)
+    moving_mask = None if moving_mask is None else moving_mask.to(dev)
     cfg = _mi_cfg_c(bins, alpha, normalized, rng, mask)
     vol = pair.vol()
     ws_bytes = lib.trx_affine_mi_workspace_bytes(ctypes.byref(vol), cfg.bins)
@@ -1802,12 +1871,15 @@ def affine_mi_loss_grad(moving, target, theta, rng, bins=32, alpha=1.0, normaliz
     tail = (_lib.ptr(th), _lib.ptr(loss), _lib.ptr(dth), _lib.ptr(ws), ws_bytes, _lib.current_stream(dev))
     with torch.cuda.device(dev):
         if two:
-            mg = pair.grid()
+            mg = pair.grid(overlap, moving_mask)
             rc = lib.trx_affine_mi_loss_grad_grids(ctypes.byref(vol), ctypes.byref(mg), ctypes.byref(cfg), *tail)
         else:
             rc = lib.trx_affine_mi_loss_grad(ctypes.byref(vol), ctypes.byref(cfg), *tail)
     _lib.check(rc, "trx_affine_mi_loss_grad_grids" if two else "trx_affine_mi_loss_grad")
-    return loss, (dth[:, : nd * (nd + 1)].reshape(B, nd, nd + 1) if need_grad else None)
+    dth = dth[:, : nd * (nd + 1)].reshape(B, nd, nd + 1) if need_grad else None
+    if return_counts:
+        return loss, dth, ws[: B * cfg.bins * cfg.bins * 8].view(torch.int64).view(B, cfg.bins, cfg.bins).clone()
+    return loss, dth
 
 
 class AffineMISolver(_AffineParams):
@@ -1824,21 +1896,27 @@ class AffineMISolver(_AffineParams):
     moving may live on a lattice of its own (another spatial shape), and moving_voxel / target_voxel (both or neither; the tensors' axis order,
     mm) make theta act in millimetres: the loop is trx_affine_mi_run_grids, sampling at theta * scale (grid_scale).  The state (theta, param,
     best_theta) stays the UNSCALED theta; .effective(theta) is what F.affine_grid takes, .world_matrix(theta) the map in mm.  With equal shapes
-    and no voxel sizes the solver is the one-lattice one: the same entry point, the same bits."""
+    and no voxel sizes the solver is the one-lattice one: the same entry point, the same bits.
+    overlap / moving_mask (overlap_args): the overlap rule - a target voxel counts only while its sample lies inside the
+    moving image (and inside moving_mask [B,1,*moving spatial], kept alive as `.moving_mask`); validity is re-decided in every pass from the
+    current theta and is constant under the gradient; the moving range is the image's own (inside the mask), not widened to 0.  The loop is then
+    trx_affine_mi_run_grids whatever the shapes.  valid_fraction(theta): the share of counted voxels at a theta."""
 
     def __init__(self, moving, target, mode="affine", mi=None, optimizer="sgd", lr=1e-5, init=None, capacity=1000, betas=(0.9, 0.999), eps=1e-8, mask=None,
-                 moving_voxel=None, target_voxel=None):
+                 moving_voxel=None, target_voxel=None, overlap=None, moving_mask=None):
         if mask is not None:
             mask = _mask_u8(mask, target)
+        self.overlap, moving_mask = overlap_args(overlap, moving_mask, moving)
         self.lib = _lib.load()
-        two = moving_voxel is not None or target_voxel is not None or (
+        two = self.overlap or moving_voxel is not None or target_voxel is not None or (
             isinstance(moving, torch.Tensor) and isinstance(target, torch.Tensor) and moving.shape[2:] != target.shape[2:])
         self.batch = _GridPair(moving, target, None, moving_voxel, target_voxel) if two else _mi_pair_batch(moving, target)
-        self.grid = self.batch.grid() if two else None      # trx_moving_grid, or None: one lattice
+        self.moving_mask = None if moving_mask is None else moving_mask.to(self.batch.device)
+        self.grid = self.batch.grid(self.overlap, self.moving_mask) if two else None      # trx_moving_grid, or None: one lattice
         b, nd, dev = self.batch.B, self.batch.nd, self.batch.device
         self.opt = opt_cfg(optimizer, lr, betas, eps)
         self._init_params(b, nd, dev, mode, init, capacity)
-        self.mi, self.mi_range, self.mask = _mi_cfg({} if mi is None else mi, self.batch.target, self.batch.moving, mask)
+        self.mi, self.mi_range, self.mask = _mi_cfg({} if mi is None else mi, self.batch.target, self.batch.moving, mask, self.overlap, self.moving_mask)
         self.vol = self.batch.vol()
         self.ws_bytes = self.lib.trx_affine_mi_workspace_bytes(ctypes.byref(self.vol), self.mi.bins)
         if self.ws_bytes == 0:
@@ -1857,6 +1935,25 @@ class AffineMISolver(_AffineParams):
                                                       ctypes.byref(self.state), iters, _lib.ptr(self.workspace), self.ws_bytes,
                                                       _lib.current_stream(self.batch.device))
         _lib.check(rc, "trx_affine_mi_run" if self.grid is None else "trx_affine_mi_run_grids")
+
+    def valid_fraction(self, theta):
+        """[B] fp32: the voxels that enter the criterion at `theta` [B,nd,nd+1] (the UNSCALED theta, like the state) over the target-mask voxels
+        (or N) - 1 without the overlap rule.  One extra evaluation of pass 1 whose counts are read back (each counted voxel adds exactly 2^31);
+        a pair with an empty target mask has 0."""
+        B, nd, dev = self.batch.B, self.nd, self.batch.device
+        total = torch.full((B,), float(math.prod(self.batch.spatial)), dtype=torch.float64, device=dev) if self.mask is None else \
+            self.mask.reshape(B, -1).sum(1).double()
+        if self.grid is None:
+            return (total > 0).float()
+        th = pad_theta(theta.detach().to(dev).reshape(B, -1), nd)
+        loss = torch.empty(B, device=dev)
+        with torch.cuda.device(dev):
+            rc = self.lib.trx_affine_mi_loss_grad_grids(ctypes.byref(self.vol), ctypes.byref(self.grid), ctypes.byref(self.mi), _lib.ptr(th), _lib.ptr(loss),
+                                                        None, _lib.ptr(self.workspace), self.ws_bytes, _lib.current_stream(dev))
+        _lib.check(rc, "trx_affine_mi_loss_grad_grids")
+        K = self.mi.bins
+        units = self.workspace[: B * K * K * 8].view(torch.int64).view(B, -1).sum(1).double()      # (the next run() zeroes the counts itself)
+        return (units / 2.0 ** 31 / total.clamp(min=1.0)).float()
 
     @property
     def scale(self):

@@ -77,7 +77,8 @@ class MICfg(ctypes.Structure):
 
 
 class MovingGrid(ctypes.Structure):
-    _fields_ = [("D", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("scale", ctypes.c_float * PSTRIDE)]
+    _fields_ = [("D", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("scale", ctypes.c_float * PSTRIDE),
+                ("overlap", ctypes.c_int), ("mask", ctypes.c_void_p)]      # zero / None: every target voxel counts (zero padding)
 
 
 # name -> (restype, argtypes); must list every symbol include/trx.h declares (tests check this)
@@ -174,6 +175,8 @@ SIGNATURES = {
     "trx_affine_flow_warp_backward": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), _P, _P, ctypes.c_int, _P, _P, _P]),
     "trx_bspline_mi_run_grids": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), _P, ctypes.POINTER(MICfg), ctypes.POINTER(OptCfg),
                                                 ctypes.POINTER(BSplineState), c_int_p, ctypes.c_int, _P, ctypes.c_size_t, _P]),
+    "trx_bspline_mi_grids_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 9 + [ctypes.POINTER(MovingGrid)]),
+    "trx_affine_flow_valid": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), _P, _P, _P, _P, _P]),
     "trx_spline_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "trx_spline_coefficients": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 5 + [_P, ctypes.c_size_t, _P]),
     "trx_transform_resample": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), _P, _P, ctypes.c_int, ctypes.c_int, _P, _P]),

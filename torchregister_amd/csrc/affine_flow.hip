@@ -28,7 +28,7 @@ struct AfRatios {
 // BWD false: io = out [B][channels][target lattice].  BWD true: io = dflow [B][ND][target lattice], grad_out [B][channels][target lattice].
 // chan_stride: moving voxels between channels.
 template <int ND, bool BWD>
-__global__ __launch_bounds__(TRX_BLOCK) void affine_flow_kernel(trx_volumes vol, trx_moving_grid mg, const float *__restrict__ theta, const float *__restrict__ flow,
+__global__ __launch_bounds__(TRX_BLOCK) void affine_flow_kernel(trx_volumes vol, MovingLattice mg, const float *__restrict__ theta, const float *__restrict__ flow,
                                                                 int channels, size_t chan_stride, AfRatios ratio, const float *__restrict__ grad_out,
                                                                 float *__restrict__ io)
 {
@@ -93,6 +93,36 @@ __global__ __launch_bounds__(TRX_BLOCK) void affine_flow_kernel(trx_volumes vol,
     }
 }
 
+// The overlap rule at the warp's coordinate (trx_affine_flow_valid; include/trx.h: trx_moving_grid): the prologue of the kernel above
+// to af_coord - the same statements on the same values, so the same coordinate bit for bit -, then valid = target mask byte (if any) and overlap_valid
+// (bounds, then the moving-mask byte at rint).  One thread per target voxel, one byte written per voxel; a voxel outside the target mask forms no coordinate.
+template <int ND>
+__global__ __launch_bounds__(TRX_BLOCK) void affine_flow_valid_kernel(trx_volumes vol, MovingLattice mg, const float *__restrict__ theta, const float *__restrict__ flow,
+                                                                      const unsigned char *__restrict__ tmask, const unsigned char *__restrict__ mmask,
+                                                                      unsigned char *__restrict__ valid)
+{
+    constexpr int NT = ND * (ND + 1);
+    const int b = blockIdx.y;
+    const int D = vol.D, H = vol.H, W = vol.W, Dm = mg.D, Hm = mg.H, Wm = mg.W;
+    const size_t nvox = (size_t)D * H * W;
+    const float *__restrict__ fl = flow + (size_t)b * ND * nvox;
+    float te[NT];
+    ami_theta_eff<ND>(theta + (size_t)b * TRX_PSTRIDE, mg, te);
+    const size_t i = (size_t)blockIdx.x * TRX_BLOCK + threadIdx.x;
+    if (i >= nvox) return;
+    bool ok = !tmask || tmask[(size_t)b * nvox + i] != 0;
+    if (ok) {
+        const unsigned row = (unsigned)i / (unsigned)W, zz = row / (unsigned)H;
+        const int x = (int)((unsigned)i - row * (unsigned)W), y = (int)(row - zz * (unsigned)H), z = (int)zz;
+        float f[ND], ic[ND];
+#pragma unroll
+        for (int c = 0; c < ND; c++) f[c] = __builtin_nontemporal_load(fl + c * nvox + i);
+        af_coord<ND>(te, f, x, y, z, D, H, W, Dm, Hm, Wm, ic);
+        ok = overlap_valid<ND>(ic, Dm, Hm, Wm, mmask ? mmask + (size_t)b * Dm * Hm * Wm : nullptr);
+    }
+    valid[(size_t)b * nvox + i] = ok ? 1 : 0;
+}
+
 // what both entry points refuse, before any HIP call
 static int af_check(const trx_volumes *vol, const trx_moving_grid *mg, const float *theta, const float *flow, int channels)
 {
@@ -141,4 +171,19 @@ extern "C" int trx_affine_flow_warp_backward(const trx_volumes *vol, const trx_m
     if (rc != TRX_OK) return rc;
     if (!grad_out || !dflow) return TRX_ERR_ARG;
     return af_launch<true>(vol, mg, theta, flow, channels, grad_out, dflow, (hipStream_t)stream);
+}
+
+extern "C" int trx_affine_flow_valid(const trx_volumes *vol, const trx_moving_grid *mg, const float *theta, const float *flow, const unsigned char *target_mask,
+                                     unsigned char *valid, void *stream)
+{
+    const int rc = af_check(vol, mg, theta, flow, 1);
+    if (rc != TRX_OK) return rc;
+    if (!valid) return TRX_ERR_ARG;
+    const size_t nvox = (size_t)vol->D * vol->H * vol->W;
+    const dim3 grid((unsigned)((nvox + TRX_BLOCK - 1) / TRX_BLOCK), (unsigned)vol->B), block(TRX_BLOCK);
+    with_ndim(vol->ndim, [&](auto nd) {
+        hipLaunchKernelGGL((affine_flow_valid_kernel<decltype(nd)::value>), grid, block, 0, (hipStream_t)stream, *vol, *mg, theta, flow, target_mask, mg->mask, valid);
+    });
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
 }

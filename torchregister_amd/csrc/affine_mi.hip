@@ -25,6 +25,10 @@
 // theta_eff and the moving sizes (ami_pose) where the one-lattice instance reads theta in place and vol's sizes.  The __global__ kernels (*_kernel one lattice,
 // *_grids_kernel two: their names and arguments are the launch interface) only forward to the body.  The sampling coordinate is affine_coord (trx_common.h),
 // shared with the cross-lattice warp here, the composed warp (affine_flow.hip) and the lattice warp (affine_lattice.hip).
+// Overlap only (trx_moving_grid.overlap / .mask; two lattices): a third instance of each pass (OV, *_overlap_kernel) forms the
+// coordinate, tests it against [0, S - 1] on every axis and then against the moving-mask byte at rint(i), and skips the voxel in front of the sampler and of
+// the target load - the masked instances' `continue`, one step later.  N_valid comes from the counts as N_m does (launch_mi_table's from_counts); the
+// other instances, and the kernels that take the moving lattice without the rule (MovingLattice: the struct's first 60 bytes), keep their code.
 #include "affine_finalize.h"   // reduce_partials, fin_load / fin_update (the epilogue of the affine step), launch_bwd_finalize (affine_host.h)
 #include "mi_dev.h"
 
@@ -65,10 +69,8 @@ struct AmiSample {
     float v, d[ND];
 };
 template <int ND>
-__device__ __forceinline__ AmiSample<ND> ami_sample(const float *__restrict__ th, const float *__restrict__ mov, int D, int H, int W, float xn, float yn, float zn)
+__device__ __forceinline__ AmiSample<ND> ami_sample_at(const float *__restrict__ mov, int D, int H, int W, const float (&ic)[ND])
 {
-    float ic[ND];
-    affine_coord<ND>(th, xn, yn, zn, D, H, W, ic);
     AmiSample<ND> r;
     if constexpr (ND == 3) {
         const Samp3 s = sample3(mov, D, H, W, ic[0], ic[1], ic[2]);
@@ -79,11 +81,34 @@ __device__ __forceinline__ AmiSample<ND> ami_sample(const float *__restrict__ th
     }
     return r;
 }
+template <int ND>
+__device__ __forceinline__ AmiSample<ND> ami_sample(const float *__restrict__ th, const float *__restrict__ mov, int D, int H, int W, float xn, float yn, float zn)
+{
+    float ic[ND];
+    affine_coord<ND>(th, xn, yn, zn, D, H, W, ic);
+    return ami_sample_at<ND>(mov, D, H, W, ic);
+}
+// The same under the overlap rule (OV; trx_moving_grid.overlap): the coordinate is formed by the same statement, tested
+// (overlap_valid: the bounds, then the moving-mask byte), and only a valid one is sampled.  Returns false for a voxel that does not count.
+template <int ND, bool OV>
+__device__ __forceinline__ bool ami_sample_valid(const float *__restrict__ th, const float *__restrict__ mov, int D, int H, int W, float xn, float yn, float zn,
+                                                 const unsigned char *__restrict__ mmask, AmiSample<ND> &s)
+{
+    if constexpr (OV) {
+        float ic[ND];
+        affine_coord<ND>(th, xn, yn, zn, D, H, W, ic);
+        if (!overlap_valid<ND>(ic, D, H, W, mmask)) return false;
+        s = ami_sample_at<ND>(mov, D, H, W, ic);
+    } else {
+        s = ami_sample<ND>(th, mov, D, H, W, xn, yn, zn);
+    }
+    return true;
+}
 
 // What a block samples pair b with: theta's row in place and vol's sizes, or (XL, two lattices: trx_moving_grid) theta_eff = theta (.) scale,
 // formed once per block into `te` (ami_theta_eff, trx_common.h), and the moving lattice's sizes.  Returns the row the voxel loop reads.
 template <int ND, bool XL>
-__device__ __forceinline__ const float *ami_pose(const trx_volumes &vol, const trx_moving_grid *mg, const float *__restrict__ th, float (&te)[ND * (ND + 1)], int &D, int &H,
+__device__ __forceinline__ const float *ami_pose(const trx_volumes &vol, const MovingLattice *mg, const float *__restrict__ th, float (&te)[ND * (ND + 1)], int &D, int &H,
                                                  int &W)
 {
     if constexpr (XL) {
@@ -97,9 +122,11 @@ __device__ __forceinline__ const float *ami_pose(const trx_volumes &vol, const t
 }
 
 // pass 1: warp and histogram.  mg: the moving lattice (XL) or unused
-template <int ND, bool MASKED, bool XL>
-__device__ __forceinline__ void ami_hist_body(const trx_volumes &vol, const trx_moving_grid *mg, const float *__restrict__ theta, unsigned N, int K, int T,
-                                              const float *__restrict__ range, unsigned long long *__restrict__ counts, const unsigned char *__restrict__ mask)
+// OV (two lattices only): the overlap rule - mmask: the moving masks [B][moving lattice] or nullptr
+template <int ND, bool MASKED, bool XL, bool OV = false>
+__device__ __forceinline__ void ami_hist_body(const trx_volumes &vol, const MovingLattice *mg, const float *__restrict__ theta, unsigned N, int K, int T,
+                                              const float *__restrict__ range, unsigned long long *__restrict__ counts, const unsigned char *__restrict__ mask,
+                                              const unsigned char *__restrict__ mmask = nullptr)
 {
     extern __shared__ unsigned long long ami_lds[];           // [T][K][K]
     const int b = blockIdx.y, tid = threadIdx.x, KK = K * K;
@@ -111,12 +138,14 @@ __device__ __forceinline__ void ami_hist_body(const trx_volumes &vol, const trx_
     const float *__restrict__ mov = vol.moving + (size_t)b * vol.moving_stride;
     const float *__restrict__ tgt = vol.target + (size_t)b * vol.target_stride;
     const unsigned char *mk = MASKED ? mask + (size_t)b * N : nullptr;      // dense, whatever target_stride says
+    const unsigned char *mm = (OV && mmask) ? mmask + (size_t)b * Dm * Hm * Wm : nullptr;
     unsigned long long *mine = ami_lds + ((tid >> 6) % T) * KK;
     const unsigned first = blockIdx.x * (unsigned)kMiChunk, last = min(N, first + (unsigned)kMiChunk);
     for (VoxelWalk vw(first + tid, TRX_BLOCK, vol.H, vol.W); vw.i < last; vw.next(vol.H, vol.W)) {
         if (!mi_counts<MASKED>(mk, vw.i)) continue;      // before any coordinate: a voxel outside the mask costs its mask byte and nothing else
         const float xn = base_coord(vol.xn, vw.x, vol.W), yn = base_coord(vol.yn, vw.y, vol.H), zn = ND == 3 ? base_coord(vol.zn, vw.z, vol.D) : 0.f;
-        const AmiSample<ND> s = ami_sample<ND>(th, mov, Dm, Hm, Wm, xn, yn, zn);
+        AmiSample<ND> s;
+        if (!ami_sample_valid<ND, OV>(th, mov, Dm, Hm, Wm, xn, yn, zn, mm, s)) continue;      // (OV) rejected behind its coordinate: nothing gathered, the target not read
         mi_accumulate(mine, mi_voxel(__builtin_nontemporal_load(tgt + vw.i), s.v, m, K), K);
     }
     __syncthreads();
@@ -129,11 +158,18 @@ __global__ __launch_bounds__(TRX_BLOCK) void ami_hist_kernel(trx_volumes vol, co
     ami_hist_body<ND, MASKED, false>(vol, nullptr, theta, N, K, T, range, counts, mask);
 }
 template <int ND, bool MASKED>
-__global__ __launch_bounds__(TRX_BLOCK) void ami_hist_grids_kernel(trx_volumes vol, trx_moving_grid mg, const float *__restrict__ theta, unsigned N, int K, int T,
+__global__ __launch_bounds__(TRX_BLOCK) void ami_hist_grids_kernel(trx_volumes vol, MovingLattice mg, const float *__restrict__ theta, unsigned N, int K, int T,
                                                                      const float *__restrict__ range, unsigned long long *__restrict__ counts,
                                                                      const unsigned char *__restrict__ mask)
 {
     ami_hist_body<ND, MASKED, true>(vol, &mg, theta, N, K, T, range, counts, mask);
+}
+template <int ND, bool MASKED>
+__global__ __launch_bounds__(TRX_BLOCK) void ami_hist_overlap_kernel(trx_volumes vol, MovingLattice mg, const float *__restrict__ theta, unsigned N, int K, int T,
+                                                                       const float *__restrict__ range, unsigned long long *__restrict__ counts,
+                                                                       const unsigned char *__restrict__ mask, const unsigned char *__restrict__ mmask)
+{
+    ami_hist_body<ND, MASKED, true, true>(vol, &mg, theta, N, K, T, range, counts, mask, mmask);
 }
 
 // The block's 256 x NV per-thread sums -> out[NV]: fp64 from here on (a voxel's terms cancel to a gradient orders of magnitude below them, and the
@@ -162,10 +198,10 @@ __device__ __forceinline__ void ami_block_sum_store(const float (&vals)[NV], flo
 
 // pass 2: gradient rows.  XL: the rows are sums of gw * (sampler derivative in moving voxels) * (xn, yn, zn, 1) - dL/dtheta_eff up to the S / 2 of the MOVING
 // sizes; the reduction behind the pass applies that and the scales.
-template <int ND, bool MASKED, bool XL>
-__device__ __forceinline__ void ami_grad_body(const trx_volumes &vol, const trx_moving_grid *mg, const float *__restrict__ theta, unsigned N, int K,
+template <int ND, bool MASKED, bool XL, bool OV = false>
+__device__ __forceinline__ void ami_grad_body(const trx_volumes &vol, const MovingLattice *mg, const float *__restrict__ theta, unsigned N, int K,
                                               const float *__restrict__ range, const float *__restrict__ G, float *__restrict__ partials,
-                                              const unsigned char *__restrict__ mask)
+                                              const unsigned char *__restrict__ mask, const unsigned char *__restrict__ mmask = nullptr)
 {
     constexpr int NT = ND * (ND + 1);
     extern __shared__ float ami_g[];                // [K][K]
@@ -182,11 +218,13 @@ __device__ __forceinline__ void ami_grad_body(const trx_volumes &vol, const trx_
 #pragma unroll
     for (int k = 0; k < NT; k++) vals[k] = 0.f;
     const unsigned char *mk = MASKED ? mask + (size_t)b * N : nullptr;
+    const unsigned char *mm = (OV && mmask) ? mmask + (size_t)b * Dm * Hm * Wm : nullptr;
     const unsigned first = blockIdx.x * (unsigned)kMiChunk, last = min(N, first + (unsigned)kMiChunk);
     for (VoxelWalk vw(first + tid, TRX_BLOCK, vol.H, vol.W); vw.i < last; vw.next(vol.H, vol.W)) {
         if (!mi_counts<MASKED>(mk, vw.i)) continue;      // grad_warped is 0 there: nothing is sampled, the row below is still written (zeros if the chunk is empty)
         const float xn = base_coord(vol.xn, vw.x, vol.W), yn = base_coord(vol.yn, vw.y, vol.H), zn = ND == 3 ? base_coord(vol.zn, vw.z, vol.D) : 0.f;
-        const AmiSample<ND> s = ami_sample<ND>(th, mov, Dm, Hm, Wm, xn, yn, zn);
+        AmiSample<ND> s;
+        if (!ami_sample_valid<ND, OV>(th, mov, Dm, Hm, Wm, xn, yn, zn, mm, s)) continue;      // (OV) validity is constant under the gradient: the voxel adds nothing
         const float gw = mi_voxel_grad(ami_g, mi_voxel(__builtin_nontemporal_load(tgt + vw.i), s.v, m, K), K);
 #pragma unroll
         for (int c = 0; c < ND; c++) {      // row c of theta: d coordinate_c / d theta[c][.] = (xn, yn, zn, 1)
@@ -207,11 +245,18 @@ __global__ __launch_bounds__(TRX_BLOCK) void ami_grad_kernel(trx_volumes vol, co
     ami_grad_body<ND, MASKED, false>(vol, nullptr, theta, N, K, range, G, partials, mask);
 }
 template <int ND, bool MASKED>
-__global__ __launch_bounds__(TRX_BLOCK) void ami_grad_grids_kernel(trx_volumes vol, trx_moving_grid mg, const float *__restrict__ theta, unsigned N, int K,
+__global__ __launch_bounds__(TRX_BLOCK) void ami_grad_grids_kernel(trx_volumes vol, MovingLattice mg, const float *__restrict__ theta, unsigned N, int K,
                                                                      const float *__restrict__ range, const float *__restrict__ G, float *__restrict__ partials,
                                                                      const unsigned char *__restrict__ mask)
 {
     ami_grad_body<ND, MASKED, true>(vol, &mg, theta, N, K, range, G, partials, mask);
+}
+template <int ND, bool MASKED>
+__global__ __launch_bounds__(TRX_BLOCK) void ami_grad_overlap_kernel(trx_volumes vol, MovingLattice mg, const float *__restrict__ theta, unsigned N, int K,
+                                                                       const float *__restrict__ range, const float *__restrict__ G, float *__restrict__ partials,
+                                                                       const unsigned char *__restrict__ mask, const unsigned char *__restrict__ mmask)
+{
+    ami_grad_body<ND, MASKED, true, true>(vol, &mg, theta, N, K, range, G, partials, mask, mmask);
 }
 
 // The loop's epilogue, one block per pair: the pair's partial rows -> dL/dtheta, the loss of the table kernel, then the affine step's epilogue
@@ -260,7 +305,7 @@ __global__ __launch_bounds__(TRX_FIN_THREADS) void ami_update_kernel(const float
     ami_update_body<ND, false>(partials, nblk, loss, D, H, W, oc, st, counts, KK, nullptr);
 }
 template <int ND>
-__global__ __launch_bounds__(TRX_FIN_THREADS) void ami_update_grids_kernel(const float *__restrict__ partials, int nblk, const float *__restrict__ loss, trx_moving_grid mg,
+__global__ __launch_bounds__(TRX_FIN_THREADS) void ami_update_grids_kernel(const float *__restrict__ partials, int nblk, const float *__restrict__ loss, MovingLattice mg,
                                                                            trx_opt_cfg oc, trx_affine_state st, unsigned long long *__restrict__ counts, int KK)
 {
     ami_update_body<ND, true>(partials, nblk, loss, mg.D, mg.H, mg.W, oc, st, counts, KK, mg.scale);
@@ -269,7 +314,7 @@ __global__ __launch_bounds__(TRX_FIN_THREADS) void ami_update_grids_kernel(const
 // Behind one cross-lattice evaluation: launch_bwd_finalize's reduction (reduce_partials' fixed order) with the moving sizes in S / 2 and the scales on top,
 // dtheta[k] = (S_row / 2 * scale[k]) * sum - one rounding to fp32, as there.
 template <int ND>
-__global__ __launch_bounds__(TRX_FIN_THREADS) void ami_grids_finalize_kernel(const float *__restrict__ partials, int nblk, trx_moving_grid mg, float *__restrict__ dtheta)
+__global__ __launch_bounds__(TRX_FIN_THREADS) void ami_grids_finalize_kernel(const float *__restrict__ partials, int nblk, MovingLattice mg, float *__restrict__ dtheta)
 {
     constexpr int NT = ND * (ND + 1);
     __shared__ double S[64];
@@ -286,7 +331,7 @@ __global__ __launch_bounds__(TRX_FIN_THREADS) void ami_grids_finalize_kernel(con
 // The cross-lattice forward warp (trx_affine_warp_grids): affine_warp_kernel's walk over the TARGET lattice (vol's sizes and tables), every channel sampled in
 // a moving volume of mg's sizes at theta_eff (formed once per block, as in the two passes).  chan_stride: moving voxels between channels.
 template <int ND>
-__global__ __launch_bounds__(TRX_BLOCK) void affine_warp_grids_kernel(trx_volumes vol, trx_moving_grid mg, const float *__restrict__ theta, int channels,
+__global__ __launch_bounds__(TRX_BLOCK) void affine_warp_grids_kernel(trx_volumes vol, MovingLattice mg, const float *__restrict__ theta, int channels,
                                                                       size_t chan_stride, float *__restrict__ out)
 {
     const int b = blockIdx.y;
@@ -316,22 +361,29 @@ static int ami_evaluate(const trx_volumes *vol, const trx_moving_grid *mg, const
     float *G = (float *)((char *)workspace + g.o_g), *partials = (float *)((char *)workspace + g.o_part);
     const dim3 grid(g.nchunk, (unsigned)vol->B), block(TRX_BLOCK);
     const unsigned char *mask = cfg->mask;               // read here on every evaluation, so on every iteration of the loop
+    const bool ov = mg && mg->overlap;                   // the overlap rule: N_valid comes from the counts, as N_m does under a mask
     const size_t lds = (size_t)T * K * K * sizeof(unsigned long long);
     with_ndim(vol->ndim, [&](auto nd) {
         constexpr int ND = decltype(nd)::value;
-        if (mg) {
+        if (ov) {
+            if (mask) hipLaunchKernelGGL((ami_hist_overlap_kernel<ND, true>), grid, block, lds, s, *vol, *mg, theta, g.N, K, T, cfg->range, counts, mask, mg->mask);
+            else hipLaunchKernelGGL((ami_hist_overlap_kernel<ND, false>), grid, block, lds, s, *vol, *mg, theta, g.N, K, T, cfg->range, counts, mask, mg->mask);
+        } else if (mg) {
             if (mask) hipLaunchKernelGGL((ami_hist_grids_kernel<ND, true>), grid, block, lds, s, *vol, *mg, theta, g.N, K, T, cfg->range, counts, mask);
             else hipLaunchKernelGGL((ami_hist_grids_kernel<ND, false>), grid, block, lds, s, *vol, *mg, theta, g.N, K, T, cfg->range, counts, mask);
         } else if (mask) hipLaunchKernelGGL((ami_hist_kernel<ND, true>), grid, block, lds, s, *vol, theta, g.N, K, T, cfg->range, counts, mask);
         else hipLaunchKernelGGL((ami_hist_kernel<ND, false>), grid, block, lds, s, *vol, theta, g.N, K, T, cfg->range, counts, mask);
     });
     TRX_CHECK_LAUNCH();
-    const int rc = launch_mi_table(counts, g.N, vol->B, cfg, loss, need_grad ? G : (float *)nullptr, s);
+    const int rc = launch_mi_table(counts, g.N, vol->B, cfg, ov, loss, need_grad ? G : (float *)nullptr, s);
     if (rc != TRX_OK || !need_grad) return rc;
     const size_t glds = (size_t)K * K * sizeof(float);
     with_ndim(vol->ndim, [&](auto nd) {
         constexpr int ND = decltype(nd)::value;
-        if (mg) {
+        if (ov) {
+            if (mask) hipLaunchKernelGGL((ami_grad_overlap_kernel<ND, true>), grid, block, glds, s, *vol, *mg, theta, g.N, K, cfg->range, (const float *)G, partials, mask, mg->mask);
+            else hipLaunchKernelGGL((ami_grad_overlap_kernel<ND, false>), grid, block, glds, s, *vol, *mg, theta, g.N, K, cfg->range, (const float *)G, partials, mask, mg->mask);
+        } else if (mg) {
             if (mask) hipLaunchKernelGGL((ami_grad_grids_kernel<ND, true>), grid, block, glds, s, *vol, *mg, theta, g.N, K, cfg->range, (const float *)G, partials, mask);
             else hipLaunchKernelGGL((ami_grad_grids_kernel<ND, false>), grid, block, glds, s, *vol, *mg, theta, g.N, K, cfg->range, (const float *)G, partials, mask);
         } else if (mask) hipLaunchKernelGGL((ami_grad_kernel<ND, true>), grid, block, glds, s, *vol, theta, g.N, K, cfg->range, (const float *)G, partials, mask);
@@ -350,6 +402,7 @@ static int ami_check(const trx_volumes *vol, const trx_moving_grid *mg, bool gri
     if (rc == TRX_OK && grids) rc = ami_grid_check(vol->ndim, mg);
     if (rc != TRX_OK) return rc;
     if (!std::isfinite(cfg->alpha)) return TRX_ERR_ARG;
+    if (grids && mg->mask && !mg->overlap) return TRX_ERR_ARG;      // a moving mask is part of the overlap rule
     if (workspace_bytes < g->ws_bytes) return TRX_ERR_WORKSPACE;
     return TRX_OK;
 }

@@ -818,6 +818,17 @@ extern "C" size_t trx_bspline_mi_workspace_bytes(int ndim, int B, int D, int H, 
     return l.ws_bytes;
 }
 
+// Under the overlap rule (trx_moving_grid.overlap) the B N validity bytes of an iteration lie behind that workspace
+static size_t bspline_mi_valid_bytes(const BsGeom &g) { return (((size_t)g.B * g.S[0] * g.S[1] * g.S[2]) + 255) & ~(size_t)255; }
+
+extern "C" size_t trx_bspline_mi_grids_workspace_bytes(int ndim, int B, int D, int H, int W, int sz, int sy, int sx, int bins, const trx_moving_grid *mg)
+{
+    BsGeom g;
+    BsMiLayout l;
+    if (bspline_geom(ndim, B, D, H, W, sz, sy, sx, &g) != TRX_OK || bspline_mi_layout(g, bins, &l) != TRX_OK) return 0;
+    return l.ws_bytes + ((mg && mg->overlap) ? bspline_mi_valid_bytes(g) : 0);
+}
+
 // Both mutual-information loops.  mg == nullptr: one lattice, the warp is trx_flow_warp.  Otherwise the deformation is composed with the initial affine
 // `theta`, the moving image on a lattice of its own (csrc/affine_flow.hip): the same checks, workspace and launches with the composed
 // warp and its backward where trx_flow_warp / trx_flow_warp_backward stand.  theta is read on the device on every iteration and never written.
@@ -834,10 +845,25 @@ static int bspline_mi_run_impl(const trx_volumes *vol, const trx_moving_grid *mg
     if (!std::isfinite(cfg->alpha)) return TRX_ERR_ARG;
     const size_t nvox = (size_t)vol->D * vol->H * vol->W;
     if (vol->B > 1 && vol->target_stride != nvox) return TRX_ERR_ARG;   // the histogram kernels take a dense [B][D][H][W] target
-    if (workspace_bytes < l.ws_bytes) return TRX_ERR_WORKSPACE;
+    if (mg && mg->mask && !mg->overlap) return TRX_ERR_ARG;      // a moving mask is part of the overlap rule
+    const bool ov = mg && mg->overlap;
+    if (workspace_bytes < l.ws_bytes + (ov ? bspline_mi_valid_bytes(g) : 0)) return TRX_ERR_WORKSPACE;
     if (st->losses && iters > st->losses_capacity) return TRX_ERR_CAPACITY;
     char *ws = (char *)workspace;
     float *mloss = (float *)(ws + g.terms_offset), *warped = (float *)(ws + l.o_warped), *go = (float *)(ws + l.o_go);
+    if (ov) {      // warp -> validity at the warp's coordinates -> the masked criterion on the validity bytes -> warp backward (grad_warped is 0 at an invalid voxel)
+        unsigned char *valid = (unsigned char *)(ws + l.ws_bytes);
+        trx_mi_cfg vcfg = *cfg;
+        vcfg.mask = valid;
+        return bspline_loop(g, vol, opt, st, iters, mloss, 1, workspace, (hipStream_t)stream, [&]() {
+            int r = trx_affine_flow_warp(vol, mg, theta, st->flow, 1, warped, stream);
+            if (r != TRX_OK) return r;
+            if ((r = trx_affine_flow_valid(vol, mg, theta, st->flow, cfg->mask, valid, stream)) != TRX_OK) return r;
+            r = trx_mi_loss_grad(vol->target, warped, vol->ndim, vol->B, vol->D, vol->H, vol->W, &vcfg, mloss, go, ws + l.o_mi, l.mi_bytes, stream);
+            if (r != TRX_OK) return r;
+            return trx_affine_flow_warp_backward(vol, mg, theta, st->flow, 1, go, st->dflow, stream);
+        });
+    }
     return bspline_loop(g, vol, opt, st, iters, mloss, 1, workspace, (hipStream_t)stream, [&]() {
         int r = mg ? trx_affine_flow_warp(vol, mg, theta, st->flow, 1, warped, stream) : trx_flow_warp(vol, st->flow, 1, warped, stream);
         if (r != TRX_OK) return r;

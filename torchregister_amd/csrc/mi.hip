@@ -171,9 +171,9 @@ static int mi_geom(int ndim, int B, int D, int H, int W, int bins, MiGeom *g)
     return TRX_OK;
 }
 
-int launch_mi_table(const unsigned long long *counts, unsigned N, int B, const trx_mi_cfg *cfg, float *loss, float *G, hipStream_t s)
+int launch_mi_table(const unsigned long long *counts, unsigned N, int B, const trx_mi_cfg *cfg, bool from_counts, float *loss, float *G, hipStream_t s)
 {
-    if (cfg->mask)
+    if (cfg->mask || from_counts)
         hipLaunchKernelGGL(mi_table_kernel<true>, dim3((unsigned)B), dim3(TRX_BLOCK), 0, s, counts, N, cfg->bins, cfg->alpha, cfg->normalized ? 1 : 0, cfg->range, loss, G);
     else
         hipLaunchKernelGGL(mi_table_kernel<false>, dim3((unsigned)B), dim3(TRX_BLOCK), 0, s, counts, N, cfg->bins, cfg->alpha, cfg->normalized ? 1 : 0, cfg->range, loss, G);
@@ -224,7 +224,7 @@ extern "C" int trx_mi_loss_grad(const float *target, const float *warped, int nd
     if (rc != TRX_OK) return rc;
     const int K = cfg->bins;
     float *G = (float *)((char *)workspace + g.g_offset);
-    const int rc_table = launch_mi_table((const unsigned long long *)workspace, g.N, B, cfg, loss, grad_warped ? G : (float *)nullptr, s);
+    const int rc_table = launch_mi_table((const unsigned long long *)workspace, g.N, B, cfg, false, loss, grad_warped ? G : (float *)nullptr, s);
     if (rc_table != TRX_OK) return rc_table;
     if (!grad_warped) return TRX_OK;
     const dim3 grid(g.nchunk, (unsigned)B), block(TRX_BLOCK);

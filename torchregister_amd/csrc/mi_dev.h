@@ -116,7 +116,8 @@ __device__ __forceinline__ bool mi_counts(const unsigned char *__restrict__ mask
 }
 
 // mi.hip: mi_table_kernel, one block per pair - counts [B][K][K] -> loss [B] (nullable) and G [B][K][K] = d loss / d P scaled by s_w / N (nullable).
-// With cfg->mask set N is ignored: the kernel takes N_m = (sum of the pair's counts) / TRX_MI_ONE, an exact integer, from the table itself.
-TRX_HIDDEN int launch_mi_table(const unsigned long long *counts, unsigned N, int B, const trx_mi_cfg *cfg, float *loss, float *G, hipStream_t s);
+// With cfg->mask set, or from_counts (the overlap rule of the fused affine passes selects voxels without a target mask), N is ignored: the kernel takes
+// N_m = (sum of the pair's counts) / TRX_MI_ONE, an exact integer, from the table itself.
+TRX_HIDDEN int launch_mi_table(const unsigned long long *counts, unsigned N, int B, const trx_mi_cfg *cfg, bool from_counts, float *loss, float *G, hipStream_t s);
 
 }  // namespace trx

@@ -144,7 +144,7 @@ __device__ __forceinline__ float spl_taps(const float *__restrict__ m, const int
 // mg: the SAMPLED lattice and the scales (the host fills in the target's own and ones where the caller gave none).  chan_stride: sampled voxels
 // between channels.  theta NULL: the flow-only chain; flow NULL: zero flow.
 template <int ND, int ORDER>
-__global__ __launch_bounds__(TRX_BLOCK) void transform_resample_kernel(trx_volumes vol, trx_moving_grid mg, const float *__restrict__ theta,
+__global__ __launch_bounds__(TRX_BLOCK) void transform_resample_kernel(trx_volumes vol, MovingLattice mg, const float *__restrict__ theta,
                                                                        const float *__restrict__ flow, int channels, size_t chan_stride, float *__restrict__ out)
 {
     constexpr int NT = ND * (ND + 1);
@@ -285,7 +285,7 @@ extern "C" int trx_transform_resample(const trx_volumes *vol, const trx_moving_g
     if (rc == TRX_OK && mg) rc = ami_grid_check(vol->ndim, mg);
     if (rc != TRX_OK) return rc;
     if (!out || (!theta && !flow) || (mg && !theta) || channels < 1 || (order != 0 && order != 3)) return TRX_ERR_ARG;
-    trx_moving_grid g;
+    MovingLattice g;      // (mg->overlap / mask are not read: a resampler pads)
     if (mg) {
         g = *mg;
     } else {

@@ -229,8 +229,33 @@ __device__ __forceinline__ float base_coord(const float *__restrict__ tab, int i
 // Two lattices (trx_moving_grid): the loop's voxels, the mask and the base coordinates stay on vol's (target) lattice, the sample is
 // taken in a moving volume of its own size at theta_eff = theta (.) scale.  theta_eff is formed here, once per block, from uniform values (theta's row
 // through scalar loads, the scales from the kernel arguments): the voxel loop sees ND (ND + 1) registers, as it does with one lattice.
+// What a kernel takes of a trx_moving_grid: the sizes and the scales, 60 bytes.  The ABI struct has grown behind them (overlap, mask: DESIGN.md section
+// 4.16); kernels that read neither keep their argument layout, and with it their code, by taking this.  A launch converts implicitly.
+struct MovingLattice {
+    int D, H, W;
+    float scale[TRX_PSTRIDE];
+    MovingLattice() = default;
+    MovingLattice(const trx_moving_grid &g) : D(g.D), H(g.H), W(g.W)
+    {
+        for (int k = 0; k < TRX_PSTRIDE; k++) scale[k] = g.scale[k];
+    }
+};
+
+// The overlap rule's test of an un-normalised moving coordinate (include/trx.h, trx_moving_grid): every axis inside [0, S - 1] (false for a NaN), then - only
+// then, so the index is in range - the moving-mask byte at rint(ic), half to even, if there is a mask.  mmask: the pair's [D][H][W] bytes or nullptr.
 template <int ND>
-__device__ __forceinline__ void ami_theta_eff(const float *__restrict__ th, const trx_moving_grid &mg, float (&te)[ND * (ND + 1)])
+__device__ __forceinline__ bool overlap_valid(const float (&ic)[ND], int D, int H, int W, const unsigned char *__restrict__ mmask)
+{
+    bool in = ic[0] >= 0.f && ic[0] <= (float)(W - 1) && ic[1] >= 0.f && ic[1] <= (float)(H - 1);
+    if constexpr (ND == 3) in = in && ic[2] >= 0.f && ic[2] <= (float)(D - 1);
+    if (!in || !mmask) return in;
+    size_t idx = (size_t)__float2int_rn(ic[1]) * W + __float2int_rn(ic[0]);
+    if constexpr (ND == 3) idx += (size_t)__float2int_rn(ic[2]) * H * W;
+    return mmask[idx] != 0;
+}
+
+template <int ND>
+__device__ __forceinline__ void ami_theta_eff(const float *__restrict__ th, const MovingLattice &mg, float (&te)[ND * (ND + 1)])
 {
 #pragma unroll
     for (int k = 0; k < ND * (ND + 1); k++)      // one fp32 rounding: (theta, scale) samples exactly where (fl(theta scale), 1) does; pinned to an SGPR like theta's own row

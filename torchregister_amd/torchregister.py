@@ -9,9 +9,9 @@ U-Net-generated flow, 'direct' = the flow field itself is the parameter), levels
 import torch
 from torch import cat
 
-from ._engine import _bending_weight, _mask_u8, _squarings, affine_warp, check_interpolation, grid_scale, resample
+from ._engine import _bending_weight, _mask_u8, _squarings, affine_warp, check_interpolation, grid_scale, overlap_args, resample
 from .pyramid import level_theta, pyramid, pyramid_masks, pyramid_shapes, upsample_flow
-from .warpings import (GRIDS_SUPPORT, INITIAL_SUPPORT, MASK_SUPPORT, affine_register, device_loop_settings, flow_register, get_affine_warp, resolve_initial, rigid_register,
+from .warpings import (GRIDS_SUPPORT, INITIAL_SUPPORT, MASK_SUPPORT, OVERLAP_SUPPORT, affine_register, device_loop_settings, flow_register, get_affine_warp, resolve_initial, rigid_register,
                        two_lattices)
 
 
@@ -123,6 +123,7 @@ class Register():
         self.world_matrix = None    # device_loop with voxel sizes: [B,nd+1,nd+1], the best theta as moving_mm = M target_mm (rows / columns x, y(, z))
         self.target_shape = None    # the spatial shape of the lattice optim registered onto: what reg(x) returns
         self.initial = None         # optim(initial=...): the effective theta [B,nd,nd+1] the deformation is composed with
+        self.valid_fraction = None  # optim(overlap=True / moving_mask=...): [B], N_valid / (target-mask voxels or N) at the returned transform
 
     def _flow_kw(self, n, lr, max_epochs):
         kw = dict(mode='bilinear', n=n, lr=lr, max_epochs=max_epochs, optimizer=self.optimizer, smooth_weight=self.smooth_weight,
@@ -166,6 +167,21 @@ class Register():
             raise ValueError(INITIAL_SUPPORT)
         return resolve_initial(initial, moving, target)
 
+    def _check_overlap(self, overlap, moving_mask, moving, initial):
+        '''overlap=... / moving_mask=... of optim: ValueError unless the loop is the fused rigid / affine mutual-information loop (device_loop=True) or
+        the B-spline mutual-information loop composed with initial=, before any device work.  Returns (on, the uint8 moving mask or None).'''
+        if not overlap and moving_mask is None:
+            return False, None
+        if self.mode == 'flow':
+            from .utils import MILoss
+            alone = self.criterion is not None and self.weight is not None and len(self.criterion) == 1 and isinstance(self.criterion[0], MILoss)
+            ok = alone and self.flow_model == 'bspline' and not self.diffeomorphic and initial is not None
+        else:
+            ok = self.device_loop
+        if not ok:
+            raise ValueError(OVERLAP_SUPPORT)
+        return overlap_args(overlap, moving_mask, moving)
+
     def _set_grids(self, grids, target, info):
         '''After a rigid / affine optim: the warp behind __call__ (two lattices: onto the target lattice, forward only) and the new attributes.'''
         self.target_shape = tuple(target.shape[2:])
@@ -173,7 +189,8 @@ class Register():
         size = self.target_shape
         self.warp = (lambda theta, x: affine_warp(theta, x, size=size)) if grids else get_affine_warp
 
-    def optim(self, moving, target, lr=1E-5, max_epochs=1000, n=32, per=0.1, *, mask=None, moving_voxel=None, target_voxel=None, initial=None):
+    def optim(self, moving, target, lr=1E-5, max_epochs=1000, n=32, per=0.1, *, mask=None, moving_voxel=None, target_voxel=None, initial=None,
+              overlap=None, moving_mask=None):
         '''
         Optimisation loop: moving, target [1,1,x,y(,z)] float32 GPU tensors (a leading batch > 1 of
         independent pairs is an extension).  Sets self.theta (best theta [B,nd,nd+1], or the flow
@@ -203,7 +220,20 @@ class Register():
             reg(x) warps any [B,c,*moving spatial] onto the target lattice by one composed interpolation, .initial holds the theta used.  With
             levels > 1 moving and target get their own pyramids (align_corners=True, as flow mode does) and a level runs with
             pyramid.level_theta of the theta; .level_shapes are the target's.
+        overlap, moving_mask : (keyword-only extension) overlap=True: the mutual information is taken over the overlap only - a target voxel counts
+            while its sample lies inside the moving image (all corners of the interpolation in the volume), so the zero padding outside the moving
+            field of view never forms an intensity class of its own (elastix / ITK / NiftyReg behaviour; partial overlap is the normal case for
+            volumes on their own grids).  moving_mask: a mask on the MOVING lattice, [B,1,*moving spatial] or [B,*moving spatial], non-zero = the
+            moving voxel counts, looked up at the sample's nearest voxel; it implies overlap (with an explicit overlap=False: ValueError).  The
+            moving range is then the image's own min / max (inside the mask), not widened to 0; validity is re-decided in every iteration and is
+            constant under the gradient.  Supported by mode 'rigid' / 'affine' with device_loop=True (one or two lattices, with or without voxel
+            sizes) and by mode 'flow' with flow_model='bspline', MILoss alone and initial=; ValueError anywhere else, before any device work.
+            Afterwards .valid_fraction [B] is N_valid / (target-mask voxels or N) at the returned transform (one extra evaluation; nothing is read
+            back inside the loop) - there is no minimum-overlap guard: a pair that lost all overlap has loss 0, check the fraction.  With levels > 1
+            the moving mask goes through pyramid_masks over the moving pyramid and every level fits its own ranges.
         '''
+        self.valid_fraction = None
+        overlap, moving_mask = self._check_overlap(overlap, moving_mask, moving, initial)
         if initial is not None:
             initial, grids = self._check_initial(initial, moving, target, moving_voxel, target_voxel), False
         else:
@@ -212,10 +242,12 @@ class Register():
         if mask is not None:
             mask = self._check_mask(mask, target)
         if self.levels > 1:
-            return self._optim_levels(moving, target, lr, max_epochs, n, per, mask, moving_voxel, target_voxel, initial)
+            return self._optim_levels(moving, target, lr, max_epochs, n, per, mask, moving_voxel, target_voxel, initial, overlap, moving_mask)
+        okw = dict(overlap=True, moving_mask=moving_mask) if overlap else {}
         if self.mode == 'flow':
             flowreg = flow_register(target.shape[2:], **self._flow_kw(n, lr, max_epochs)).to(moving.device)
-            flowreg.optimize(moving, target, self.device, self.debug, mask=mask, initial=initial)
+            flowreg.optimize(moving, target, self.device, self.debug, mask=mask, initial=initial, **okw)
+            self.valid_fraction = flowreg.valid_fraction
             if initial is not None:
                 self.target_shape = tuple(target.shape[2:])
             self.theta = flowreg.flow
@@ -238,7 +270,8 @@ class Register():
             kw.update(mask=mask)
         if grids:
             kw.update(moving_voxel=moving_voxel, target_voxel=target_voxel)
-        _, theta = fn(moving, target, **kw)
+        _, theta = fn(moving, target, **kw, **okw)
+        self.valid_fraction = info.get('valid_fraction')
         self.theta = theta[-1]                                                # best theta (Q8)
         self.final_theta = theta[0]
         self.losses = info.get('losses')
@@ -246,7 +279,8 @@ class Register():
         self.final_pose = info.get('final_pose')
         self._set_grids(grids, target, info)
 
-    def _optim_levels(self, moving, target, lr, max_epochs, n, per, mask=None, moving_voxel=None, target_voxel=None, initial=None):
+    def _optim_levels(self, moving, target, lr, max_epochs, n, per, mask=None, moving_voxel=None, target_voxel=None, initial=None, overlap=False,
+                      moving_mask=None):
         '''Coarse-to-fine: the single-level machinery (flow_register / _affine_family) on each level of pyramid(moving) and
         pyramid(target), coarsest first; each level starts from the previous level's FINAL parameters (rigid: the pose, drawn by
         torch.rand for the coarsest level as a single-level run draws it; affine: theta; flow: upsample_flow of the flow).  Optimiser
@@ -264,6 +298,8 @@ class Register():
         flow = self.mode == 'flow'
         movs, tgts = pyramid(moving, L, align_corners=flow), pyramid(target, L, align_corners=flow)
         masks = [None] * L if mask is None else pyramid_masks(mask, L, align_corners=flow)      # raises for a pair whose mask empties at some level
+        mmasks = [None] * L if moving_mask is None else pyramid_masks(moving_mask.to(moving.device), L, align_corners=flow)      # over the MOVING pyramid's shapes
+        okw = (lambda k: dict(overlap=True, moving_mask=mmasks[k])) if overlap else (lambda k: {})      # the flag goes to every level
         init = None if flow else self.init
         mshapes = None if initial is None else pyramid_shapes(moving.shape[2:], L)
         self.level_losses, self.level_shapes = [], shapes
@@ -276,7 +312,8 @@ class Register():
                 else:
                     reg.init_flow = up
                 lvl_initial = None if initial is None else level_theta(initial, target.shape[2:], shapes[k], moving.shape[2:], mshapes[k])
-                reg.optimize(movs[k], tgts[k], self.device, False, mask=masks[k], initial=lvl_initial)
+                reg.optimize(movs[k], tgts[k], self.device, False, mask=masks[k], initial=lvl_initial, **okw(k))
+                self.valid_fraction = reg.valid_fraction
                 if initial is not None:
                     self.target_shape = tuple(shapes[k])
                 init = reg.final_velocity if self.diffeomorphic else reg.final_flow      # diffeomorphic: the levels add up as velocities
@@ -299,7 +336,8 @@ class Register():
                     # align_corners=False keeps an image's field of view: a level's voxel is the full one times (full size / level size), per axis
                     lvl = lambda voxel, full, x: None if voxel is None else tuple(v * s / sl for v, s, sl in zip(voxel, full.shape[2:], x.shape[2:]))  # noqa: E731
                     kw.update(moving_voxel=lvl(moving_voxel, moving, movs[k]), target_voxel=lvl(target_voxel, target, tgts[k]))
-                _, theta = fn(movs[k], tgts[k], **kw)
+                _, theta = fn(movs[k], tgts[k], **kw, **okw(k))
+                self.valid_fraction = info.get('valid_fraction')
                 # (a level whose two shapes happen to coincide, without voxel sizes, is a one-lattice run: its theta is unscaled as it is)
                 init = info['final_pose'] if self.mode == 'rigid' else info.get('final_unscaled_theta', theta[0])
                 self.theta, self.final_theta = theta[-1], theta[0]

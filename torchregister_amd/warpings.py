@@ -295,6 +295,12 @@ INITIAL_SUPPORT = ("initial= (the rigid / affine result of the stage before, com
                    "[B,nd,nd+1] or a Register of mode 'rigid' / 'affine' that has run onto the same target lattice")
 
 
+OVERLAP_SUPPORT = ("overlap=True / moving_mask= (mutual information over the overlap only: a target voxel counts while its sample lies inside the moving "
+                   "image and inside the moving mask) are honoured by the fused rigid / affine loop - mode='rigid' / 'affine' with device_loop=True and "
+                   "criterion=[MILoss()] - and by the B-spline mutual-information loop composed with an initial affine - mode='flow' with "
+                   "flow_model='bspline', criterion=[MILoss()] alone and initial=; the other criteria and loops pad with zeros")
+
+
 def resolve_initial(initial, moving, target):
     """`initial` of the flow path -> the effective theta [B,nd,nd+1] (a tensor wherever the caller keeps it): a tensor of that shape (or one
     [nd,nd+1] for every pair), or a Register of mode 'rigid' / 'affine' that has run - its .theta, which is already the effective one, and its
@@ -330,9 +336,13 @@ def device_loop_settings(criterions, weights):
 
 
 def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, weights, grad_edges, honor_criterion,
-                   optimizer, init, info, device_loop=False, mask=None, moving_voxel=None, target_voxel=None):
+                   optimizer, init, info, device_loop=False, mask=None, moving_voxel=None, target_voxel=None, overlap=None, moving_mask=None):
     mi = device_loop_settings(criterions, weights) if device_loop else None      # (before anything else: a refused list touches no tensor)
     grids = two_lattices(moving, target, moving_voxel, target_voxel)
+    if overlap or moving_mask is not None:
+        if mi is None:
+            raise ValueError(OVERLAP_SUPPORT)
+        overlap, moving_mask = _engine.overlap_args(overlap, moving_mask, moving)
     if grids:
         if mi is None:
             raise ValueError(GRIDS_SUPPORT)
@@ -358,11 +368,12 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
         B = moving.shape[0]
         init_b = None if init is None else (init.reshape(-1, npose).expand(B, -1) if mode == "rigid" else init.reshape(-1, nd, nd + 1).expand(B, nd, nd + 1))
         solver = AffineMISolver(moving, target, mode=mode, mi=mi, optimizer=optimizer, lr=lr, init=init_b, capacity=max(1, epochs), mask=mask,
-                                moving_voxel=moving_voxel, target_voxel=target_voxel)
+                                moving_voxel=moving_voxel, target_voxel=target_voxel, overlap=overlap, moving_mask=moving_mask)
         solver.run(epochs)
         final_theta, best_theta = solver.current_theta, solver.best
         if epochs == 0:
             best_theta = final_theta.clone()
+        valid = solver.valid_fraction(best_theta) if solver.overlap else None      # one extra evaluation behind the loop, its counts read back
         if grids:
             # two lattices: the thetas handed out are the EFFECTIVE ones - grid_sample(moving, affine_grid(theta, target.shape)) is the warp - and
             # the warps land on the target lattice; the unscaled theta of the last forward goes along for a coarse-to-fine hand-over
@@ -375,6 +386,8 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
         res = dict(losses=solver.losses[:, :epochs], final_theta=final_theta, best_theta=best_theta, best_idx=solver.best_idx, solver=solver)
         if grids:
             res.update(final_unscaled_theta=final_unscaled, world_matrix=world)
+        if valid is not None:
+            res.update(valid_fraction=valid)
         if mode == "rigid":
             res["final_pose"] = solver.param[:, :npose].clone()
     elif spec is None:
@@ -406,7 +419,7 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
 
 def affine_register(moving, target, lr=1E-5, epochs=1000, per=0.1, device="cpu", debug=True, criterions=None,
                     weights=[0.33, 0.33, 0.33], grad_edges=True, *, honor_criterion=False, optimizer="sgd", init=None, info=None,
-                    device_loop=False, mask=None, moving_voxel=None, target_voxel=None):
+                    device_loop=False, mask=None, moving_voxel=None, target_voxel=None, overlap=None, moving_mask=None):
     """ref:warpings.py:30-113.  Returns ([final_warped, best_warped], [final_theta, best_theta]).
 
     NOTE: like the reference, grad_edges defaults to True here when called directly (and then
@@ -420,18 +433,21 @@ def affine_register(moving, target, lr=1E-5, epochs=1000, per=0.1, device="cpu",
     order, (dz, dy, dx) / (dy, dx), both or neither; moving may then also have a spatial shape of its own.  theta acts between the two volumes in
     millimetres (centres coinciding, axes aligned; _engine.grid_scale), the returned thetas are the effective ones of F.affine_grid(theta,
     target.shape), the returned warps lie on the target lattice, and info gains world_matrix (best theta, mm) and final_unscaled_theta.  Differing
-    shapes or voxel sizes anywhere else: ValueError(GRIDS_SUPPORT) before any device work."""
+    shapes or voxel sizes anywhere else: ValueError(GRIDS_SUPPORT) before any device work.
+    overlap, moving_mask (keyword-only extension, with device_loop=True only; ValueError(OVERLAP_SUPPORT) otherwise; also on rigid_register): the
+    overlap rule of _engine.AffineMISolver - only target voxels whose sample lies inside the moving image (and inside moving_mask, [B,1,*moving
+    spatial] or [B,*moving spatial], which implies the rule) count; info gains valid_fraction [B], the share counted at the best theta."""
     return _affine_family("affine", moving, target, lr, epochs, device, debug, criterions, weights, grad_edges,
-                          honor_criterion, optimizer, init, info, device_loop, mask, moving_voxel, target_voxel)
+                          honor_criterion, optimizer, init, info, device_loop, mask, moving_voxel, target_voxel, overlap, moving_mask)
 
 
 def rigid_register(moving, target, lr=1E-5, epochs=1000, per=0.1, device="cpu", debug=True, criterions=None,
                    weights=[0.33, 0.33, 0.33], grad_edges=True, *, honor_criterion=False, optimizer="sgd", init=None, info=None,
-                   device_loop=False, mask=None, moving_voxel=None, target_voxel=None):
+                   device_loop=False, mask=None, moving_voxel=None, target_voxel=None, overlap=None, moving_mask=None):
     """ref:warpings.py:117-174.  `init` = initial pose (default torch.rand on the tensors' device).  moving_voxel / target_voxel: see
     affine_register - with them Theta(pose) is a rigid motion in millimetres whatever the voxel sizes."""
     return _affine_family("rigid", moving, target, lr, epochs, device, debug, criterions, weights, grad_edges,
-                          honor_criterion, optimizer, init, info, device_loop, mask, moving_voxel, target_voxel)
+                          honor_criterion, optimizer, init, info, device_loop, mask, moving_voxel, target_voxel, overlap, moving_mask)
 
 
 class _FlowLossFn(torch.autograd.Function):
@@ -542,6 +558,7 @@ class flow_register(nn.Module):
         self.base_flow = None      # flow_model='bspline': a fixed dense flow the lattice adds to (None = none; Register's coarse-to-fine loop)
         self.velocity = self.final_velocity = self.inverse_flow = None   # diffeomorphic=True: see the class docstring
         self.initial = None        # optimize(initial=...): the effective theta [B,nd,nd+1] the deformation is composed with
+        self.valid_fraction = None  # optimize(initial=..., overlap=True): [B], the share of target voxels counted at `.flow`
 
     def _deform(self, x, flow):
         if self.initial is not None:
@@ -563,13 +580,20 @@ class flow_register(nn.Module):
         """Whether optimize() takes initial=: the B-spline mutual-information loop (MILoss alone, not diffeomorphic)."""
         return self.flow_model == "bspline" and not self.diffeomorphic and len(self.criterions) == 1 and isinstance(self.criterions[0], MILoss)
 
-    def optimize(self, moving, target, device=None, debug=True, grad_edges=False, *, mask=None, initial=None):
+    def optimize(self, moving, target, device=None, debug=True, grad_edges=False, *, mask=None, initial=None, overlap=None, moving_mask=None):
         """mask (keyword-only extension): a region of interest on the target lattice, [B,1,*spatial] or [B,*spatial], non-zero = the voxel counts,
         for MILoss alone with flow_model='direct' (3-D) or 'bspline'; ValueError anywhere else, before any device work.
-        initial (keyword-only extension): see the class docstring; ValueError(INITIAL_SUPPORT) anywhere else, before any device work."""
+        initial (keyword-only extension): see the class docstring; ValueError(INITIAL_SUPPORT) anywhere else, before any device work.
+        overlap, moving_mask (keyword-only extension, with initial= only; ValueError(OVERLAP_SUPPORT) anywhere else, before any device work): the
+        overlap rule of _engine.BSplineSolver - a target voxel counts while its composed sample lies inside the moving image (and inside
+        moving_mask on the moving lattice, which implies the rule); `.valid_fraction` [B] is the share counted at `.flow`."""
         if grad_edges:
             raise NotImplementedError("grad_edges=True is not supported (SURVEY Q6)")
-        self.initial = None
+        self.initial = self.valid_fraction = None
+        if overlap or moving_mask is not None:
+            if initial is None or not self.initial_supported():
+                raise ValueError(OVERLAP_SUPPORT)
+            overlap, moving_mask = _engine.overlap_args(overlap, moving_mask, moving)
         if initial is not None:
             if not self.initial_supported():
                 raise ValueError(INITIAL_SUPPORT)
@@ -590,7 +614,7 @@ class flow_register(nn.Module):
                     return self._optimize_unet(moving, target, spec, debug)
             return self._optimize_unet(moving, target, spec, debug)
         if self.flow_model == "bspline":
-            return self._optimize_bspline(moving, target, spec, debug, mask, initial)
+            return self._optimize_bspline(moving, target, spec, debug, mask, initial, overlap, moving_mask)
         lncc = mi = None
         if spec is None and moving.dim() == 5 and len(self.criterions) == 1 and isinstance(self.criterions[0], MILoss):
             # direct flow + mutual information (+ smoothness) as ONE device-side loop (trx_flow_mi_run); ranges fitted once to (target, moving)
@@ -619,13 +643,14 @@ class flow_register(nn.Module):
         if debug:
             print("Optimization ended with status: %s" % message)
 
-    def _optimize_bspline(self, moving, target, spec, debug, mask=None, initial=None):
+    def _optimize_bspline(self, moving, target, spec, debug, mask=None, initial=None, overlap=None, moving_mask=None):
         """The 'direct' loop with a control lattice as the parameter: one trx_bspline_run call, per-pair early stop on the device, one host sync."""
         from ._engine import BSplineSolver
         mi = self.criterions[0].settings(self.weights[0]) if spec is None else None     # __init__ admits MILoss alone beside the fused criteria
         solver = BSplineSolver(moving, target, self.spacing, loss=spec, mi=mi, optimizer=self.optimizer_kind, lr=self.lr, init=self.init_control,
                                base=self.base_flow, capacity=max(1, self.max_epochs), stop_crit=self.stop_crit, keep_last=True,
-                               bending_weight=self.bending_weight, squarings=self.squarings if self.diffeomorphic else None, mask=mask, initial=initial)
+                               bending_weight=self.bending_weight, squarings=self.squarings if self.diffeomorphic else None, mask=mask, initial=initial,
+                               overlap=overlap, moving_mask=moving_mask)
         self.initial = initial
         solver.run(self.max_epochs)
         done = solver.step.cpu()
@@ -640,6 +665,8 @@ class flow_register(nn.Module):
         self.losses = solver.losses[:, :n]
         self.iterations = done
         self.solver = solver
+        if solver.overlap:
+            self.valid_fraction = solver.valid_fraction(self.flow)      # at the flow handed out: the last forward's
         message = "Converged to %f" % self.stop_crit if bool((solver.stopped != 0).all()) else "Reached max epochs"
         if debug:
             print("Optimization ended with status: %s" % message)
