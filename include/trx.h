@@ -59,7 +59,10 @@ extern "C" {
  *        Later addition under the same number: trx_affine_flow_warp, trx_affine_flow_warp_backward, trx_bspline_mi_run_grids (a flow composed with an
  *        initial affine and sampled once in a moving image on its own lattice; the B-spline mutual-information loop over it) - new entry points only.
  *        Later addition under the same number: trx_spline_workspace_bytes, trx_spline_coefficients, trx_transform_resample (nearest-neighbour and cubic
- *        B-spline resampling through the final transform) - new entry points only. */
+ *        B-spline resampling through the final transform) - new entry points only.
+ *        Later addition under the same number: trx_moving_grid grows by one trailing field, `world` (voxel-to-world geometry for the rigid / affine
+ *        mutual-information entry points; NULL = the scale, the launches and bits of before), trx_affine_world_theta, trx_image_moments and its
+ *        workspace query - no entry point changed its signature. */
 #define TRX_VERSION 240
 #define TRX_PSTRIDE 12  /* floats per pair in theta / param / adam / best_theta arrays */
 
@@ -624,7 +627,35 @@ typedef struct {
                                   * below.  Later addition under TRX_VERSION 240, like `mask`: a caller built against the shorter struct must zero both */
     const unsigned char *mask;   /* device [B][D][H][W] of THIS (moving) lattice, dense, nullable; non-zero = the moving voxel counts.  Needs overlap != 0
                                   * (TRX_ERR_ARG otherwise).  Read on the device on every evaluation: it must outlive the call / run */
+    const double *world;         /* device [B][TRX_WORLD_STRIDE], nullable: world geometry (below).  When given, `scale` is not read.  Read on the device on
+                                  * every evaluation: it must outlive the call / run.  Later addition under TRX_VERSION 240: a caller built against the
+                                  * shorter struct must zero it, like `overlap` and `mask` */
 } trx_moving_grid;
+/* World geometry (elastix AutomaticTransformInitialization, ITK CenteredTransformInitializer, ANTs -r): each image carries a
+ * voxel-to-world matrix A (columns in the tensor's axis order d, h, w; rows world x, y, z, in mm), and theta acts in world millimetres about a centre c
+ * behind a fixed world transform T0:  p_moving = T0 Tr(c) Theta Tr(-c) p_target,  Theta = [theta[:, :nd] | l (.) theta[:, nd]] (homogeneous),
+ * l_r = sum_a |A_m[r][a]| S_m,a / 2 the half extent of the moving volume's bounding box along world axis r.  With N(S) the map from affine_grid's
+ * normalised coordinate (x, y, z order) to the voxel index (d, h, w order), i_a = ((n_a + 1) S_a - 1) / 2:
+ *   R = Tr(-c) A_t N(S_t),   L = N(S_m)^-1 A_m^-1 T0 Tr(c),   theta_eff = (L Theta R)[:nd].
+ * The record of pair b, TRX_WORLD_STRIDE doubles, made by the caller on the host in fp64: L row-major [nd][nd + 1] at offset 0, R row-major
+ * [nd][nd + 1] at offset 12, l [nd] at offset 24; the rest is not read.  One record per pair: every patient has their own origin.
+ * theta_eff is formed once per block, where theta (.) scale is formed otherwise, in fp64 with one IEEE multiply and one IEEE add per term (no
+ * contraction), each sum in ascending index order with the homogeneous term last:
+ *   M[r][j] = sum_{c < nd} theta[r][c] R[c][j]  (+ l_r theta[r][nd] for j = nd),   theta_eff[i][j] = sum_{r < nd} L[i][r] M[r][j]  (+ L[i][nd] for j = nd),
+ * rounded once to fp32.  trx_affine_world_theta runs the same device function: its output is, bit for bit, the theta the passes sample at, and a call
+ * with that theta, scale 1 and no record gives the same counts and the same loss bits.  The voxel loop is the one of the other instances.
+ * Gradient, in fp64 behind reduce_partials (whose order does not change): g[i][j] = (S_m,i / 2) (sum of the partial rows)[i][j] = dL/dtheta_eff;
+ *   P[r][j] = sum_i L[i][r] g[i][j];   dtheta[r][c < nd] = sum_{j <= nd} P[r][j] R[c][j];   dtheta[r][nd] = l_r P[r][nd].
+ * The state (theta, param, best_theta) stays the unscaled theta, as under `scale`.
+ * Honoured by trx_affine_mi_loss_grad_grids and trx_affine_mi_run_grids, alone, with cfg->mask and under the overlap rule (instances of their own,
+ * *_world_kernel; the other instances keep their code).  Every other entry point that takes a trx_moving_grid - trx_affine_warp_grids,
+ * trx_affine_flow_warp / _backward / _valid, trx_bspline_mi_run_grids, trx_transform_resample - refuses a non-NULL `world` with TRX_ERR_ARG before any HIP call: they take the effective theta
+ * (trx_affine_world_theta) and scale 1.  trx_bspline_mi_grids_workspace_bytes is host arithmetic on sizes and ignores it, as it ignores the scale.  The entries of a record
+ * are device memory and cannot be checked on the host: a non-finite entry gives a non-finite theta_eff, hence loss, for that pair only. */
+#define TRX_WORLD_STRIDE 32
+#define TRX_WORLD_L 0
+#define TRX_WORLD_R 12
+#define TRX_WORLD_EXT 24
 /* The overlap rule (elastix -mMask and its discarded samples, NiftyReg -fmask / NaN padding, ITK's Mattes metric): with
  * mg->overlap != 0, target voxel v of pair b with un-normalised moving coordinate i (x, y(, z)), formed exactly as the sampling kernel forms it, is
  *   valid(v) = (cfg->mask at v, if any)  and  0 <= i_a <= S_m,a - 1 on every axis a  and  (mg->mask at rint(i) != 0, if any)
@@ -644,6 +675,23 @@ int trx_affine_mi_run_grids(const trx_volumes *vol, const trx_moving_grid *mg /*
  * layout: vol->moving_stride between batch items).  vol->target is not read.  Equal sizes and scale == 1: trx_affine_warp itself, the same bits.  No
  * backward; the nearest-neighbour and cubic forms are trx_transform_resample. */
 int trx_affine_warp_grids(const trx_volumes *vol, const trx_moving_grid *mg /*[host]*/, const float *theta, int channels, float *out, void *stream);
+/* theta_eff[B][TRX_PSTRIDE] of theta[B][TRX_PSTRIDE] under mg->world (the device function of the two passes: the same bits; entries past
+ * ndim (ndim + 1) are written as 0).  One launch, no workspace; of mg only `world` is read.  Later addition under TRX_VERSION 240.  Refusals before
+ * any HIP call: TRX_ERR_ARG (mg, mg->world, theta or theta_eff NULL, B outside 1 .. 65535), TRX_ERR_NDIM. */
+int trx_affine_world_theta(const trx_moving_grid *mg /*[host]*/, int ndim, int B, const float *theta, float *theta_eff, void *stream);
+
+/* ---- Intensity moments of N volumes (the centre-of-mass initialiser of DESIGN.md section 4.17).  Extension; later addition under TRX_VERSION 240.
+ * x: N volumes [D][H][W] fp32 contiguous (2-D: ndim 2, D = 1); mask: dense uint8 [N][D][H][W], nullable, non-zero = the voxel counts; offset: device
+ * [N] fp32, nullable (= 0).  out [N][1 + ndim] fp64: sum w, sum w x, sum w y(, sum w z) over the counted voxels with w = v - offset[n] (formed in
+ * fp64) and (x, y, z) the voxel's index along W, H, D - voxel-index units, theta's axis order.  Each block sums kMomChunk consecutive voxels of one
+ * volume in fp64 (per thread in ascending voxels, a fixed shuffle tree, the waves in order) into a partial row; one wave per volume then sums the
+ * rows in a fixed order.  No atomics: the same bits on every call, and a volume's sums do not depend on N.  4 B/voxel read (5 with a mask), two
+ * launches.  Workspace: trx_image_moments_workspace_bytes (the partial rows; 0 = arguments rejected: ndim outside 2 .. 3, D != 1 in 2-D, a size < 1,
+ * N outside 1 .. 65535, >= 2^31 voxels per volume).  Refusals before any HIP call: TRX_ERR_ARG (x, out or workspace NULL, the sizes above),
+ * TRX_ERR_NDIM, TRX_ERR_WORKSPACE. */
+size_t trx_image_moments_workspace_bytes(int ndim, int N, int D, int H, int W);
+int trx_image_moments(const float *x, const unsigned char *mask /*nullable*/, const float *offset /*nullable*/, int ndim, int N, int D, int H, int W,
+                      double *out /*[N][1 + ndim]*/, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- A deformation composed with an initial affine, sampled ONCE (what elastix, NiftyReg and ANTs do with the transform of the
  * stage before).  Extension.  Later addition under TRX_VERSION 240.  vol describes the TARGET lattice S_t = (D, H, W); vol->moving holds

@@ -1559,6 +1559,278 @@ def grid_scale(moving_shape, target_shape, moving_voxel=None, target_voxel=None)
     return scale
 
 
+def _norm_to_voxel(shape, inverse=False):
+    """N(S) [nd+1, nd+1] fp64: affine_grid's normalised coordinate (x, y(, z) order) -> the voxel index in the tensor's axis order (d, h, w),
+    i_a = ((n_a + 1) S_a - 1) / 2 with x <-> w, y <-> h, z <-> d; inverse: its exact inverse n_a = (2 i_a + 1) / S_a - 1."""
+    nd = len(shape)
+    N = torch.zeros(nd + 1, nd + 1, dtype=torch.float64)
+    for a, S in enumerate(shape):
+        if inverse:
+            N[nd - 1 - a, a], N[nd - 1 - a, nd] = 2.0 / S, 1.0 / S - 1.0
+        else:
+            N[a, nd - 1 - a], N[a, nd] = S / 2.0, (S - 1) / 2.0
+    N[nd, nd] = 1.0
+    return N
+
+
+def _world_shapes(moving_shape, target_shape):
+    moving_shape, target_shape = tuple(int(s) for s in moving_shape), tuple(int(s) for s in target_shape)
+    nd = len(target_shape)
+    if nd not in (2, 3) or len(moving_shape) != nd or min(moving_shape + target_shape) < 1:
+        raise ValueError(f"expected two spatial shapes of 2 or 3 positive sizes, got {moving_shape} and {target_shape}")
+    return moving_shape, target_shape, nd
+
+
+def _world_affine(A, nd, name, B=None):
+    """A voxel-to-world matrix [nd+1, nd+1] (shared) or [B, nd+1, nd+1] -> fp64 [B | 1, nd+1, nd+1] on the CPU.  ValueError for a wrong shape, a
+    non-finite entry, a last row that is not (0, ..., 0, 1) within 1e-6, or a linear part whose condition number exceeds 1e8."""
+    A = torch.as_tensor(A).detach().to("cpu", torch.float64)
+    if A.dim() == 2:
+        A = A[None]
+    if A.dim() != 3 or tuple(A.shape[1:]) != (nd + 1, nd + 1) or (B is not None and A.shape[0] not in (1, B)):
+        raise ValueError(f"{name} must be [{nd + 1}, {nd + 1}] or [B, {nd + 1}, {nd + 1}]" + ("" if B is None else f" with B = {B}") + f", got {tuple(A.shape)}")
+    if not bool(torch.isfinite(A).all()):
+        raise ValueError(f"{name} has a non-finite entry")
+    last = torch.zeros(nd + 1, dtype=torch.float64)
+    last[nd] = 1.0
+    if float((A[:, nd] - last).abs().max()) > 1e-6:
+        raise ValueError(f"{name}: the last row must be (0, ..., 0, 1), got {A[:, nd].tolist()}")
+    sv = torch.linalg.svdvals(A[:, :nd, :nd])
+    if bool((sv[:, -1] <= 0).any()) or float((sv[:, 0] / sv[:, -1]).max()) > 1e8:
+        raise ValueError(f"{name}: the linear part is singular or ill-conditioned (condition number above 1e8)")
+    A = A.clone()
+    A[:, nd] = last
+    return A
+
+
+def _translation(t):
+    """[B, nd] -> homogeneous translations [B, nd+1, nd+1] fp64."""
+    B, nd = t.shape
+    T = torch.eye(nd + 1, dtype=torch.float64).repeat(B, 1, 1)
+    T[:, :nd, nd] = t
+    return T
+
+
+def lattice_center(shape, affine):
+    """[B | 1, nd] fp64: the world position (x, y(, z)) of the geometric centre of a lattice, affine . ((S - 1) / 2)."""
+    shape = tuple(int(s) for s in shape)
+    A = _world_affine(affine, len(shape), "affine")
+    mid = torch.tensor([(s - 1) / 2.0 for s in shape] + [1.0], dtype=torch.float64)
+    return (A @ mid)[:, : len(shape)]
+
+
+def level_affine(affine, full_shape, level_shape):
+    """The voxel-to-world matrix of a pyramid level (align_corners=False keeps the field of view): A . [diag(S / S_l) | S / (2 S_l) - 1/2]."""
+    nd = len(full_shape)
+    A = _world_affine(affine, nd, "affine")
+    M = torch.eye(nd + 1, dtype=torch.float64)
+    for a, (S, Sl) in enumerate(zip(full_shape, level_shape)):
+        M[a, a], M[a, nd] = S / Sl, S / (2.0 * Sl) - 0.5
+    return A @ M
+
+
+class WorldGeometry:
+    """What world_geometry makes, all fp64 on the CPU: record [B, 32] (include/trx.h: trx_moving_grid.world - L | R | l),
+    center [B, nd] = c, init [B, nd+1, nd+1] = T0, extent [B, nd] = l.  Iterates as (record, center)."""
+
+    def __init__(self, record, center, init, extent):
+        self.record, self.center, self.init, self.extent = record, center, init, extent
+        self.B, self.nd = center.shape
+
+    def __iter__(self):
+        return iter((self.record, self.center))
+
+    def pair(self, b):
+        return WorldGeometry(self.record[b:b + 1], self.center[b:b + 1], self.init[b:b + 1], self.extent[b:b + 1])
+
+    def L(self):
+        nd = self.nd
+        return self.record[:, _lib.WORLD_L:_lib.WORLD_L + nd * (nd + 1)].reshape(-1, nd, nd + 1)
+
+    def R(self):
+        nd = self.nd
+        return self.record[:, _lib.WORLD_R:_lib.WORLD_R + nd * (nd + 1)].reshape(-1, nd, nd + 1)
+
+    def matrix(self, theta):
+        """T [B, nd+1, nd+1] fp64 of the UNSCALED theta [B, nd, nd+1]: p_moving = T p_target = T0 Tr(c) Theta Tr(-c) p_target (world mm, x, y(, z))."""
+        nd = self.nd
+        th = theta.detach().to("cpu", torch.float64).reshape(-1, nd, nd + 1)
+        Th = torch.eye(nd + 1, dtype=torch.float64).repeat(th.shape[0], 1, 1)
+        Th[:, :nd, :nd] = th[:, :, :nd]
+        Th[:, :nd, nd] = th[:, :, nd] * self.extent
+        return self.init @ _translation(self.center) @ Th @ _translation(-self.center)
+
+
+def world_geometry(moving_shape, target_shape, moving_affine, target_affine, init=None, center=None):
+    """The world-geometry record of the fused rigid / affine mutual-information loop (include/trx.h: trx_moving_grid.world).
+    Host arithmetic in fp64 only.  Shapes in the tensors' axis order; an affine is the voxel-to-world matrix [nd+1, nd+1] (one for every pair) or
+    [B, nd+1, nd+1], columns in the tensor's axis order (d, h, w) - nibabel's img.affine for get_fdata() put into [B,1,*shape] - rows world x, y(, z).
+    init: T0, a world transform [nd+1, nd+1] / [B, nd+1, nd+1] in front of what is optimised, None = identity, or 'centers' = the translation
+    taking the target's geometric centre to the moving image's.  center: c [nd] / [B, nd] in world mm, None = the target's geometric centre.
+    With T = T0 Tr(c) Theta Tr(-c), Theta = [theta[:, :nd] | l (.) theta[:, nd]]:  R = Tr(-c) A_t N(S_t),  L = N(S_m)^-1 A_m^-1 T0 Tr(c),
+    l_r = sum_a |A_m[r][a]| S_m,a / 2, and theta_eff = (L Theta R)[:nd].  Returns a WorldGeometry; `record, c = world_geometry(...)` unpacks it."""
+    ms, ts, nd = _world_shapes(moving_shape, target_shape)
+    if moving_affine is None or target_affine is None:
+        raise ValueError("moving_affine and target_affine go together: give both voxel-to-world matrices or neither")
+    Am, At = _world_affine(moving_affine, nd, "moving_affine"), _world_affine(target_affine, nd, "target_affine")
+    B = max(Am.shape[0], At.shape[0])
+    if isinstance(init, str):
+        if init != "centers":
+            raise ValueError(f"init must be None, 'centers' or a matrix, got {init!r}")
+        T0 = _translation((lattice_center(ms, Am) - lattice_center(ts, At)).expand(B, nd))
+    else:
+        T0 = torch.eye(nd + 1, dtype=torch.float64)[None] if init is None else _world_affine(init, nd, "init")
+    c = lattice_center(ts, At) if center is None else torch.as_tensor(center).detach().to("cpu", torch.float64).reshape(-1, nd)
+    if not bool(torch.isfinite(c).all()):
+        raise ValueError("center has a non-finite entry")
+    B = max(B, T0.shape[0], c.shape[0])
+    for t, name in ((Am, "moving_affine"), (At, "target_affine"), (T0, "init"), (c, "center")):
+        if t.shape[0] not in (1, B):
+            raise ValueError(f"{name} is given for {t.shape[0]} pairs, the others for {B}")
+    Am, At, T0, c = (t.expand(B, *t.shape[1:]).contiguous() for t in (Am, At, T0, c))
+    R = _translation(-c) @ At @ _norm_to_voxel(ts)
+    L = _norm_to_voxel(ms, inverse=True) @ torch.stack([torch.linalg.inv(a) for a in Am]) @ T0 @ _translation(c)      # (one matrix at a time: a pair's record does not depend on its batch)
+    ext = (Am[:, :nd, :nd].abs() * torch.tensor(ms, dtype=torch.float64)[None, None, :]).sum(2) / 2.0
+    rec = torch.zeros(B, _lib.WORLD_STRIDE, dtype=torch.float64)
+    rec[:, _lib.WORLD_L:_lib.WORLD_L + nd * (nd + 1)] = L[:, :nd].reshape(B, -1)
+    rec[:, _lib.WORLD_R:_lib.WORLD_R + nd * (nd + 1)] = R[:, :nd].reshape(B, -1)
+    rec[:, _lib.WORLD_EXT:_lib.WORLD_EXT + nd] = ext
+    return WorldGeometry(rec, c, T0, ext)
+
+
+def world_theta_host(theta, record, nd):
+    """theta_eff [B, nd, nd+1] fp32 of the UNSCALED theta under a record, on the host with the device function's own operations (include/trx.h: fp64, one
+    multiply and one add per term, ascending index order, the homogeneous term last, one rounding to fp32): the bits of trx_affine_world_theta."""
+    import numpy as np
+    th = theta.detach().to("cpu", torch.float32).reshape(-1, nd, nd + 1).double().numpy()
+    rec = record.detach().to("cpu", torch.float64).numpy()
+    B, NC = th.shape[0], nd + 1
+    out = np.zeros((B, nd, NC), dtype=np.float32)
+    for b in range(B):
+        L = rec[b, _lib.WORLD_L:_lib.WORLD_L + nd * NC].reshape(nd, NC)
+        R = rec[b, _lib.WORLD_R:_lib.WORLD_R + nd * NC].reshape(nd, NC)
+        ext = rec[b, _lib.WORLD_EXT:_lib.WORLD_EXT + nd]
+        M = np.zeros((nd, NC))
+        for r in range(nd):
+            for j in range(NC):
+                s = th[b, r, 0] * R[0, j]
+                for c in range(1, nd):
+                    s = s + th[b, r, c] * R[c, j]
+                if j == nd:
+                    s = s + ext[r] * th[b, r, nd]
+                M[r, j] = s
+        for i in range(nd):
+            for j in range(NC):
+                s = L[i, 0] * M[0, j]
+                for r in range(1, nd):
+                    s = s + L[i, r] * M[r, j]
+                if j == nd:
+                    s = s + L[i, nd]
+                out[b, i, j] = np.float32(s)
+    return torch.from_numpy(out)
+
+
+def world_chain_host(g_eff, record, nd):
+    """dL/dtheta [B, nd, nd+1] fp64 (the UNSCALED theta) from g_eff = dL/dtheta_eff [B, nd, nd+1] under a record: P = L[:, :nd]^T g,
+    dtheta[:, :nd] = P R^T, dtheta[:, nd] = l (.) P[:, nd] - the chain rule the kernels apply behind the reduction."""
+    g = g_eff.detach().to("cpu", torch.float64).reshape(-1, nd, nd + 1)
+    rec = record.detach().to("cpu", torch.float64)
+    L = rec[:, _lib.WORLD_L:_lib.WORLD_L + nd * (nd + 1)].reshape(-1, nd, nd + 1)
+    R = rec[:, _lib.WORLD_R:_lib.WORLD_R + nd * (nd + 1)].reshape(-1, nd, nd + 1)
+    ext = rec[:, _lib.WORLD_EXT:_lib.WORLD_EXT + nd]
+    P = L[:, :, :nd].transpose(1, 2) @ g
+    out = torch.zeros_like(g)
+    out[:, :, :nd] = P @ R.transpose(1, 2)
+    out[:, :, nd] = ext * P[:, :, nd]
+    return out
+
+
+def _homogeneous(theta, nd):
+    th = torch.as_tensor(theta).detach().to("cpu", torch.float64).reshape(-1, nd, nd + 1)
+    H = torch.eye(nd + 1, dtype=torch.float64).repeat(th.shape[0], 1, 1)
+    H[:, :nd] = th
+    return H
+
+
+def theta_from_world(matrix, moving_affine, target_affine, moving_shape, target_shape):
+    """A world transform from any tool, p_moving = matrix p_target (mm, [nd+1, nd+1] or [B, nd+1, nd+1]) -> the EFFECTIVE theta [B, nd, nd+1] fp64 that
+    resample(theta=), affine_warp(size=) and optim(initial=) take: (N(S_m)^-1 A_m^-1 matrix A_t N(S_t))[:nd].  Host arithmetic in fp64."""
+    ms, ts, nd = _world_shapes(moving_shape, target_shape)
+    T, Am, At = _world_affine(matrix, nd, "matrix"), _world_affine(moving_affine, nd, "moving_affine"), _world_affine(target_affine, nd, "target_affine")
+    return (_norm_to_voxel(ms, inverse=True) @ torch.linalg.inv(Am) @ T @ At @ _norm_to_voxel(ts))[:, :nd]
+
+
+def world_from_theta(theta, moving_affine, target_affine, moving_shape, target_shape):
+    """The inverse of theta_from_world: an effective theta [nd, nd+1] / [B, nd, nd+1] -> the world transform [B, nd+1, nd+1] fp64,
+    A_m N(S_m) theta N(S_t)^-1 A_t^-1."""
+    ms, ts, nd = _world_shapes(moving_shape, target_shape)
+    Am, At = _world_affine(moving_affine, nd, "moving_affine"), _world_affine(target_affine, nd, "target_affine")
+    return Am @ _norm_to_voxel(ms) @ _homogeneous(theta, nd) @ _norm_to_voxel(ts, inverse=True) @ torch.linalg.inv(At)
+
+
+def image_moments(x, mask=None):
+    """(mass [B], centre [B, nd]) fp64 on x's device (include/trx.h: trx_image_moments): x [B,1,*spatial] fp32 on the GPU, mask (see _mask_u8, on
+    x's lattice) or None.  The weights are v - the volume's minimum over the counted voxels, so the centre is that of the contrast; it is in voxel
+    indices, in the TENSOR's axis order.  ValueError for a volume without contrast (mass 0) or an empty mask.  Deterministic; reads the result back."""
+    _require_gpu(x, "x")
+    if x.dim() not in (4, 5) or x.shape[1] != 1:
+        raise ValueError(f"expected [B,1,H,W] or [B,1,D,H,W], got {tuple(x.shape)}")
+    lib = _lib.load()
+    vol = x.detach().float().contiguous()
+    B, nd, dev = vol.shape[0], vol.dim() - 2, vol.device
+    D, H, W = _dhw(tuple(vol.shape[2:]))
+    flat = vol.reshape(B, -1)
+    m8 = None
+    if mask is not None:
+        m8 = _mask_u8(mask, vol)
+        if bool((m8.reshape(B, -1).sum(1) == 0).any()):
+            raise ValueError("image_moments: a mask is empty")
+        offset = torch.where(m8.reshape(B, -1) != 0, flat, torch.full_like(flat, float("inf"))).amin(1).contiguous()
+    else:
+        offset = flat.amin(1).contiguous()
+    ws_bytes = lib.trx_image_moments_workspace_bytes(nd, B, D, H, W)
+    if ws_bytes == 0:
+        raise _lib.TrxError(f"trx_image_moments_workspace_bytes rejected {B} x {tuple(vol.shape[2:])}")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(B, 1 + nd, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.trx_image_moments(_lib.ptr(vol), _lib.ptr(m8), _lib.ptr(offset), nd, B, D, H, W, _lib.ptr(out), _lib.ptr(ws), ws_bytes, _lib.current_stream(dev))
+    _lib.check(rc, "trx_image_moments")
+    mass = out[:, 0]
+    if bool((mass <= 0).any()) or not bool(torch.isfinite(out).all()):
+        raise ValueError("image_moments: a volume has no contrast over the counted voxels (or a non-finite voxel)")
+    return mass, (out[:, 1:] / mass[:, None]).flip(1)
+
+
+WORLD_INITS = (None, "centers", "moments")
+
+
+def world_setup(moving, target, moving_affine, target_affine, world_init=None, mask=None, moving_mask=None):
+    """WorldGeometry of a pair of tensors [B,1,*spatial] from their headers and world_init: None (trust the headers: T0 = I, c = the target's geometric
+    centre), 'centers' (T0 = the translation between the geometric centres), 'moments' (T0 = the translation between the intensity centres of mass -
+    image_moments inside mask / moving_mask where given - and c = the target's centre of mass) or a world matrix [nd+1, nd+1] / [B, nd+1, nd+1]."""
+    ms, ts, nd = _world_shapes(moving.shape[2:], target.shape[2:])
+    B = target.shape[0]
+    if isinstance(world_init, str) and world_init not in WORLD_INITS:
+        raise ValueError(f"world_init must be None, 'centers', 'moments' or a matrix, got {world_init!r}")
+    Am, At = _world_affine(moving_affine, nd, "moving_affine", B), _world_affine(target_affine, nd, "target_affine", B)
+    if isinstance(world_init, str) and world_init == "moments":
+        def com(x, A, m):
+            ctr = image_moments(x, m)[1].cpu()                                       # voxel indices, the tensor's axis order: A's columns
+            return (A[:, :nd, :nd] @ ctr[:, :, None])[:, :, 0] + A[:, :nd, nd]
+        cm, ct = com(moving, Am, moving_mask), com(target, At, mask)
+        geo = world_geometry(ms, ts, Am, At, _translation(cm - ct), ct)
+    else:
+        if world_init is not None and not isinstance(world_init, str):
+            world_init = _world_affine(world_init, nd, "world_init", B)
+        geo = world_geometry(ms, ts, Am, At, world_init)
+    if geo.B not in (1, B):
+        raise ValueError(f"the headers describe {geo.B} pairs, the batch has {B}")
+    if geo.B != B:
+        geo = WorldGeometry(*(t.expand(B, *t.shape[1:]).contiguous() for t in (geo.record, geo.center, geo.init, geo.extent)))
+    return geo
+
+
 class _GridPair:
     """B single-channel (moving, target) pairs on two lattices, described for the cross-lattice entry points (include/trx.h: trx_moving_grid):
     the Volumes carry the TARGET lattice and its base-coordinate tables, the MovingGrid the moving lattice and the scales.  _Batch keeps
@@ -1588,15 +1860,17 @@ class _GridPair:
     def vol(self):
         return _volumes(self.moving, self.target, self.moving[0].numel(), self.target[0].numel(), self.spatial, tables=self.tables)
 
-    def grid(self, overlap=False, moving_mask=None):
-        return _moving_grid(self.moving_spatial, self.scale, overlap, moving_mask)
+    def grid(self, overlap=False, moving_mask=None, world=None):
+        return _moving_grid(self.moving_spatial, self.scale, overlap, moving_mask, world)
 
 
-def _moving_grid(moving_spatial, scale=None, overlap=False, moving_mask=None):
+def _moving_grid(moving_spatial, scale=None, overlap=False, moving_mask=None, world=None):
     """trx_moving_grid of a moving lattice (the tensor's spatial shape) and a scale [nd, nd+1] (None: ones); overlap / moving_mask (uint8 on the
-    device, kept alive by the caller): the overlap rule and its mask on the moving lattice."""
+    device, kept alive by the caller): the overlap rule and its mask on the moving lattice; world (fp64 [B, 32] on the device, kept alive by the
+    caller): the world-geometry records, in whose presence the scale is not read."""
     g = _lib.MovingGrid()
     g.overlap, g.mask = int(bool(overlap)), None if moving_mask is None else moving_mask.data_ptr()
+    g.world = None if world is None else world.data_ptr()
     g.D, g.H, g.W = _dhw(tuple(moving_spatial))
     nd = len(moving_spatial)
     flat = [1.0] * (nd * (nd + 1)) if scale is None else [float(s) for s in scale.reshape(-1)]
@@ -1835,8 +2109,32 @@ def resample(x, *, theta=None, flow=None, size=None, scale=None, interpolation="
     return out
 
 
+def _world_record(world, B, dev):
+    """The records [B, 32] (a WorldGeometry or a tensor) as a contiguous fp64 tensor on `dev`."""
+    rec = world.record if isinstance(world, WorldGeometry) else torch.as_tensor(world)
+    if tuple(rec.shape) != (B, _lib.WORLD_STRIDE):
+        raise ValueError(f"expected world-geometry records of shape {(B, _lib.WORLD_STRIDE)}, got {tuple(rec.shape)}")
+    return rec.detach().to(device=dev, dtype=torch.float64).contiguous()
+
+
+def affine_world_theta(theta, world):
+    """theta_eff [B, nd, nd+1] fp32 of the UNSCALED theta [B, nd, nd+1] (on the GPU) under world-geometry records (a WorldGeometry or [B, 32]):
+    trx_affine_world_theta - the device function of the fused passes, so bit for bit the theta they sample at."""
+    _require_gpu(theta, "theta")
+    B, nd, dev = theta.shape[0], theta.shape[-1] - 1, theta.device
+    rec = _world_record(world, B, dev)
+    th = pad_theta(theta.detach().reshape(B, -1), nd)
+    out = torch.empty(B, PSTRIDE, device=dev)
+    mg = _lib.MovingGrid()
+    mg.world = rec.data_ptr()
+    with torch.cuda.device(dev):
+        rc = _lib.load().trx_affine_world_theta(ctypes.byref(mg), nd, B, _lib.ptr(th), _lib.ptr(out), _lib.current_stream(dev))
+    _lib.check(rc, "trx_affine_world_theta")
+    return out[:, : nd * (nd + 1)].reshape(B, nd, nd + 1)
+
+
 def affine_mi_loss_grad(moving, target, theta, rng, bins=32, alpha=1.0, normalized=False, need_grad=True, mask=None, scale=None, overlap=None,
-                        moving_mask=None, return_counts=False):
+                        moving_mask=None, return_counts=False, world=None):
     """Mutual information of (target, affine warp of moving by theta) and its gradient with respect to theta without a warped volume (extension,
     include/trx.h: trx_affine_mi_loss_grad): moving / target [B,1,*spatial] fp32 on the GPU, theta [B,nd,nd+1], rng [B,4] (mi_range), mask (see
     _mask_u8) or None = every voxel.  Returns (loss [B], dtheta [B,nd,nd+1] or None) - what affine_warp -> mi_loss_grad -> affine_warp_backward
@@ -1846,12 +2144,16 @@ def affine_mi_loss_grad(moving, target, theta, rng, bins=32, alpha=1.0, normaliz
     the target's.  With moving's shape equal to target's and scale None this is the one-lattice entry point, the bits of before.
     overlap / moving_mask (overlap_args): only target voxels whose sample lies inside the moving image - and inside
     moving_mask [B,1,*moving spatial], looked up at the nearest moving voxel - count; the call then goes through the cross-lattice entry point
-    whatever the shapes.  return_counts: a third result, the pairs' joint tables uint64-as-int64 [B,K,K] (2^31 units per counted voxel)."""
+    whatever the shapes.  return_counts: a third result, the pairs' joint tables uint64-as-int64 [B,K,K] (2^31 units per counted voxel).
+    world (a WorldGeometry or records [B, 32]; not with scale): theta_eff = (L Theta R)[:nd] instead, dtheta through the matrix
+    chain rule; also the cross-lattice entry point."""
     if mask is not None:
         mask = _mask_u8(mask, target)
     overlap, moving_mask = overlap_args(overlap, moving_mask, moving)
+    if world is not None and scale is not None:
+        raise ValueError("world replaces scale: give one of them")
     lib = _lib.load()
-    two = overlap or scale is not None or (isinstance(moving, torch.Tensor) and isinstance(target, torch.Tensor) and moving.shape[2:] != target.shape[2:])
+    two = overlap or scale is not None or world is not None or (isinstance(moving, torch.Tensor) and isinstance(target, torch.Tensor) and moving.shape[2:] != target.shape[2:])
     pair = _GridPair(moving, target, scale) if two else _mi_pair_batch(moving, target)
     B, nd, dev = pair.B, pair.nd, pair.device
     if tuple(rng.shape) != (B, 4):
@@ -1871,7 +2173,8 @@ def affine_mi_loss_grad(moving, target, theta, rng, bins=32, alpha=1.0, normaliz
     tail = (_lib.ptr(th), _lib.ptr(loss), _lib.ptr(dth), _lib.ptr(ws), ws_bytes, _lib.current_stream(dev))
     with torch.cuda.device(dev):
         if two:
-            mg = pair.grid(overlap, moving_mask)
+            rec = None if world is None else _world_record(world, B, dev)
+            mg = pair.grid(overlap, moving_mask, rec)
             rc = lib.trx_affine_mi_loss_grad_grids(ctypes.byref(vol), ctypes.byref(mg), ctypes.byref(cfg), *tail)
         else:
             rc = lib.trx_affine_mi_loss_grad(ctypes.byref(vol), ctypes.byref(cfg), *tail)
@@ -1900,19 +2203,37 @@ class AffineMISolver(_AffineParams):
     overlap / moving_mask (overlap_args): the overlap rule - a target voxel counts only while its sample lies inside the
     moving image (and inside moving_mask [B,1,*moving spatial], kept alive as `.moving_mask`); validity is re-decided in every pass from the
     current theta and is constant under the gradient; the moving range is the image's own (inside the mask), not widened to 0.  The loop is then
-    trx_affine_mi_run_grids whatever the shapes.  valid_fraction(theta): the share of counted voxels at a theta."""
+    trx_affine_mi_run_grids whatever the shapes.  valid_fraction(theta): the share of counted voxels at a theta.
+    moving_affine / target_affine (both or neither, not with voxel sizes; world_geometry describes them) and world_init (None, 'centers', 'moments'
+    or a world matrix; world_setup): world geometry, DESIGN.md section 4.17 - theta acts in world millimetres about a centre behind a fixed
+    initial transform, whatever the origins and axis directions of the two headers.  `.world` is the WorldGeometry used (T0 = .world.init, c =
+    .world.center), `.world_record` its records on the device (kept alive for the loop); world= takes a prepared WorldGeometry instead (the levels
+    of a pyramid share one).  .effective(theta) then goes through trx_affine_world_theta and .world_matrix(theta) is T."""
 
     def __init__(self, moving, target, mode="affine", mi=None, optimizer="sgd", lr=1e-5, init=None, capacity=1000, betas=(0.9, 0.999), eps=1e-8, mask=None,
-                 moving_voxel=None, target_voxel=None, overlap=None, moving_mask=None):
+                 moving_voxel=None, target_voxel=None, overlap=None, moving_mask=None, moving_affine=None, target_affine=None, world_init=None, world=None):
         if mask is not None:
             mask = _mask_u8(mask, target)
         self.overlap, moving_mask = overlap_args(overlap, moving_mask, moving)
+        headers = moving_affine is not None or target_affine is not None
+        if headers and (moving_affine is None or target_affine is None):
+            raise ValueError("moving_affine and target_affine go together: give both voxel-to-world matrices or neither")
+        if (headers or world is not None) and (moving_voxel is not None or target_voxel is not None):
+            raise ValueError("a voxel-to-world matrix carries the voxel sizes: give moving_affine / target_affine or moving_voxel / target_voxel, not both")
+        if world_init is not None and not headers:
+            raise ValueError("world_init needs moving_affine and target_affine")
+        if headers and world is not None:
+            raise ValueError("world is the prepared geometry of moving_affine / target_affine / world_init: give one or the other")
         self.lib = _lib.load()
-        two = self.overlap or moving_voxel is not None or target_voxel is not None or (
+        if headers:      # (its ValueErrors - and, for 'moments', two launches of trx_image_moments - before the solver allocates anything)
+            world = world_setup(moving, target, moving_affine, target_affine, world_init, mask, moving_mask)
+        self.world = world                 # WorldGeometry (host, fp64) or None
+        two = self.overlap or world is not None or moving_voxel is not None or target_voxel is not None or (
             isinstance(moving, torch.Tensor) and isinstance(target, torch.Tensor) and moving.shape[2:] != target.shape[2:])
         self.batch = _GridPair(moving, target, None, moving_voxel, target_voxel) if two else _mi_pair_batch(moving, target)
         self.moving_mask = None if moving_mask is None else moving_mask.to(self.batch.device)
-        self.grid = self.batch.grid(self.overlap, self.moving_mask) if two else None      # trx_moving_grid, or None: one lattice
+        self.world_record = None if world is None else _world_record(world, self.batch.B, self.batch.device)      # kept alive: the grid points to it
+        self.grid = self.batch.grid(self.overlap, self.moving_mask, self.world_record) if two else None      # trx_moving_grid, or None: one lattice
         b, nd, dev = self.batch.B, self.batch.nd, self.batch.device
         self.opt = opt_cfg(optimizer, lr, betas, eps)
         self._init_params(b, nd, dev, mode, init, capacity)
@@ -1963,12 +2284,18 @@ class AffineMISolver(_AffineParams):
         return self.batch.scale.to(self.batch.device)
 
     def effective(self, theta):
-        """theta * scale in fp32, as the kernels form it: the theta of F.affine_grid(., target.shape) + F.grid_sample(moving, .)."""
+        """theta * scale in fp32, as the kernels form it: the theta of F.affine_grid(., target.shape) + F.grid_sample(moving, .).  Under world
+        geometry: trx_affine_world_theta, the passes' own device function."""
+        if self.world is not None:
+            return affine_world_theta(theta.to(device=self.batch.device, dtype=torch.float32).reshape(-1, self.nd, self.nd + 1), self.world_record).to(theta.device)
         return theta.to(torch.float32) * self.scale.to(theta.device)
 
     def world_matrix(self, theta):
         """[B, nd+1, nd+1] fp64, homogeneous, rows and columns in theta's order (x, y(, z)): moving_mm = M target_mm for the two volumes with
-        their centres at the origin, M = [theta[:, :nd] | e_moving * theta[:, nd]].  None without voxel sizes."""
+        their centres at the origin, M = [theta[:, :nd] | e_moving * theta[:, nd]].  None without voxel sizes.  Under world geometry:
+        T = T0 Tr(c) Theta Tr(-c) between the two world frames (WorldGeometry.matrix), on theta's device."""
+        if self.world is not None:
+            return self.world.matrix(theta).to(theta.device)
         e_m = getattr(self.batch, "half_extent_moving", None)
         if e_m is None:
             return None

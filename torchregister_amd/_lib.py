@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libtrx.so")
 
 PSTRIDE = 12
+WORLD_STRIDE, WORLD_L, WORLD_R, WORLD_EXT = 32, 0, 12, 24   # trx_moving_grid.world: doubles per pair, offsets of L, R and the half extents
 OPT_SGD, OPT_ADAM = 0, 1
 PARAM_AFFINE, PARAM_RIGID = 0, 1
 # trx_volumes.flags (include/trx.h)
@@ -78,7 +79,8 @@ class MICfg(ctypes.Structure):
 
 class MovingGrid(ctypes.Structure):
     _fields_ = [("D", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("scale", ctypes.c_float * PSTRIDE),
-                ("overlap", ctypes.c_int), ("mask", ctypes.c_void_p)]      # zero / None: every target voxel counts (zero padding)
+                ("overlap", ctypes.c_int), ("mask", ctypes.c_void_p),      # zero / None: every target voxel counts (zero padding)
+                ("world", ctypes.c_void_p)]                                # None: the scale; else device [B][WORLD_STRIDE] fp64 records
 
 
 # name -> (restype, argtypes); must list every symbol include/trx.h declares (tests check this)
@@ -171,6 +173,9 @@ SIGNATURES = {
     "trx_affine_mi_run_grids": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), ctypes.POINTER(MICfg), ctypes.POINTER(OptCfg),
                                                ctypes.POINTER(AffineState), ctypes.c_int, _P, ctypes.c_size_t, _P]),
     "trx_affine_warp_grids": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), _P, ctypes.c_int, _P, _P]),
+    "trx_affine_world_theta": (ctypes.c_int, [ctypes.POINTER(MovingGrid), ctypes.c_int, ctypes.c_int, _P, _P, _P]),
+    "trx_image_moments_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "trx_image_moments": (ctypes.c_int, [_P, _P, _P] + [ctypes.c_int] * 5 + [_P, _P, ctypes.c_size_t, _P]),
     "trx_affine_flow_warp": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), _P, _P, ctypes.c_int, _P, _P]),
     "trx_affine_flow_warp_backward": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), _P, _P, ctypes.c_int, _P, _P, _P]),
     "trx_bspline_mi_run_grids": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), _P, ctypes.POINTER(MICfg), ctypes.POINTER(OptCfg),

@@ -22,13 +22,15 @@ TRX_HIDDEN int launch_loss_finalize(const trx_volumes *vol, const trx_loss_cfg *
 TRX_HIDDEN int launch_bwd_finalize(const trx_volumes *vol, const float *partials, int nblk, float *dtheta, hipStream_t s);
 
 // what the cross-lattice entry points (trx_affine_*_grids in affine_mi.hip, trx_affine_flow_* in affine_flow.hip) refuse on top of the others
-// (ndim: 2 or 3, already checked)
-static inline int ami_grid_check(int ndim, const trx_moving_grid *mg)
+// (ndim: 2 or 3, already checked).  world_ok: the entry point honours mg->world (the rigid / affine mutual-information pair); every other one refuses it,
+// and with it the scale is not read
+static inline int ami_grid_check(int ndim, const trx_moving_grid *mg, bool world_ok = false)
 {
     if (!mg) return TRX_ERR_ARG;
+    if (mg->world && !world_ok) return TRX_ERR_ARG;
     if (mg->D < 1 || mg->H < 1 || mg->W < 1 || (double)mg->D * mg->H * mg->W >= 2147483648.0) return TRX_ERR_ARG;
     if (ndim == 2 && mg->D != 1) return TRX_ERR_NDIM;
-    for (int k = 0; k < ndim * (ndim + 1); k++) {
+    for (int k = 0; k < ndim * (ndim + 1) && !mg->world; k++) {
         if (!std::isfinite(mg->scale[k])) return TRX_ERR_ARG;
         if (k % (ndim + 1) < ndim && !(mg->scale[k] > 0.f)) return TRX_ERR_ARG;      // the matrix part: a ratio of extents
     }

@@ -29,6 +29,10 @@
 // coordinate, tests it against [0, S - 1] on every axis and then against the moving-mask byte at rint(i), and skips the voxel in front of the sampler and of
 // the target load - the masked instances' `continue`, one step later.  N_valid comes from the counts as N_m does (launch_mi_table's from_counts); the
 // other instances, and the kernels that take the moving lattice without the rule (MovingLattice: the struct's first 60 bytes), keep their code.
+// World geometry (trx_moving_grid.world; two lattices): a fourth instance of each pass (WD, *_world_kernel, with or without OV) whose
+// prologue forms theta_eff = (L Theta R)[:ND] in fp64 from the pair's record (ami_theta_eff_world, trx_common.h) where the others form theta (.) scale - the
+// voxel loop is the same statement -, an update / finalise instance that applies the matrix chain rule (ami_world_chain) behind the unchanged reduction, and
+// trx_affine_world_theta, which runs the prologue's device function on its own.  The other instances keep their code (profiles/affine_mi_world_codegen.txt).
 #include "affine_finalize.h"   // reduce_partials, fin_load / fin_update (the epilogue of the affine step), launch_bwd_finalize (affine_host.h)
 #include "mi_dev.h"
 
@@ -107,12 +111,14 @@ __device__ __forceinline__ bool ami_sample_valid(const float *__restrict__ th, c
 
 // What a block samples pair b with: theta's row in place and vol's sizes, or (XL, two lattices: trx_moving_grid) theta_eff = theta (.) scale,
 // formed once per block into `te` (ami_theta_eff, trx_common.h), and the moving lattice's sizes.  Returns the row the voxel loop reads.
-template <int ND, bool XL>
+// WD (world geometry: trx_moving_grid.world): theta_eff = (L Theta R)[:ND] from the pair's record `w` instead (ami_theta_eff_world).
+template <int ND, bool XL, bool WD = false>
 __device__ __forceinline__ const float *ami_pose(const trx_volumes &vol, const MovingLattice *mg, const float *__restrict__ th, float (&te)[ND * (ND + 1)], int &D, int &H,
-                                                 int &W)
+                                                 int &W, const double *__restrict__ w = nullptr)
 {
     if constexpr (XL) {
-        ami_theta_eff<ND>(th, *mg, te);
+        if constexpr (WD) ami_theta_eff_world<ND>(th, w, te);
+        else ami_theta_eff<ND>(th, *mg, te);
         D = mg->D; H = mg->H; W = mg->W;
         return te;
     } else {
@@ -123,10 +129,11 @@ __device__ __forceinline__ const float *ami_pose(const trx_volumes &vol, const M
 
 // pass 1: warp and histogram.  mg: the moving lattice (XL) or unused
 // OV (two lattices only): the overlap rule - mmask: the moving masks [B][moving lattice] or nullptr
-template <int ND, bool MASKED, bool XL, bool OV = false>
+// WD (two lattices only): world geometry - world: the records [B][TRX_WORLD_STRIDE]; only the prologue differs
+template <int ND, bool MASKED, bool XL, bool OV = false, bool WD = false>
 __device__ __forceinline__ void ami_hist_body(const trx_volumes &vol, const MovingLattice *mg, const float *__restrict__ theta, unsigned N, int K, int T,
                                               const float *__restrict__ range, unsigned long long *__restrict__ counts, const unsigned char *__restrict__ mask,
-                                              const unsigned char *__restrict__ mmask = nullptr)
+                                              const unsigned char *__restrict__ mmask = nullptr, const double *__restrict__ world = nullptr)
 {
     extern __shared__ unsigned long long ami_lds[];           // [T][K][K]
     const int b = blockIdx.y, tid = threadIdx.x, KK = K * K;
@@ -134,7 +141,7 @@ __device__ __forceinline__ void ami_hist_body(const trx_volumes &vol, const Movi
     const MiScale m = mi_scale(range, b, K);
     float te[ND * (ND + 1)];
     int Dm, Hm, Wm;
-    const float *__restrict__ th = ami_pose<ND, XL>(vol, mg, theta + (size_t)b * TRX_PSTRIDE, te, Dm, Hm, Wm);
+    const float *__restrict__ th = ami_pose<ND, XL, WD>(vol, mg, theta + (size_t)b * TRX_PSTRIDE, te, Dm, Hm, Wm, WD ? world + (size_t)b * TRX_WORLD_STRIDE : nullptr);
     const float *__restrict__ mov = vol.moving + (size_t)b * vol.moving_stride;
     const float *__restrict__ tgt = vol.target + (size_t)b * vol.target_stride;
     const unsigned char *mk = MASKED ? mask + (size_t)b * N : nullptr;      // dense, whatever target_stride says
@@ -171,6 +178,14 @@ __global__ __launch_bounds__(TRX_BLOCK) void ami_hist_overlap_kernel(trx_volumes
 {
     ami_hist_body<ND, MASKED, true, true>(vol, &mg, theta, N, K, T, range, counts, mask, mmask);
 }
+// world geometry: with (OV) or without the overlap rule; mg's scale is not read
+template <int ND, bool MASKED, bool OV>
+__global__ __launch_bounds__(TRX_BLOCK) void ami_hist_world_kernel(trx_volumes vol, MovingLattice mg, const double *__restrict__ world, const float *__restrict__ theta,
+                                                                     unsigned N, int K, int T, const float *__restrict__ range, unsigned long long *__restrict__ counts,
+                                                                     const unsigned char *__restrict__ mask, const unsigned char *__restrict__ mmask)
+{
+    ami_hist_body<ND, MASKED, true, OV, true>(vol, &mg, theta, N, K, T, range, counts, mask, mmask, world);
+}
 
 // The block's 256 x NV per-thread sums -> out[NV]: fp64 from here on (a voxel's terms cancel to a gradient orders of magnitude below them, and the
 // fused pass may not be noisier than the warped-volume chain it replaces), a fixed shuffle tree per wave, the four waves in order, one rounding to
@@ -198,10 +213,11 @@ __device__ __forceinline__ void ami_block_sum_store(const float (&vals)[NV], flo
 
 // pass 2: gradient rows.  XL: the rows are sums of gw * (sampler derivative in moving voxels) * (xn, yn, zn, 1) - dL/dtheta_eff up to the S / 2 of the MOVING
 // sizes; the reduction behind the pass applies that and the scales.
-template <int ND, bool MASKED, bool XL, bool OV = false>
+template <int ND, bool MASKED, bool XL, bool OV = false, bool WD = false>
 __device__ __forceinline__ void ami_grad_body(const trx_volumes &vol, const MovingLattice *mg, const float *__restrict__ theta, unsigned N, int K,
                                               const float *__restrict__ range, const float *__restrict__ G, float *__restrict__ partials,
-                                              const unsigned char *__restrict__ mask, const unsigned char *__restrict__ mmask = nullptr)
+                                              const unsigned char *__restrict__ mask, const unsigned char *__restrict__ mmask = nullptr,
+                                              const double *__restrict__ world = nullptr)
 {
     constexpr int NT = ND * (ND + 1);
     extern __shared__ float ami_g[];                // [K][K]
@@ -211,7 +227,7 @@ __device__ __forceinline__ void ami_grad_body(const trx_volumes &vol, const Movi
     const MiScale m = mi_scale(range, b, K);
     float te[NT];
     int Dm, Hm, Wm;
-    const float *__restrict__ th = ami_pose<ND, XL>(vol, mg, theta + (size_t)b * TRX_PSTRIDE, te, Dm, Hm, Wm);
+    const float *__restrict__ th = ami_pose<ND, XL, WD>(vol, mg, theta + (size_t)b * TRX_PSTRIDE, te, Dm, Hm, Wm, WD ? world + (size_t)b * TRX_WORLD_STRIDE : nullptr);
     const float *__restrict__ mov = vol.moving + (size_t)b * vol.moving_stride;
     const float *__restrict__ tgt = vol.target + (size_t)b * vol.target_stride;
     float vals[NT];
@@ -258,14 +274,24 @@ __global__ __launch_bounds__(TRX_BLOCK) void ami_grad_overlap_kernel(trx_volumes
 {
     ami_grad_body<ND, MASKED, true, true>(vol, &mg, theta, N, K, range, G, partials, mask, mmask);
 }
+template <int ND, bool MASKED, bool OV>
+__global__ __launch_bounds__(TRX_BLOCK) void ami_grad_world_kernel(trx_volumes vol, MovingLattice mg, const double *__restrict__ world, const float *__restrict__ theta,
+                                                                     unsigned N, int K, const float *__restrict__ range, const float *__restrict__ G,
+                                                                     float *__restrict__ partials, const unsigned char *__restrict__ mask,
+                                                                     const unsigned char *__restrict__ mmask)
+{
+    ami_grad_body<ND, MASKED, true, OV, true>(vol, &mg, theta, N, K, range, G, partials, mask, mmask, world);
+}
 
 // The loop's epilogue, one block per pair: the pair's partial rows -> dL/dtheta, the loss of the table kernel, then the affine step's epilogue
 // (records, pose chain rule, optimiser, theta of the next forward); the pair's counts are zeroed for the next iteration's pass 1.
 // D, H, W: the sizes the sampler un-normalised with (the S / 2 per row of theta) - the moving lattice's in a cross-lattice run (XL), where the state's theta
 // is the unscaled one and lane i's dL/dtheta_i = dL/dtheta_eff_i * gscale[i], formed in fp64 in front of the epilogue (gscale == 1: the same bits).
+// world (XL, nullable; trx_moving_grid.world): the records - lane i's dL/dtheta_i is the matrix chain rule ami_world_chain instead, gscale is not read.
 template <int ND, bool XL>
 __device__ __forceinline__ void ami_update_body(const float *__restrict__ partials, int nblk, const float *__restrict__ loss, int D, int H, int W, const trx_opt_cfg &oc,
-                                                const trx_affine_state &st, unsigned long long *__restrict__ counts, int KK, const float *gscale)
+                                                const trx_affine_state &st, unsigned long long *__restrict__ counts, int KK, const float *gscale,
+                                                const double *__restrict__ world = nullptr)
 {
     constexpr int NT = ND * (ND + 1);
     constexpr int NPOSE = (ND == 3) ? 6 : 3;
@@ -296,7 +322,11 @@ __device__ __forceinline__ void ami_update_body(const float *__restrict__ partia
         for (int k = 0; k < NT; k++) gs = (k == ic) ? gscale[k] : gs;      // (selects: a lane-indexed read of a kernel argument would go through scratch)
         row_scale *= (double)gs;
     }
-    fin_update<ND>((double)lossf, row_scale * S[ic], bc1, rsbc2, r, b, i, oc, st, param, theta, am, av, st.step + b, true, nullptr, sh_dth, sh_pose);
+    double dth = row_scale * S[ic];
+    if constexpr (XL) {
+        if (world) dth = ami_world_chain<ND>(S, scale, world + (size_t)b * TRX_WORLD_STRIDE, ic);      // block-uniform
+    }
+    fin_update<ND>((double)lossf, dth, bc1, rsbc2, r, b, i, oc, st, param, theta, am, av, st.step + b, true, nullptr, sh_dth, sh_pose);
 }
 template <int ND>
 __global__ __launch_bounds__(TRX_FIN_THREADS) void ami_update_kernel(const float *__restrict__ partials, int nblk, const float *__restrict__ loss, int D, int H, int W,
@@ -309,6 +339,13 @@ __global__ __launch_bounds__(TRX_FIN_THREADS) void ami_update_grids_kernel(const
                                                                            trx_opt_cfg oc, trx_affine_state st, unsigned long long *__restrict__ counts, int KK)
 {
     ami_update_body<ND, true>(partials, nblk, loss, mg.D, mg.H, mg.W, oc, st, counts, KK, mg.scale);
+}
+template <int ND>
+__global__ __launch_bounds__(TRX_FIN_THREADS) void ami_update_world_kernel(const float *__restrict__ partials, int nblk, const float *__restrict__ loss, MovingLattice mg,
+                                                                           const double *__restrict__ world, trx_opt_cfg oc, trx_affine_state st,
+                                                                           unsigned long long *__restrict__ counts, int KK)
+{
+    ami_update_body<ND, true>(partials, nblk, loss, mg.D, mg.H, mg.W, oc, st, counts, KK, mg.scale, world);
 }
 
 // Behind one cross-lattice evaluation: launch_bwd_finalize's reduction (reduce_partials' fixed order) with the moving sizes in S / 2 and the scales on top,
@@ -326,6 +363,32 @@ __global__ __launch_bounds__(TRX_FIN_THREADS) void ami_grids_finalize_kernel(con
 #pragma unroll
     for (int k = 0; k < NT; k++) gs = (k == i) ? mg.scale[k] : gs;
     dtheta[(size_t)b * TRX_PSTRIDE + i] = (float)(scale[i / (ND + 1)] * (double)gs * S[i]);
+}
+
+// ... and under world geometry: the matrix chain rule (ami_world_chain) on the same reduction
+template <int ND>
+__global__ __launch_bounds__(TRX_FIN_THREADS) void ami_world_finalize_kernel(const float *__restrict__ partials, int nblk, MovingLattice mg, const double *__restrict__ world,
+                                                                             float *__restrict__ dtheta)
+{
+    constexpr int NT = ND * (ND + 1);
+    __shared__ double S[64];
+    const int b = blockIdx.x, i = threadIdx.x;
+    reduce_partials<NT>(partials + (size_t)b * nblk * NT, nblk, S);
+    if (i >= NT) return;
+    const double scale[3] = {0.5 * mg.W, 0.5 * mg.H, 0.5 * mg.D};
+    dtheta[(size_t)b * TRX_PSTRIDE + i] = (float)ami_world_chain<ND>(S, scale, world + (size_t)b * TRX_WORLD_STRIDE, i);
+}
+
+// trx_affine_world_theta: one thread per pair runs the passes' own statement
+template <int ND>
+__global__ void ami_world_theta_kernel(const double *__restrict__ world, const float *__restrict__ theta, int B, float *__restrict__ out)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    float raw[ND * (ND + 1)];
+    ami_world_theta<ND>(theta + (size_t)b * TRX_PSTRIDE, world + (size_t)b * TRX_WORLD_STRIDE, raw);
+#pragma unroll
+    for (int k = 0; k < TRX_PSTRIDE; k++) out[(size_t)b * TRX_PSTRIDE + k] = k < ND * (ND + 1) ? raw[k] : 0.f;
 }
 
 // The cross-lattice forward warp (trx_affine_warp_grids): affine_warp_kernel's walk over the TARGET lattice (vol's sizes and tables), every channel sampled in
@@ -362,10 +425,17 @@ static int ami_evaluate(const trx_volumes *vol, const trx_moving_grid *mg, const
     const dim3 grid(g.nchunk, (unsigned)vol->B), block(TRX_BLOCK);
     const unsigned char *mask = cfg->mask;               // read here on every evaluation, so on every iteration of the loop
     const bool ov = mg && mg->overlap;                   // the overlap rule: N_valid comes from the counts, as N_m does under a mask
+    const double *wd = mg ? mg->world : nullptr;         // world geometry: the *_world_kernel instances
     const size_t lds = (size_t)T * K * K * sizeof(unsigned long long);
     with_ndim(vol->ndim, [&](auto nd) {
         constexpr int ND = decltype(nd)::value;
-        if (ov) {
+        if (wd) {
+            const unsigned char *mm = ov ? mg->mask : nullptr;
+            if (ov && mask) hipLaunchKernelGGL((ami_hist_world_kernel<ND, true, true>), grid, block, lds, s, *vol, *mg, wd, theta, g.N, K, T, cfg->range, counts, mask, mm);
+            else if (ov) hipLaunchKernelGGL((ami_hist_world_kernel<ND, false, true>), grid, block, lds, s, *vol, *mg, wd, theta, g.N, K, T, cfg->range, counts, mask, mm);
+            else if (mask) hipLaunchKernelGGL((ami_hist_world_kernel<ND, true, false>), grid, block, lds, s, *vol, *mg, wd, theta, g.N, K, T, cfg->range, counts, mask, mm);
+            else hipLaunchKernelGGL((ami_hist_world_kernel<ND, false, false>), grid, block, lds, s, *vol, *mg, wd, theta, g.N, K, T, cfg->range, counts, mask, mm);
+        } else if (ov) {
             if (mask) hipLaunchKernelGGL((ami_hist_overlap_kernel<ND, true>), grid, block, lds, s, *vol, *mg, theta, g.N, K, T, cfg->range, counts, mask, mg->mask);
             else hipLaunchKernelGGL((ami_hist_overlap_kernel<ND, false>), grid, block, lds, s, *vol, *mg, theta, g.N, K, T, cfg->range, counts, mask, mg->mask);
         } else if (mg) {
@@ -380,7 +450,13 @@ static int ami_evaluate(const trx_volumes *vol, const trx_moving_grid *mg, const
     const size_t glds = (size_t)K * K * sizeof(float);
     with_ndim(vol->ndim, [&](auto nd) {
         constexpr int ND = decltype(nd)::value;
-        if (ov) {
+        if (wd) {
+            const unsigned char *mm = ov ? mg->mask : nullptr;
+            if (ov && mask) hipLaunchKernelGGL((ami_grad_world_kernel<ND, true, true>), grid, block, glds, s, *vol, *mg, wd, theta, g.N, K, cfg->range, (const float *)G, partials, mask, mm);
+            else if (ov) hipLaunchKernelGGL((ami_grad_world_kernel<ND, false, true>), grid, block, glds, s, *vol, *mg, wd, theta, g.N, K, cfg->range, (const float *)G, partials, mask, mm);
+            else if (mask) hipLaunchKernelGGL((ami_grad_world_kernel<ND, true, false>), grid, block, glds, s, *vol, *mg, wd, theta, g.N, K, cfg->range, (const float *)G, partials, mask, mm);
+            else hipLaunchKernelGGL((ami_grad_world_kernel<ND, false, false>), grid, block, glds, s, *vol, *mg, wd, theta, g.N, K, cfg->range, (const float *)G, partials, mask, mm);
+        } else if (ov) {
             if (mask) hipLaunchKernelGGL((ami_grad_overlap_kernel<ND, true>), grid, block, glds, s, *vol, *mg, theta, g.N, K, cfg->range, (const float *)G, partials, mask, mg->mask);
             else hipLaunchKernelGGL((ami_grad_overlap_kernel<ND, false>), grid, block, glds, s, *vol, *mg, theta, g.N, K, cfg->range, (const float *)G, partials, mask, mg->mask);
         } else if (mg) {
@@ -399,7 +475,7 @@ static int ami_check(const trx_volumes *vol, const trx_moving_grid *mg, bool gri
 {
     if (!vol || !cfg || !cfg->range || !workspace || !vol->moving || !vol->target || (grids && !mg)) return TRX_ERR_ARG;
     int rc = ami_geom(vol, cfg->bins, g);
-    if (rc == TRX_OK && grids) rc = ami_grid_check(vol->ndim, mg);
+    if (rc == TRX_OK && grids) rc = ami_grid_check(vol->ndim, mg, true);
     if (rc != TRX_OK) return rc;
     if (!std::isfinite(cfg->alpha)) return TRX_ERR_ARG;
     if (grids && mg->mask && !mg->overlap) return TRX_ERR_ARG;      // a moving mask is part of the overlap rule
@@ -422,7 +498,9 @@ static int ami_loss_grad(const trx_volumes *vol, const trx_moving_grid *mg, cons
     const float *partials = (const float *)((char *)workspace + g.o_part);
     if (!mg) return launch_bwd_finalize(vol, partials, (int)g.nchunk, dtheta, s);
     with_ndim(vol->ndim, [&](auto nd) {
-        hipLaunchKernelGGL((ami_grids_finalize_kernel<decltype(nd)::value>), dim3((unsigned)vol->B), dim3(TRX_FIN_THREADS), 0, s, partials, (int)g.nchunk, *mg, dtheta);
+        constexpr int ND = decltype(nd)::value;
+        if (mg->world) hipLaunchKernelGGL((ami_world_finalize_kernel<ND>), dim3((unsigned)vol->B), dim3(TRX_FIN_THREADS), 0, s, partials, (int)g.nchunk, *mg, mg->world, dtheta);
+        else hipLaunchKernelGGL((ami_grids_finalize_kernel<ND>), dim3((unsigned)vol->B), dim3(TRX_FIN_THREADS), 0, s, partials, (int)g.nchunk, *mg, dtheta);
     });
     TRX_CHECK_LAUNCH();
     return TRX_OK;
@@ -452,7 +530,8 @@ static int ami_run(const trx_volumes *vol, const trx_moving_grid *mg, const trx_
         if (r != TRX_OK) return r;
         with_ndim(vol->ndim, [&](auto nd) {
             constexpr int ND = decltype(nd)::value;
-            if (mg) hipLaunchKernelGGL((ami_update_grids_kernel<ND>), dim3((unsigned)vol->B), dim3(TRX_FIN_THREADS), 0, s, partials, (int)g.nchunk, (const float *)loss, *mg, *opt, *st, counts, KK);
+            if (mg && mg->world) hipLaunchKernelGGL((ami_update_world_kernel<ND>), dim3((unsigned)vol->B), dim3(TRX_FIN_THREADS), 0, s, partials, (int)g.nchunk, (const float *)loss, *mg, mg->world, *opt, *st, counts, KK);
+            else if (mg) hipLaunchKernelGGL((ami_update_grids_kernel<ND>), dim3((unsigned)vol->B), dim3(TRX_FIN_THREADS), 0, s, partials, (int)g.nchunk, (const float *)loss, *mg, *opt, *st, counts, KK);
             else hipLaunchKernelGGL((ami_update_kernel<ND>), dim3((unsigned)vol->B), dim3(TRX_FIN_THREADS), 0, s, partials, (int)g.nchunk, (const float *)loss, vol->D, vol->H, vol->W, *opt, *st, counts, KK);
         });
         TRX_CHECK_LAUNCH();
@@ -513,6 +592,17 @@ extern "C" int trx_affine_warp_grids(const trx_volumes *vol, const trx_moving_gr
     const dim3 grid((unsigned)nb, (unsigned)vol->B), block(TRX_BLOCK);
     with_ndim(vol->ndim, [&](auto nd) {
         hipLaunchKernelGGL((affine_warp_grids_kernel<decltype(nd)::value>), grid, block, 0, s, *vol, *mg, theta, channels, nmov, out);
+    });
+    TRX_CHECK_LAUNCH();
+    return TRX_OK;
+}
+
+extern "C" int trx_affine_world_theta(const trx_moving_grid *mg, int ndim, int B, const float *theta, float *theta_eff, void *stream)
+{
+    if (!mg || !mg->world || !theta || !theta_eff || B < 1 || B > 65535) return TRX_ERR_ARG;
+    if (ndim != 2 && ndim != 3) return TRX_ERR_NDIM;
+    with_ndim(ndim, [&](auto nd) {
+        hipLaunchKernelGGL((ami_world_theta_kernel<decltype(nd)::value>), dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, mg->world, theta, B, theta_eff);
     });
     TRX_CHECK_LAUNCH();
     return TRX_OK;

@@ -262,6 +262,73 @@ __device__ __forceinline__ void ami_theta_eff(const float *__restrict__ th, cons
         te[k] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(th[k] * mg.scale[k])));
 }
 
+// World geometry (trx_moving_grid.world): theta_eff = (L Theta R)[:ND] from the pair's record w (TRX_WORLD_STRIDE doubles: L | R | l)
+// where ami_theta_eff forms theta (.) scale.  fp64, one IEEE multiply and one IEEE add per term (the intrinsics: no contraction, so every instance - the two
+// passes, trx_affine_world_theta - and a host restatement give the same bits), each sum in ascending index order with the homogeneous term last, one rounding
+// to fp32.  Uniform inputs (theta's row and the record through scalar loads); raw: the fp32 values, for the caller to pin or to store.
+template <int ND>
+__device__ __forceinline__ void ami_world_theta(const float *__restrict__ th, const double *__restrict__ w, float (&raw)[ND * (ND + 1)])
+{
+    constexpr int NC = ND + 1;
+    const double *__restrict__ L = w + TRX_WORLD_L, *__restrict__ R = w + TRX_WORLD_R, *__restrict__ ext = w + TRX_WORLD_EXT;
+    double M[ND][NC];
+#pragma unroll
+    for (int r = 0; r < ND; r++) {
+#pragma unroll
+        for (int j = 0; j < NC; j++) {
+            double s = __dmul_rn((double)th[r * NC], R[j]);
+#pragma unroll
+            for (int c = 1; c < ND; c++) s = __dadd_rn(s, __dmul_rn((double)th[r * NC + c], R[c * NC + j]));
+            if (j == ND) s = __dadd_rn(s, __dmul_rn(ext[r], (double)th[r * NC + ND]));
+            M[r][j] = s;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < ND; i++) {
+#pragma unroll
+        for (int j = 0; j < NC; j++) {
+            double s = __dmul_rn(L[i * NC], M[0][j]);
+#pragma unroll
+            for (int r = 1; r < ND; r++) s = __dadd_rn(s, __dmul_rn(L[i * NC + r], M[r][j]));
+            if (j == ND) s = __dadd_rn(s, L[i * NC + ND]);
+            raw[i * NC + j] = (float)s;
+        }
+    }
+}
+// ... pinned to SGPRs for a voxel loop, as ami_theta_eff's row is
+template <int ND>
+__device__ __forceinline__ void ami_theta_eff_world(const float *__restrict__ th, const double *__restrict__ w, float (&te)[ND * (ND + 1)])
+{
+    float raw[ND * (ND + 1)];
+    ami_world_theta<ND>(th, w, raw);
+#pragma unroll
+    for (int k = 0; k < ND * (ND + 1); k++) te[k] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(raw[k])));
+}
+
+// The matrix chain rule behind it, entry k = r (ND + 1) + c of dL/dtheta (the unscaled theta) from S[i (ND + 1) + j] = the reduced partial rows (LDS) and
+// half[i] = S_m,i / 2 (x, y(, z) order):  g = half (.) S,  P[r][j] = sum_i L[i][r] g[i][j],  dtheta[r][c < ND] = sum_{j <= ND} P[r][j] R[c][j],
+// dtheta[r][ND] = l_r P[r][ND].  fp64, IEEE multiplies and adds in ascending index order, as above.
+template <int ND>
+__device__ __forceinline__ double ami_world_chain(const double *S, const double (&half)[3], const double *__restrict__ w, int k)
+{
+    constexpr int NC = ND + 1;
+    const double *__restrict__ L = w + TRX_WORLD_L, *__restrict__ R = w + TRX_WORLD_R, *__restrict__ ext = w + TRX_WORLD_EXT;
+    const int r = k / NC, c = k % NC;
+    double P[NC];
+#pragma unroll
+    for (int j = 0; j < NC; j++) {
+        double s = __dmul_rn(L[r], __dmul_rn(half[0], S[j]));
+#pragma unroll
+        for (int i = 1; i < ND; i++) s = __dadd_rn(s, __dmul_rn(L[i * NC + r], __dmul_rn(half[i], S[i * NC + j])));
+        P[j] = s;
+    }
+    if (c == ND) return __dmul_rn(ext[r], P[ND]);
+    double d = __dmul_rn(P[0], R[c * NC]);
+#pragma unroll
+    for (int j = 1; j < NC; j++) d = __dadd_rn(d, __dmul_rn(P[j], R[c * NC + j]));
+    return d;
+}
+
 // ------------------------------------------------------------------------------------------
 // Block reduction of NV per-thread floats -> out[NV] (written by the first NV threads).
 // Deterministic (fixed order).  Staged through LDS in chunks of CH values so the footprint

@@ -9,9 +9,9 @@ U-Net-generated flow, 'direct' = the flow field itself is the parameter), levels
 import torch
 from torch import cat
 
-from ._engine import _bending_weight, _mask_u8, _squarings, affine_warp, check_interpolation, grid_scale, overlap_args, resample
+from ._engine import _bending_weight, _mask_u8, _squarings, affine_warp, check_interpolation, grid_scale, overlap_args, resample, world_setup
 from .pyramid import level_theta, pyramid, pyramid_masks, pyramid_shapes, upsample_flow
-from .warpings import (GRIDS_SUPPORT, INITIAL_SUPPORT, MASK_SUPPORT, OVERLAP_SUPPORT, affine_register, device_loop_settings, flow_register, get_affine_warp, resolve_initial, rigid_register,
+from .warpings import (GRIDS_SUPPORT, INITIAL_SUPPORT, MASK_SUPPORT, OVERLAP_SUPPORT, WORLD_SUPPORT, affine_register, device_loop_settings, flow_register, get_affine_warp, resolve_initial, rigid_register,
                        two_lattices)
 
 
@@ -121,6 +121,8 @@ class Register():
         self.level_losses = None
         self.level_shapes = None
         self.world_matrix = None    # device_loop with voxel sizes: [B,nd+1,nd+1], the best theta as moving_mm = M target_mm (rows / columns x, y(, z))
+        self.world_init = None      # optim(moving_affine=, target_affine=): T0 [B,nd+1,nd+1] fp64, the fixed world transform in front of what was optimised
+        self.world_center = None    # ... and c [B,nd] fp64, the centre (world mm) theta acted about; world_matrix is then T0 Tr(c) Theta Tr(-c)
         self.target_shape = None    # the spatial shape of the lattice optim registered onto: what reg(x) returns
         self.initial = None         # optim(initial=...): the effective theta [B,nd,nd+1] the deformation is composed with
         self.valid_fraction = None  # optim(overlap=True / moving_mask=...): [B], N_valid / (target-mask voxels or N) at the returned transform
@@ -182,15 +184,30 @@ class Register():
             raise ValueError(OVERLAP_SUPPORT)
         return overlap_args(overlap, moving_mask, moving)
 
+    def _check_world(self, moving, target, moving_affine, target_affine, world_init, moving_voxel, target_voxel, mask, moving_mask):
+        '''moving_affine=... / target_affine=... / world_init=... of optim: ValueError unless the loop is the fused mutual-information loop of mode
+        'rigid' / 'affine' (device_loop=True) - GRIDS_SUPPORT's rule - and for every malformed header, before any device work (world_init='moments'
+        then runs trx_image_moments on each image).  Returns the WorldGeometry, made once from the full-resolution headers, or None.'''
+        if moving_affine is None and target_affine is None and world_init is None:
+            return None
+        if self.mode == 'flow' or not self.device_loop or moving.dim() != target.dim():
+            raise ValueError(WORLD_SUPPORT)
+        if moving_affine is None or target_affine is None:
+            raise ValueError("moving_affine and target_affine go together: give both voxel-to-world matrices or neither")
+        if moving_voxel is not None or target_voxel is not None:
+            raise ValueError("a voxel-to-world matrix carries the voxel sizes: give moving_affine / target_affine or moving_voxel / target_voxel, not both")
+        return world_setup(moving, target, moving_affine, target_affine, world_init, mask, moving_mask)
+
     def _set_grids(self, grids, target, info):
         '''After a rigid / affine optim: the warp behind __call__ (two lattices: onto the target lattice, forward only) and the new attributes.'''
         self.target_shape = tuple(target.shape[2:])
         self.world_matrix = info.get('world_matrix')
+        self.world_init, self.world_center = info.get('world_init'), info.get('world_center')
         size = self.target_shape
         self.warp = (lambda theta, x: affine_warp(theta, x, size=size)) if grids else get_affine_warp
 
     def optim(self, moving, target, lr=1E-5, max_epochs=1000, n=32, per=0.1, *, mask=None, moving_voxel=None, target_voxel=None, initial=None,
-              overlap=None, moving_mask=None):
+              overlap=None, moving_mask=None, moving_affine=None, target_affine=None, world_init=None):
         '''
         Optimisation loop: moving, target [1,1,x,y(,z)] float32 GPU tensors (a leading batch > 1 of
         independent pairs is an extension).  Sets self.theta (best theta [B,nd,nd+1], or the flow
@@ -231,18 +248,36 @@ class Register():
             Afterwards .valid_fraction [B] is N_valid / (target-mask voxels or N) at the returned transform (one extra evaluation; nothing is read
             back inside the loop) - there is no minimum-overlap guard: a pair that lost all overlap has loss 0, check the fraction.  With levels > 1
             the moving mask goes through pyramid_masks over the moving pyramid and every level fits its own ranges.
+        moving_affine, target_affine, world_init : (keyword-only extension) the images' voxel-to-world matrices, [nd+1,nd+1]
+            for every pair or [B,nd+1,nd+1]: columns in the tensor's axis order (nibabel's img.affine for get_fdata() put into [B,1,*shape]), rows
+            world x, y(, z) in mm.  Both or neither, not together with voxel sizes (they carry them).  The transform is optimised in world
+            millimetres about a centre c, behind a fixed world transform T0 chosen by world_init: None - trust the headers, T0 = I, c = the target's
+            geometric centre; 'centers' - T0 takes the target's geometric centre to the moving image's; 'moments' - T0 is the translation between the
+            intensity centres of mass (inside mask / moving_mask where given), c = the target's centre of mass; or a world matrix from anywhere
+            ([nd+1,nd+1] / [B,nd+1,nd+1], p_moving = T0 p_target).  Honoured where voxel sizes are: mode 'rigid' / 'affine' with device_loop=True;
+            ValueError anywhere else and for a malformed header, before any device work.  Works with mask=, overlap=, moving_mask= and levels=
+            (the geometry is made once from the full-resolution headers and shared by the levels).  Afterwards .theta / .final_theta are EFFECTIVE
+            thetas as with voxel sizes, .world_matrix [B,nd+1,nd+1] fp64 is T = T0 Tr(c) Theta Tr(-c) at the best theta (p_moving = T p_target),
+            .world_init and .world_center are T0 and c, .final_pose keeps its meaning; ffd.optim(moving, target, initial=reg) and
+            reg(x, interpolation=) work as before - they only ever see the effective theta.
         '''
         self.valid_fraction = None
         overlap, moving_mask = self._check_overlap(overlap, moving_mask, moving, initial)
+        headers = moving_affine is not None or target_affine is not None or world_init is not None
         if initial is not None:
+            if headers:
+                raise ValueError(WORLD_SUPPORT)
             initial, grids = self._check_initial(initial, moving, target, moving_voxel, target_voxel), False
+        elif headers and (self.mode == 'flow' or not self.device_loop):
+            raise ValueError(WORLD_SUPPORT)
         else:
-            grids = self._check_grids(moving, target, moving_voxel, target_voxel)
+            grids = self._check_grids(moving, target, moving_voxel, target_voxel) or headers
         self.initial = initial
         if mask is not None:
             mask = self._check_mask(mask, target)
+        world = self._check_world(moving, target, moving_affine, target_affine, world_init, moving_voxel, target_voxel, mask, moving_mask) if headers else None
         if self.levels > 1:
-            return self._optim_levels(moving, target, lr, max_epochs, n, per, mask, moving_voxel, target_voxel, initial, overlap, moving_mask)
+            return self._optim_levels(moving, target, lr, max_epochs, n, per, mask, moving_voxel, target_voxel, initial, overlap, moving_mask, world)
         okw = dict(overlap=True, moving_mask=moving_mask) if overlap else {}
         if self.mode == 'flow':
             flowreg = flow_register(target.shape[2:], **self._flow_kw(n, lr, max_epochs)).to(moving.device)
@@ -268,7 +303,9 @@ class Register():
             kw.update(weights=self.weight)
         if mask is not None:
             kw.update(mask=mask)
-        if grids:
+        if world is not None:
+            kw.update(world=world)
+        elif grids:
             kw.update(moving_voxel=moving_voxel, target_voxel=target_voxel)
         _, theta = fn(moving, target, **kw, **okw)
         self.valid_fraction = info.get('valid_fraction')
@@ -280,7 +317,7 @@ class Register():
         self._set_grids(grids, target, info)
 
     def _optim_levels(self, moving, target, lr, max_epochs, n, per, mask=None, moving_voxel=None, target_voxel=None, initial=None, overlap=False,
-                      moving_mask=None):
+                      moving_mask=None, world=None):
         '''Coarse-to-fine: the single-level machinery (flow_register / _affine_family) on each level of pyramid(moving) and
         pyramid(target), coarsest first; each level starts from the previous level's FINAL parameters (rigid: the pose, drawn by
         torch.rand for the coarsest level as a single-level run draws it; affine: theta; flow: upsample_flow of the flow).  Optimiser
@@ -289,7 +326,7 @@ class Register():
         voxel sizes - the half extents, and with them the scale, are the same at every level; the theta handed up is the unscaled one.
         initial (flow, B-spline mutual information): moving and target get their own pyramids (align_corners=True) and level k runs with
         level_theta(initial, ...), the theta between the two level lattices; the flow is handed up by upsample_flow as without it.'''
-        grids = two_lattices(moving, target, moving_voxel, target_voxel)      # (refused by optim unless the loop is the fused mutual-information one)
+        grids = world is not None or two_lattices(moving, target, moving_voxel, target_voxel)      # (refused by optim unless the loop is the fused mutual-information one)
         L = self.levels
         lrs, epochs = _per_level(lr, L, 'lr'), _per_level(max_epochs, L, 'max_epochs')
         shapes = pyramid_shapes(target.shape[2:], L)
@@ -332,7 +369,9 @@ class Register():
                     kw.update(weights=self.weight)
                 if masks[k] is not None:
                     kw.update(mask=masks[k])
-                if grids:
+                if world is not None:
+                    kw.update(world=world)      # A . N(S) does not depend on the level (align_corners=False keeps the field of view): one record for all
+                elif grids:
                     # align_corners=False keeps an image's field of view: a level's voxel is the full one times (full size / level size), per axis
                     lvl = lambda voxel, full, x: None if voxel is None else tuple(v * s / sl for v, s, sl in zip(voxel, full.shape[2:], x.shape[2:]))  # noqa: E731
                     kw.update(moving_voxel=lvl(moving_voxel, moving, movs[k]), target_voxel=lvl(target_voxel, target, tgts[k]))

@@ -289,6 +289,11 @@ GRIDS_SUPPORT = ("a moving image on a lattice of its own (another spatial shape)
                  "loops resample moving onto the target lattice first (reg(moving) of such a registration does it)")
 
 
+WORLD_SUPPORT = ("voxel-to-world matrices (moving_affine=, target_affine=) and world_init= follow the rule of voxel sizes: they are honoured by the fused "
+                 "mutual-information loop, mode='rigid' / 'affine' with device_loop=True and criterion=[MILoss()]; every other loop reaches world "
+                 "geometry through initial= or theta_from_world")
+
+
 INITIAL_SUPPORT = ("initial= (the rigid / affine result of the stage before, composed into the deformation so that the moving image is sampled once, on "
                    "its own lattice) is honoured by the B-spline mutual-information loop: mode='flow' with flow_model='bspline' and criterion=[MILoss()] "
                    "alone, without diffeomorphic=True and without voxel sizes (the effective theta carries them); `initial` is an effective theta "
@@ -336,9 +341,13 @@ def device_loop_settings(criterions, weights):
 
 
 def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, weights, grad_edges, honor_criterion,
-                   optimizer, init, info, device_loop=False, mask=None, moving_voxel=None, target_voxel=None, overlap=None, moving_mask=None):
+                   optimizer, init, info, device_loop=False, mask=None, moving_voxel=None, target_voxel=None, overlap=None, moving_mask=None,
+                   moving_affine=None, target_affine=None, world_init=None, world=None):
     mi = device_loop_settings(criterions, weights) if device_loop else None      # (before anything else: a refused list touches no tensor)
-    grids = two_lattices(moving, target, moving_voxel, target_voxel)
+    headers = moving_affine is not None or target_affine is not None or world_init is not None or world is not None
+    if headers and mi is None:
+        raise ValueError(WORLD_SUPPORT)
+    grids = headers or two_lattices(moving, target, moving_voxel, target_voxel)
     if overlap or moving_mask is not None:
         if mi is None:
             raise ValueError(OVERLAP_SUPPORT)
@@ -368,7 +377,8 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
         B = moving.shape[0]
         init_b = None if init is None else (init.reshape(-1, npose).expand(B, -1) if mode == "rigid" else init.reshape(-1, nd, nd + 1).expand(B, nd, nd + 1))
         solver = AffineMISolver(moving, target, mode=mode, mi=mi, optimizer=optimizer, lr=lr, init=init_b, capacity=max(1, epochs), mask=mask,
-                                moving_voxel=moving_voxel, target_voxel=target_voxel, overlap=overlap, moving_mask=moving_mask)
+                                moving_voxel=moving_voxel, target_voxel=target_voxel, overlap=overlap, moving_mask=moving_mask,
+                                moving_affine=moving_affine, target_affine=target_affine, world_init=world_init, world=world)
         solver.run(epochs)
         final_theta, best_theta = solver.current_theta, solver.best
         if epochs == 0:
@@ -377,7 +387,7 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
         if grids:
             # two lattices: the thetas handed out are the EFFECTIVE ones - grid_sample(moving, affine_grid(theta, target.shape)) is the warp - and
             # the warps land on the target lattice; the unscaled theta of the last forward goes along for a coarse-to-fine hand-over
-            final_unscaled, world = final_theta, solver.world_matrix(best_theta)
+            final_unscaled, world_mat = final_theta, solver.world_matrix(best_theta)
             final_theta, best_theta = solver.effective(final_theta), solver.effective(best_theta)
             warped = [_engine.affine_warp(t, moving, size=target.shape[2:]) for t in (final_theta, best_theta)]
         else:
@@ -385,7 +395,9 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
         theta = [final_theta, best_theta]
         res = dict(losses=solver.losses[:, :epochs], final_theta=final_theta, best_theta=best_theta, best_idx=solver.best_idx, solver=solver)
         if grids:
-            res.update(final_unscaled_theta=final_unscaled, world_matrix=world)
+            res.update(final_unscaled_theta=final_unscaled, world_matrix=world_mat)
+            if solver.world is not None:
+                res.update(world=solver.world, world_init=solver.world.init.clone(), world_center=solver.world.center.clone())
         if valid is not None:
             res.update(valid_fraction=valid)
         if mode == "rigid":
@@ -419,7 +431,8 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
 
 def affine_register(moving, target, lr=1E-5, epochs=1000, per=0.1, device="cpu", debug=True, criterions=None,
                     weights=[0.33, 0.33, 0.33], grad_edges=True, *, honor_criterion=False, optimizer="sgd", init=None, info=None,
-                    device_loop=False, mask=None, moving_voxel=None, target_voxel=None, overlap=None, moving_mask=None):
+                    device_loop=False, mask=None, moving_voxel=None, target_voxel=None, overlap=None, moving_mask=None, moving_affine=None,
+                    target_affine=None, world_init=None, world=None):
     """ref:warpings.py:30-113.  Returns ([final_warped, best_warped], [final_theta, best_theta]).
 
     NOTE: like the reference, grad_edges defaults to True here when called directly (and then
@@ -436,18 +449,26 @@ def affine_register(moving, target, lr=1E-5, epochs=1000, per=0.1, device="cpu",
     shapes or voxel sizes anywhere else: ValueError(GRIDS_SUPPORT) before any device work.
     overlap, moving_mask (keyword-only extension, with device_loop=True only; ValueError(OVERLAP_SUPPORT) otherwise; also on rigid_register): the
     overlap rule of _engine.AffineMISolver - only target voxels whose sample lies inside the moving image (and inside moving_mask, [B,1,*moving
-    spatial] or [B,*moving spatial], which implies the rule) count; info gains valid_fraction [B], the share counted at the best theta."""
+    spatial] or [B,*moving spatial], which implies the rule) count; info gains valid_fraction [B], the share counted at the best theta.
+    moving_affine, target_affine, world_init (keyword-only extension, with device_loop=True only; ValueError(WORLD_SUPPORT) otherwise; also on
+    rigid_register; not with voxel sizes): voxel-to-world matrices of the two images and the initial world transform (_engine.world_setup) - theta
+    acts in world millimetres about a centre, whatever the origins and axis directions; the returns are those of voxel sizes, info's world_matrix is
+    T = T0 Tr(c) Theta Tr(-c) at the best theta, and info gains world (the WorldGeometry), world_init (T0) and world_center (c).  world: a prepared
+    WorldGeometry instead of the three (the levels of a pyramid share one)."""
     return _affine_family("affine", moving, target, lr, epochs, device, debug, criterions, weights, grad_edges,
-                          honor_criterion, optimizer, init, info, device_loop, mask, moving_voxel, target_voxel, overlap, moving_mask)
+                          honor_criterion, optimizer, init, info, device_loop, mask, moving_voxel, target_voxel, overlap, moving_mask,
+                          moving_affine, target_affine, world_init, world)
 
 
 def rigid_register(moving, target, lr=1E-5, epochs=1000, per=0.1, device="cpu", debug=True, criterions=None,
                    weights=[0.33, 0.33, 0.33], grad_edges=True, *, honor_criterion=False, optimizer="sgd", init=None, info=None,
-                   device_loop=False, mask=None, moving_voxel=None, target_voxel=None, overlap=None, moving_mask=None):
+                   device_loop=False, mask=None, moving_voxel=None, target_voxel=None, overlap=None, moving_mask=None, moving_affine=None,
+                   target_affine=None, world_init=None, world=None):
     """ref:warpings.py:117-174.  `init` = initial pose (default torch.rand on the tensors' device).  moving_voxel / target_voxel: see
     affine_register - with them Theta(pose) is a rigid motion in millimetres whatever the voxel sizes."""
     return _affine_family("rigid", moving, target, lr, epochs, device, debug, criterions, weights, grad_edges,
-                          honor_criterion, optimizer, init, info, device_loop, mask, moving_voxel, target_voxel, overlap, moving_mask)
+                          honor_criterion, optimizer, init, info, device_loop, mask, moving_voxel, target_voxel, overlap, moving_mask,
+                          moving_affine, target_affine, world_init, world)
 
 
 class _FlowLossFn(torch.autograd.Function):
