@@ -62,7 +62,10 @@ extern "C" {
  *        B-spline resampling through the final transform) - new entry points only.
  *        Later addition under the same number: trx_moving_grid grows by one trailing field, `world` (voxel-to-world geometry for the rigid / affine
  *        mutual-information entry points; NULL = the scale, the launches and bits of before), trx_affine_world_theta, trx_image_moments and its
- *        workspace query - no entry point changed its signature. */
+ *        workspace query - no entry point changed its signature.
+ *        Later addition under the same number: trx_flow_jacobian, trx_flow_folding and its workspace query, trx_fold_cfg, trx_bspline_run_fold,
+ *        trx_bspline_mi_run_fold and their workspace queries (the Jacobian determinant map of a dense flow and a folding penalty on it, alone and
+ *        inside the free-form deformation loops) - new entry points and one new struct only. */
 #define TRX_VERSION 240
 #define TRX_PSTRIDE 12  /* floats per pair in theta / param / adam / best_theta arrays */
 
@@ -808,6 +811,49 @@ int trx_svf_exp_backward(const float *vel, const float *dflow, float *dvel, int 
 size_t trx_bspline_svf_workspace_bytes(int ndim, int B, int D, int H, int W, int sz, int sy, int sx, int squarings);
 int trx_bspline_svf_run(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt, const trx_bspline_state *st,
                         const int *spacing /*[host]*/, int squarings, int iters, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- Jacobian determinant of a dense flow and the folding penalty on it.  Extension: the reference has neither.  Later
+ * addition under TRX_VERSION 240: new entry points only.  CPU restatement: tests/jacobian_ref.py.
+ * flow [B][ndim][D][H][W] fp32 in voxel units, channel a along spatial axis a (trx_svf_exp's convention).  D_b u is the difference along axis b:
+ * (u(x + e_b) - u(x - e_b)) / 2 inside, u(1) - u(0) on the first voxel, u(S - 1) - u(S - 2) on the last, 0 on an axis of one voxel.
+ *   J(x)[a][b] = delta_ab + (D_b u_a)(x),   det(x) = det J(x)   - a map of the full size [B][D][H][W];
+ *   P_b = (1 / N) sum_x max(0, eps - det(x))^2,   N = D H W      - C^1, zero where nothing is near a fold;
+ *   dP/dJ(x) = -(2 / N) max(0, eps - det(x)) cof J(x), pulled back to the flow through the adjoint of D with the same one-sided faces.
+ * The determinant in voxel units is the determinant in millimetres (the two matrices are similar): nothing here depends on voxel sizes.  Behind an
+ * initial affine (trx_bspline_mi_run_grids) the whole transform's local volume change is this map times the constant determinant of the affine.
+ * No atomics, every sum in a fixed order (per-block fp64 partials, then a fixed-order second stage): the same bits on every call, and a pair's result does
+ * not depend on the batch around it; a non-finite flow in one pair leaves the others alone.  No host sync, no allocation.  Refusals before any HIP
+ * call: TRX_ERR_ARG (null pointer, a size < 1, B outside 1 .. 65535, >= 2^31 voxels, threshold or weight not finite, weight < 0), TRX_ERR_NDIM,
+ * TRX_ERR_WORKSPACE. */
+/* det [B][D][H][W] = the map; one launch, no workspace. */
+int trx_flow_jacobian(const float *flow, int ndim, int B, int D, int H, int W, float *det, void *stream);
+/* Bytes of workspace trx_flow_folding accepts: the map (4 B N bytes) and one double per 2048 voxels of a pair, each part rounded up to 256.
+ * 0 = arguments rejected. */
+size_t trx_flow_folding_workspace_bytes(int ndim, int B, int D, int H, int W);
+/* penalty[b] = P_b (unweighted) with eps = threshold; dflow (nullable, [B][ndim][D][H][W]) = (accumulate ? dflow : 0) + weight dP/dflow -
+ * trx_bspline_bending's convention.  The map is left at the start of the workspace.  dflow must not overlap flow. */
+int trx_flow_folding(const float *flow, int ndim, int B, int D, int H, int W, float threshold, float weight, float *penalty /*[B]*/,
+                     float *dflow /*nullable*/, int accumulate, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The folding penalty inside the free-form deformation loops.  It travels in a struct of its own: trx_bspline_state does not grow. */
+typedef struct {
+    float weight;    /* >= 0, finite; 0: the launches and the bits of the unpenalised entry point */
+    float threshold; /* eps, finite */
+} trx_fold_cfg;
+/* trx_bspline_run / trx_bspline_mi_run / trx_bspline_mi_run_grids (mg and theta both NULL: the one-lattice loop; both given: the composed one, its
+ * overlap rule included) with objective L = data term + lambda E_b + weight P_b, P_b on the TOTAL flow st->flow = base + expand(ctrl).  Per iteration,
+ * after the data term has written st->dflow and before reduce: the map and the partials (one launch), dflow += weight dP/dflow (one launch); losses[b][t]
+ * and the early stop see the total; `base` receives no gradient.  Everything else - state, refusals, capacity - is the unpenalised entry point's; fold
+ * NULL, a weight or threshold that is not finite, weight < 0: TRX_ERR_ARG.  Workspace: the *_fold_workspace_bytes query (the unpenalised entry point's bytes,
+ * rounded up to 256, + trx_flow_folding_workspace_bytes), whatever the weight; one byte short is TRX_ERR_WORKSPACE.  The diffeomorphic loop
+ * (trx_bspline_svf_run) has no such form.  Arbiter: the unpenalised loop's arbiter + weight * tests/jacobian_ref.py::penalty under torch autograd. */
+size_t trx_bspline_fold_workspace_bytes(int ndim, int B, int D, int H, int W, int sz, int sy, int sx);
+int trx_bspline_run_fold(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt, const trx_bspline_state *st,
+                         const int *spacing /*[host]*/, const trx_fold_cfg *fold /*[host]*/, int iters, void *workspace, size_t workspace_bytes, void *stream);
+size_t trx_bspline_mi_fold_workspace_bytes(int ndim, int B, int D, int H, int W, int sz, int sy, int sx, int bins, const trx_moving_grid *mg /*[host], nullable*/);
+int trx_bspline_mi_run_fold(const trx_volumes *vol, const trx_moving_grid *mg /*[host], nullable*/, const float *theta /*nullable*/, const trx_mi_cfg *cfg,
+                            const trx_opt_cfg *opt, const trx_bspline_state *st, const int *spacing /*[host]*/, const trx_fold_cfg *fold /*[host]*/, int iters,
+                            void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

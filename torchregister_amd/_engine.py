@@ -633,6 +633,105 @@ def svf_exp_backward(velocity, dflow, squarings=6, inverse=False):
     return _svf_backward(_svf_forward(velocity, squarings, bool(inverse))[1], dflow)
 
 
+def _folding_weight(value):
+    """A finite float >= 0, or ValueError."""
+    try:
+        w = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"folding_weight must be a finite number >= 0, got {value!r}") from None
+    if isinstance(value, bool) or not (w >= 0.0) or w == float("inf"):
+        raise ValueError(f"folding_weight must be a finite number >= 0, got {value!r}")
+    return w
+
+
+def _folding_threshold(value):
+    """A finite float, or ValueError."""
+    try:
+        t = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"folding_threshold must be a finite number, got {value!r}") from None
+    if isinstance(value, bool) or not math.isfinite(t):
+        raise ValueError(f"folding_threshold must be a finite number, got {value!r}")
+    return t
+
+
+def _dense_flow(flow, name="flow"):
+    """flow [B, nd, *spatial] on the GPU -> (lib, fp32 contiguous detached flow, nd, (nd, B, D, H, W))."""
+    if not isinstance(flow, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    nd = flow.dim() - 2
+    if nd not in (2, 3) or flow.shape[1] != nd or flow.shape[0] < 1:
+        raise ValueError(f"expected a dense flow [B,nd,*spatial], got {tuple(flow.shape)}")
+    _require_gpu(flow, name)
+    fl = flow.detach().contiguous()
+    return _lib.load(), fl, nd, (nd, fl.shape[0]) + _dhw(fl.shape[2:])
+
+
+def jacobian_determinant(flow):
+    """The Jacobian determinant map [B, 1, *spatial] of x -> x + flow(x) for a dense flow [B, nd, *spatial] (fp32, GPU; voxel units, channel a along
+    spatial axis a - svf_exp's and reg.theta's convention): det(delta_ab + D_b flow_a) with D the central difference, one-sided on the first and last
+    voxel of an axis and 0 on an axis of one voxel (trx_flow_jacobian).  det <= 0: the deformation folds there.  The determinant in voxels is the
+    determinant in millimetres; behind an initial affine the whole transform's local volume change is this map times the affine's constant determinant."""
+    lib, fl, nd, geom = _dense_flow(flow)
+    det = torch.empty((fl.shape[0], 1) + tuple(fl.shape[2:]), dtype=torch.float32, device=fl.device)
+    with torch.cuda.device(fl.device):
+        rc = lib.trx_flow_jacobian(_lib.ptr(fl), *geom, _lib.ptr(det), _lib.current_stream(fl.device))
+    _lib.check(rc, "trx_flow_jacobian")
+    return det
+
+
+def folding_penalty_grad(flow, threshold=0.3, weight=1.0, into=None, need_grad=True):
+    """trx_flow_folding: (P [B], dflow) for a dense flow [B, nd, *spatial] (fp32, GPU) - P_b = mean_x max(0, threshold - det(x))^2, unweighted, and
+    dflow = weight * dP/dflow, added onto `into` (fp32, contiguous, the flow's shape; written in place and returned) when it is given.
+    need_grad=False: (P, None)."""
+    lib, fl, nd, geom = _dense_flow(flow)
+    threshold, weight = _folding_threshold(threshold), _folding_weight(weight)
+    ws_bytes = lib.trx_flow_folding_workspace_bytes(*geom)
+    if ws_bytes == 0:
+        raise _lib.TrxError(f"trx_flow_folding_workspace_bytes rejected {tuple(fl.shape)}")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=fl.device)
+    penalty = torch.empty(fl.shape[0], dtype=torch.float32, device=fl.device)
+    dflow = None
+    if into is not None:
+        _require_gpu(into, "into")
+        if into.shape != fl.shape or into.dtype != torch.float32 or not into.is_contiguous():
+            raise ValueError(f"into must be a contiguous fp32 tensor of the flow's shape {tuple(fl.shape)}")
+        dflow = into
+    elif need_grad:
+        dflow = torch.empty_like(fl)
+    with torch.cuda.device(fl.device):
+        rc = lib.trx_flow_folding(_lib.ptr(fl), *geom, threshold, weight, _lib.ptr(penalty), _lib.ptr(dflow), 1 if into is not None else 0, _lib.ptr(ws),
+                                  ws_bytes, _lib.current_stream(fl.device))
+    _lib.check(rc, "trx_flow_folding")
+    return penalty, dflow
+
+
+class _FoldingPenaltyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flow, threshold):
+        penalty, dflow = folding_penalty_grad(flow, threshold)
+        ctx.save_for_backward(dflow)
+        ctx.dtype = flow.dtype
+        return penalty
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (dflow,) = ctx.saved_tensors
+        return (dflow * grad_out.reshape((-1,) + (1,) * (dflow.dim() - 1))).to(ctx.dtype), None
+
+
+def folding_penalty(flow, threshold=0.3):
+    """The folding penalty P [B] of a dense flow [B, nd, *spatial] (fp32, GPU): P_b = mean_x max(0, threshold - det(x))^2 with det =
+    jacobian_determinant(flow) - C^1, and zero where nothing is near a fold (trx_flow_folding).  Differentiable: a flow from any torch module
+    (a U-Net, a direct flow) gets the penalty's gradient through autograd, formed with the value in one call.
+    The default threshold 0.3 is a choice: the finite-difference determinant is sampled at voxel centres, and the margin above 0 is for what lies
+    between them - a field whose sampled determinant stays above 0.3 has room before the interpolated deformation folds."""
+    threshold = _folding_threshold(threshold)
+    if torch.is_grad_enabled() and flow.requires_grad:
+        return _FoldingPenaltyFn.apply(flow, threshold)
+    return folding_penalty_grad(flow, threshold, need_grad=False)[0]
+
+
 class BSplineSolver:
     """Cubic B-spline free-form deformation (extension): the control lattice `ctrl` [B, nd, *grid] is the parameter, the displacement field
     is base + expand(ctrl); the whole loop (expand, fused loss and dL/dflow, reduce, SGD / Adam, early stop) runs in trx_bspline_run.
@@ -648,11 +747,20 @@ class BSplineSolver:
     initial (with mi only, not with squarings; ValueError otherwise) = an affine theta [B,nd,nd+1] the deformation is composed with: the warp of
     the loop is affine_flow_warp(moving, initial, flow, initial_scale) and the loop runs in trx_bspline_mi_run_grids.  `moving` may then have a
     spatial shape of its own; ctrl, flow and mask stay on the target lattice, in target voxels; initial_scale [nd,nd+1] (grid_scale; None = ones:
-    `initial` is the effective theta).  theta is read on the device on every iteration (kept as `.initial`) and never written."""
+    `initial` is the effective theta).  theta is read on the device on every iteration (kept as `.initial`) and never written.
+    folding_weight = w > 0 adds w * folding_penalty(flow, folding_threshold) to each pair's loss, on the TOTAL flow base + expand(ctrl) of every
+    forward (the *_fold entry points: trx_bspline_run_fold, trx_bspline_mi_run_fold): `losses` and the early stop see the total, `base` gets no
+    gradient.  It works with every route above - fused criteria, mi, initial, mask, overlap, bending_weight - except squarings (ValueError: the
+    exponential of a velocity field does not fold).  0 (default): the entry points, launches and bits of before.  The threshold's default 0.3 is
+    a margin, see folding_penalty."""
 
     def __init__(self, moving, target, spacing, loss=None, optimizer="sgd", lr=1e-3, init=None, base=None, capacity=1000, stop_crit=None,
                  keep_last=False, betas=(0.9, 0.999), eps=1e-8, bending_weight=0.0, mi=None, squarings=None, mask=None, initial=None,
-                 initial_scale=None, overlap=None, moving_mask=None):
+                 initial_scale=None, overlap=None, moving_mask=None, folding_weight=0.0, folding_threshold=0.3):
+        self.folding_weight, self.folding_threshold = _folding_weight(folding_weight), _folding_threshold(folding_threshold)
+        if squarings is not None and self.folding_weight != 0:
+            raise ValueError("folding_weight is the folding penalty of the displacement models: with squarings the deformation is the exponential of a "
+                             "velocity field, which does not fold")
         if initial is not None and (mi is None or squarings is not None):
             raise ValueError("initial (an affine composed into the deformation) runs the mutual-information loop only: give it with `mi` and without `squarings`")
         self.overlap, moving_mask = overlap_args(overlap, moving_mask, moving)
@@ -716,6 +824,7 @@ class BSplineSolver:
         self.velocity_last = self.flow_last if squarings is not None else None
         self.vol = self.batch.vol()
         self.mi = None
+        self.fold = _lib.FoldCfg(self.folding_weight, self.folding_threshold) if self.folding_weight > 0 else None
         if squarings is not None:
             self.ws_bytes = self.lib.trx_bspline_svf_workspace_bytes(nd, b, *_dhw(self.batch.spatial), *self.sp3, squarings)
             if self.ws_bytes == 0:
@@ -723,10 +832,15 @@ class BSplineSolver:
             self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
         elif mi is not None:
             self.mi, self.mi_range, self.mask = _mi_cfg(mi, self.batch.target, self.batch.moving, mask, self.overlap, self.moving_mask)
-            self.ws_bytes = self.lib.trx_bspline_mi_grids_workspace_bytes(nd, b, *_dhw(self.batch.spatial), *self.sp3, self.mi.bins,
-                                                                          None if self.moving_grid is None else ctypes.byref(self.moving_grid))
+            query = self.lib.trx_bspline_mi_grids_workspace_bytes if self.fold is None else self.lib.trx_bspline_mi_fold_workspace_bytes
+            self.ws_bytes = query(nd, b, *_dhw(self.batch.spatial), *self.sp3, self.mi.bins, None if self.moving_grid is None else ctypes.byref(self.moving_grid))
             if self.ws_bytes == 0:
                 raise _lib.TrxError(f"trx_bspline_mi_grids_workspace_bytes rejected {b} x {tuple(self.batch.spatial)} with spacing {self.spacing}")
+            self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+        elif self.fold is not None:
+            self.ws_bytes = self.lib.trx_bspline_fold_workspace_bytes(nd, b, *_dhw(self.batch.spatial), *self.sp3)
+            if self.ws_bytes == 0:
+                raise _lib.TrxError(f"trx_bspline_fold_workspace_bytes rejected {b} x {tuple(self.batch.spatial)} with spacing {self.spacing}")
             self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
         else:
             self.workspace, self.ws_bytes = _bspline_workspace(self.lib, nd, b, self.batch.spatial, tuple(self.sp3), dev)
@@ -777,8 +891,25 @@ class BSplineSolver:
             raise ValueError("inverse_flow() needs the diffeomorphic model: create the solver with squarings=K")
         return svf_exp(self.velocity, self.squarings, inverse=True)
 
+    def _run_fold(self, iters):
+        """The *_fold entry point of this solver's route (folding_weight > 0)."""
+        stream = _lib.current_stream(self.batch.device)
+        if self.mi is not None:
+            mg, theta = (None, None) if self.initial is None else (ctypes.byref(self.moving_grid), _lib.ptr(self.initial))
+            rc = self.lib.trx_bspline_mi_run_fold(ctypes.byref(self.vol), mg, theta, ctypes.byref(self.mi), ctypes.byref(self.opt), ctypes.byref(self.state),
+                                                  self.sp3, ctypes.byref(self.fold), iters, _lib.ptr(self.workspace), self.ws_bytes, stream)
+            return rc, "trx_bspline_mi_run_fold"
+        rc = self.lib.trx_bspline_run_fold(ctypes.byref(self.vol), ctypes.byref(self.loss_c), ctypes.byref(self.opt), ctypes.byref(self.state), self.sp3,
+                                           ctypes.byref(self.fold), iters, _lib.ptr(self.workspace), self.ws_bytes, stream)
+        return rc, "trx_bspline_run_fold"
+
     def run(self, iters):
         iters = _reserve(self, iters)
+        if self.fold is not None:
+            with torch.cuda.device(self.batch.device):
+                rc, what = self._run_fold(iters)
+            _lib.check(rc, what)
+            return self._expand()
         with torch.cuda.device(self.batch.device):
             if self.squarings is not None:
                 rc = self.lib.trx_bspline_svf_run(ctypes.byref(self.vol), ctypes.byref(self.loss_c), ctypes.byref(self.opt), ctypes.byref(self.state),

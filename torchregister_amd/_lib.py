@@ -72,6 +72,10 @@ class BSplineState(ctypes.Structure):
                 ("bending_weight", ctypes.c_float)]
 
 
+class FoldCfg(ctypes.Structure):
+    _fields_ = [("weight", ctypes.c_float), ("threshold", ctypes.c_float)]
+
+
 class MICfg(ctypes.Structure):
     _fields_ = [("bins", ctypes.c_int), ("alpha", ctypes.c_float), ("normalized", ctypes.c_int), ("range", ctypes.c_void_p),
                 ("mask", ctypes.c_void_p)]
@@ -191,6 +195,15 @@ SIGNATURES = {
     "trx_bspline_svf_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 9),
     "trx_bspline_svf_run": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(LossCfg), ctypes.POINTER(OptCfg), ctypes.POINTER(BSplineState), c_int_p,
                                            ctypes.c_int, ctypes.c_int, _P, ctypes.c_size_t, _P]),
+    "trx_flow_jacobian": (ctypes.c_int, [_P] + [ctypes.c_int] * 5 + [_P, _P]),
+    "trx_flow_folding_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "trx_flow_folding": (ctypes.c_int, [_P] + [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_float, _P, _P, ctypes.c_int, _P, ctypes.c_size_t, _P]),
+    "trx_bspline_fold_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 8),
+    "trx_bspline_run_fold": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(LossCfg), ctypes.POINTER(OptCfg), ctypes.POINTER(BSplineState), c_int_p,
+                                            ctypes.POINTER(FoldCfg), ctypes.c_int, _P, ctypes.c_size_t, _P]),
+    "trx_bspline_mi_fold_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 9 + [ctypes.POINTER(MovingGrid)]),
+    "trx_bspline_mi_run_fold": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), _P, ctypes.POINTER(MICfg), ctypes.POINTER(OptCfg),
+                                               ctypes.POINTER(BSplineState), c_int_p, ctypes.POINTER(FoldCfg), ctypes.c_int, _P, ctypes.c_size_t, _P]),
 }
 
 _lib = None

@@ -2,8 +2,9 @@
 // lattice and a dense flow (trx_bspline_expand), its exact adjoint (trx_bspline_reduce) and a device-side optimisation loop over them
 // (trx_bspline_run), and the bending energy of the lattice with its gradient (trx_bspline_bending; in the loop: trx_bspline_state.bending_weight).
 // The same loop with other data terms: mutual information (trx_bspline_mi_run, csrc/mi.hip) and the diffeomorphic form, in which the expanded
-// lattice is a stationary velocity field (trx_bspline_svf_run, csrc/svf.hip).
-// CPU restatements: tests/bspline_ref.py, tests/bspline_bending_ref.py.
+// lattice is a stationary velocity field (trx_bspline_svf_run, csrc/svf.hip).  The displacement loops with a folding penalty on the Jacobian determinant
+// of the total flow: trx_bspline_run_fold, trx_bspline_mi_run_fold (the penalty's kernels: csrc/jacobian.hip).
+// CPU restatements: tests/bspline_ref.py, tests/bspline_bending_ref.py, tests/jacobian_ref.py.
 //
 // Definition (include/trx.h): an axis of S voxels with spacing d has G = (S - 1) / d + 4 control points, point i at voxel (i - 1) d; at
 // voxel x, i0 = x / d, t = (x % d) / d and the four weights B0..B3(t) of the uniform cubic B-spline act on points i0 .. i0 + 3 (always
@@ -22,6 +23,7 @@
 // Cache hints: `base` and `dflow` are read once per call and carry the non-temporal hint; the flow written by expand is
 // read again at once by the loss-and-gradient passes behind it, so its stores carry none.
 #include "affine_host.h"   // ami_grid_check (trx_bspline_mi_run_grids); includes trx_common.h
+#include "jacobian.h"      // the folding penalty of the *_fold entry points (csrc/jacobian.hip)
 
 #include <algorithm>
 #include <cmath>
@@ -523,6 +525,28 @@ __global__ __launch_bounds__(64) void bspline_decide_bending_kernel(const float 
     if (threadIdx.x == 0) bspline_decide_pair<true>(b, lambda * (float)e, terms, tstride, oc, losses, losses_capacity, step, stop_crit, stopped, coef);
 }
 
+// bspline_decide_bending_kernel with the folding penalty (the *_fold entry points, weight > 0): one wave per pair sums the bending partials (where
+// lambda > 0) and the folding partials, lane 0 decides on terms[b][0] + (lambda E_b + weight P_b)
+__global__ __launch_bounds__(64) void bspline_decide_fold_kernel(const float *__restrict__ terms, int tstride, const float *__restrict__ partials, int per_pair,
+                                                                   float lambda, const double *__restrict__ fold_partials, int nchunk, unsigned nvox,
+                                                                   float fold_weight, trx_opt_cfg oc, float *__restrict__ losses, int losses_capacity,
+                                                                   int *__restrict__ step, float stop_crit, int *__restrict__ stopped,
+                                                                   BsCoef *__restrict__ coef)
+{
+    const int b = blockIdx.x;
+    const double e = partials ? bspline_sum_partials(partials + (size_t)b * per_pair, per_pair) : 0.0;
+    const float p = fold_penalty_from_partials(fold_partials + (size_t)b * nchunk, nchunk, nvox);
+    if (threadIdx.x == 0)
+        bspline_decide_pair<true>(b, fmaf(fold_weight, p, lambda * (float)e), terms, tstride, oc, losses, losses_capacity, step, stop_crit, stopped, coef);
+}
+
+// The folding penalty of a *_fold run: its geometry, its settings and its workspace (behind the unpenalised entry point's)
+struct FoldRun {
+    FoldGeom g;
+    float weight, threshold;
+    void *ws;
+};
+
 struct BsGeom {
     int ndim, B, S[3], d[3], G[3];   // axes z, y, x (2-D: S[0] = G[0] = d[0] = 1, no z pass)
     size_t t1, t2;                   // floats per volume (pair and channel) of [D][Gy][Gx] and [D][H][Gx]
@@ -744,7 +768,7 @@ static int bspline_run_checks(const trx_volumes *vol, const trx_opt_cfg *opt, co
 // The loop both data terms share.  data_term(): the launches that turn st->flow into the pairs' data terms (terms[b * tstride]) and st->dflow.
 template <typename DataTerm>
 static int bspline_loop(const BsGeom &g, const trx_volumes *vol, const trx_opt_cfg *opt, const trx_bspline_state *st, int iters, const float *terms,
-                        int tstride, void *workspace, hipStream_t s, DataTerm data_term)
+                        int tstride, void *workspace, hipStream_t s, DataTerm data_term, const FoldRun *fold = nullptr)
 {
     int rc;
     char *ws = (char *)workspace;
@@ -759,8 +783,18 @@ static int bspline_loop(const BsGeom &g, const trx_volumes *vol, const trx_opt_c
     for (int i = 0; i < iters; i++) {
         if ((rc = bspline_expand_impl(g, st->ctrl, st->base, st->flow, workspace, s)) != TRX_OK) return rc;
         if ((rc = data_term()) != TRX_OK) return rc;
+        if (fold) {   // on the TOTAL flow base + expand(ctrl): dflow += weight dP/dflow; base receives nothing, as ever
+            if ((rc = fold_forward_impl(fold->g, st->flow, fold->threshold, fold->ws, s)) != TRX_OK) return rc;
+            if ((rc = fold_backward_impl(fold->g, st->flow, fold->threshold, fold->weight, st->dflow, 1, fold->ws, s)) != TRX_OK) return rc;
+        }
         if ((rc = bspline_reduce_impl(g, st->dflow, dctrl, workspace, s)) != TRX_OK) return rc;
-        if (bend) {
+        if (fold) {
+            if (bend && (rc = bspline_bending_impl(g, st->ctrl, dctrl, lambda, 1, workspace, s)) != TRX_OK) return rc;
+            hipLaunchKernelGGL(bspline_decide_fold_kernel, dim3((unsigned)vol->B), dim3(64), 0, s, terms, tstride,
+                               bend ? (const float *)(ws + g.part_offset) : (const float *)nullptr, (int)(g.ndim * g.bend_ntile), lambda,
+                               (const double *)((const char *)fold->ws + fold->g.part_offset), (int)fold->g.nchunk, fold->g.nvox, fold->weight, *opt, st->losses,
+                               st->losses_capacity, st->step, st->stop_crit, st->stopped, coef);
+        } else if (bend) {
             if ((rc = bspline_bending_impl(g, st->ctrl, dctrl, lambda, 1, workspace, s)) != TRX_OK) return rc;
             hipLaunchKernelGGL(bspline_decide_bending_kernel, dim3((unsigned)vol->B), dim3(64), 0, s, terms, tstride, (const float *)(ws + g.part_offset),
                                (int)(g.ndim * g.bend_ntile), lambda, *opt, st->losses, st->losses_capacity, st->step, st->stop_crit, st->stopped, coef);
@@ -790,6 +824,51 @@ extern "C" int trx_bspline_run(const trx_volumes *vol, const trx_loss_cfg *loss,
     return bspline_loop(g, vol, opt, st, iters, terms, 4, workspace, (hipStream_t)stream, [&]() {
         return trx_flow_loss_grad(vol, loss, st->flow, terms, st->dflow, ws + g.flow_offset, g.flow_bytes, stream);
     });
+}
+
+// The *_fold entry points: the penalty's settings (refused before any HIP call) and its workspace, which starts at the next 256-byte boundary behind
+// the unpenalised entry point's `base_bytes`.  weight == 0: no FoldRun, the loop is the unpenalised one launch for launch; the workspace size is still
+// the *_fold query's, so a caller sizes it once whatever the weight.
+static int fold_cfg_check(const trx_fold_cfg *fold)
+{
+    if (!fold || !std::isfinite(fold->weight) || !std::isfinite(fold->threshold) || fold->weight < 0.f) return TRX_ERR_ARG;
+    return TRX_OK;
+}
+
+static size_t fold_ws_offset(size_t base_bytes) { return (base_bytes + 255) & ~(size_t)255; }
+
+static int fold_run_setup(const BsGeom &g, const trx_fold_cfg *fold, void *workspace, size_t base_bytes, size_t workspace_bytes, FoldRun *fr)
+{
+    const int rc = fold_geom(g.ndim, g.B, g.S[0], g.S[1], g.S[2], &fr->g);
+    if (rc != TRX_OK) return rc;
+    if (workspace_bytes < fold_ws_offset(base_bytes) + fr->g.ws_bytes) return TRX_ERR_WORKSPACE;
+    fr->weight = fold->weight; fr->threshold = fold->threshold;
+    fr->ws = (char *)workspace + fold_ws_offset(base_bytes);
+    return TRX_OK;
+}
+
+extern "C" size_t trx_bspline_fold_workspace_bytes(int ndim, int B, int D, int H, int W, int sz, int sy, int sx)
+{
+    const size_t base = trx_bspline_workspace_bytes(ndim, B, D, H, W, sz, sy, sx), fold = trx_flow_folding_workspace_bytes(ndim, B, D, H, W);
+    return base && fold ? fold_ws_offset(base) + fold : 0;
+}
+
+extern "C" int trx_bspline_run_fold(const trx_volumes *vol, const trx_loss_cfg *loss, const trx_opt_cfg *opt, const trx_bspline_state *st, const int *spacing,
+                                    const trx_fold_cfg *fold, int iters, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!loss) return TRX_ERR_ARG;
+    BsGeom g;
+    int rc = bspline_run_checks(vol, opt, st, spacing, iters, workspace, &g);
+    if (rc == TRX_OK) rc = fold_cfg_check(fold);
+    if (rc != TRX_OK) return rc;
+    FoldRun fr;
+    if ((rc = fold_run_setup(g, fold, workspace, g.ws_bytes, workspace_bytes, &fr)) != TRX_OK) return rc;
+    if (st->losses && iters > st->losses_capacity) return TRX_ERR_CAPACITY;
+    char *ws = (char *)workspace;
+    float *terms = (float *)(ws + g.terms_offset);
+    return bspline_loop(g, vol, opt, st, iters, terms, 4, workspace, (hipStream_t)stream, [&]() {
+        return trx_flow_loss_grad(vol, loss, st->flow, terms, st->dflow, ws + g.flow_offset, g.flow_bytes, stream);
+    }, fr.weight > 0.f ? &fr : nullptr);
 }
 
 // Free-form deformation + mutual information (csrc/mi.hip): behind the loop's workspace lie the warped volumes, dL/dwarped and trx_mi_loss_grad's
@@ -833,7 +912,8 @@ extern "C" size_t trx_bspline_mi_grids_workspace_bytes(int ndim, int B, int D, i
 // `theta`, the moving image on a lattice of its own (csrc/affine_flow.hip): the same checks, workspace and launches with the composed
 // warp and its backward where trx_flow_warp / trx_flow_warp_backward stand.  theta is read on the device on every iteration and never written.
 static int bspline_mi_run_impl(const trx_volumes *vol, const trx_moving_grid *mg, const float *theta, const trx_mi_cfg *cfg, const trx_opt_cfg *opt,
-                               const trx_bspline_state *st, const int *spacing, int iters, void *workspace, size_t workspace_bytes, void *stream)
+                               const trx_bspline_state *st, const int *spacing, int iters, void *workspace, size_t workspace_bytes, void *stream,
+                               const trx_fold_cfg *fold = nullptr, bool with_fold = false)
 {
     if (!cfg || !cfg->range) return TRX_ERR_ARG;
     BsGeom g;
@@ -848,6 +928,13 @@ static int bspline_mi_run_impl(const trx_volumes *vol, const trx_moving_grid *mg
     if (mg && mg->mask && !mg->overlap) return TRX_ERR_ARG;      // a moving mask is part of the overlap rule
     const bool ov = mg && mg->overlap;
     if (workspace_bytes < l.ws_bytes + (ov ? bspline_mi_valid_bytes(g) : 0)) return TRX_ERR_WORKSPACE;
+    FoldRun fr;
+    const FoldRun *frp = nullptr;
+    if (with_fold) {   // trx_bspline_mi_run_fold: the penalty's workspace lies behind everything above
+        if ((rc = fold_cfg_check(fold)) != TRX_OK) return rc;
+        if ((rc = fold_run_setup(g, fold, workspace, l.ws_bytes + (ov ? bspline_mi_valid_bytes(g) : 0), workspace_bytes, &fr)) != TRX_OK) return rc;
+        if (fr.weight > 0.f) frp = &fr;
+    }
     if (st->losses && iters > st->losses_capacity) return TRX_ERR_CAPACITY;
     char *ws = (char *)workspace;
     float *mloss = (float *)(ws + g.terms_offset), *warped = (float *)(ws + l.o_warped), *go = (float *)(ws + l.o_go);
@@ -862,7 +949,7 @@ static int bspline_mi_run_impl(const trx_volumes *vol, const trx_moving_grid *mg
             r = trx_mi_loss_grad(vol->target, warped, vol->ndim, vol->B, vol->D, vol->H, vol->W, &vcfg, mloss, go, ws + l.o_mi, l.mi_bytes, stream);
             if (r != TRX_OK) return r;
             return trx_affine_flow_warp_backward(vol, mg, theta, st->flow, 1, go, st->dflow, stream);
-        });
+        }, frp);
     }
     return bspline_loop(g, vol, opt, st, iters, mloss, 1, workspace, (hipStream_t)stream, [&]() {
         int r = mg ? trx_affine_flow_warp(vol, mg, theta, st->flow, 1, warped, stream) : trx_flow_warp(vol, st->flow, 1, warped, stream);
@@ -870,7 +957,7 @@ static int bspline_mi_run_impl(const trx_volumes *vol, const trx_moving_grid *mg
         r = trx_mi_loss_grad(vol->target, warped, vol->ndim, vol->B, vol->D, vol->H, vol->W, cfg, mloss, go, ws + l.o_mi, l.mi_bytes, stream);
         if (r != TRX_OK) return r;
         return mg ? trx_affine_flow_warp_backward(vol, mg, theta, st->flow, 1, go, st->dflow, stream) : trx_flow_warp_backward(vol, st->flow, 1, go, st->dflow, stream);
-    });
+    }, frp);
 }
 
 extern "C" int trx_bspline_mi_run(const trx_volumes *vol, const trx_mi_cfg *cfg, const trx_opt_cfg *opt, const trx_bspline_state *st, const int *spacing,
@@ -884,6 +971,21 @@ extern "C" int trx_bspline_mi_run_grids(const trx_volumes *vol, const trx_moving
 {
     if (!mg || !theta) return TRX_ERR_ARG;      // (with the impl's first refusal: one return code, as before)
     return bspline_mi_run_impl(vol, mg, theta, cfg, opt, st, spacing, iters, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t trx_bspline_mi_fold_workspace_bytes(int ndim, int B, int D, int H, int W, int sz, int sy, int sx, int bins, const trx_moving_grid *mg)
+{
+    const size_t base = trx_bspline_mi_grids_workspace_bytes(ndim, B, D, H, W, sz, sy, sx, bins, mg), fold = trx_flow_folding_workspace_bytes(ndim, B, D, H, W);
+    return base && fold ? fold_ws_offset(base) + fold : 0;
+}
+
+// trx_bspline_mi_run (mg and theta NULL) and trx_bspline_mi_run_grids (both given), the overlap rule included, with the folding penalty
+extern "C" int trx_bspline_mi_run_fold(const trx_volumes *vol, const trx_moving_grid *mg, const float *theta, const trx_mi_cfg *cfg, const trx_opt_cfg *opt,
+                                       const trx_bspline_state *st, const int *spacing, const trx_fold_cfg *fold, int iters, void *workspace,
+                                       size_t workspace_bytes, void *stream)
+{
+    if ((mg == nullptr) != (theta == nullptr)) return TRX_ERR_ARG;
+    return bspline_mi_run_impl(vol, mg, theta, cfg, opt, st, spacing, iters, workspace, workspace_bytes, stream, fold, true);
 }
 
 // Diffeomorphic free-form deformation (csrc/svf.hip): the expanded lattice is a stationary velocity field.  Behind the loop's workspace lie

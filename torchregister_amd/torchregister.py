@@ -9,7 +9,7 @@ U-Net-generated flow, 'direct' = the flow field itself is the parameter), levels
 import torch
 from torch import cat
 
-from ._engine import _bending_weight, _mask_u8, _squarings, affine_warp, check_interpolation, grid_scale, overlap_args, resample, world_setup
+from ._engine import _bending_weight, _folding_threshold, _folding_weight, jacobian_determinant, _mask_u8, _squarings, affine_warp, check_interpolation, grid_scale, overlap_args, resample, world_setup
 from .pyramid import level_theta, pyramid, pyramid_masks, pyramid_shapes, upsample_flow
 from .warpings import (GRIDS_SUPPORT, INITIAL_SUPPORT, MASK_SUPPORT, OVERLAP_SUPPORT, WORLD_SUPPORT, affine_register, device_loop_settings, flow_register, get_affine_warp, resolve_initial, rigid_register,
                        two_lattices)
@@ -27,7 +27,7 @@ def _per_level(value, levels, name):
 class Register():
     def __init__(self, mode='rigid', device='cpu', criterion=None, weight=None, grad_edges=False, debug=False, *,
                  optimizer='sgd', honor_criterion=False, init=None, smooth_weight=0.0, flow_model='unet', levels=1, spacing=None,
-                 bending_weight=0.0, device_loop=False, diffeomorphic=False, squarings=6):
+                 bending_weight=0.0, device_loop=False, diffeomorphic=False, squarings=6, folding_weight=0.0, folding_threshold=0.3):
         '''
         Numerical registration on an AMD GPU (MI355X) behind the TorchRegister API.
 
@@ -60,6 +60,14 @@ class Register():
             `.inverse_flow` = exp(-velocity), and `.inverse(x)` warps x with it.  With levels > 1 the hand-over passes the VELOCITY: a level's base
             is upsample_flow(the previous level's final velocity), its velocity is base + expand(control), and the exponential is taken of the
             sum; bending_weight acts on each level's own lattice as without diffeomorphic.
+        folding_weight, folding_threshold : (keyword-only extension, flow_model='bspline' only, not with diffeomorphic=True; ValueError otherwise, here)
+            w >= 0 and eps: w * folding_penalty(flow, eps) = w * mean_x max(0, eps - det(x))^2 joins each pair's loss, det being the Jacobian
+            determinant map of the level's TOTAL flow (jacobian_determinant: finite differences at voxel centres).  It keeps the deformation from
+            folding where bending_weight only penalises curvature, on every route of the B-spline loop - fused criteria, MILoss, initial=, mask=,
+            overlap=.  `.losses` hold the total.  With levels > 1 the same weight applies at every level, each on its own lattice and on the sum
+            base + expand(control) handed up so far.  The default eps = 0.3 is a margin for what lies between the voxel centres.  After optim,
+            `.jacobian()` is the map of `.theta`.  With initial= the whole transform's local volume change is that map times the constant
+            determinant of the affine.
         device_loop : (keyword-only extension, mode='rigid' / 'affine') True: criterion must be exactly [MILoss] with a non-zero weight (ValueError
             otherwise, here) and optim runs the whole loop on the device (trx_affine_mi_run: the warp fused into the histogram and gradient passes
             of the mutual information, no host sync per iteration); honor_criterion is implied, a batch is B independent pairs, and with levels > 1
@@ -86,6 +94,12 @@ class Register():
         bending_weight = _bending_weight(bending_weight)
         if bending_weight != 0 and not (mode == 'flow' and flow_model == 'bspline'):
             raise ValueError("bending_weight is the bending-energy penalty of mode='flow' with flow_model='bspline'")
+        folding_weight, folding_threshold = _folding_weight(folding_weight), _folding_threshold(folding_threshold)
+        if folding_weight != 0 and not (mode == 'flow' and flow_model == 'bspline'):
+            raise ValueError("folding_weight is the folding penalty of mode='flow' with flow_model='bspline' (autograd users have folding_penalty)")
+        if folding_weight != 0 and diffeomorphic:
+            raise ValueError("folding_weight is not taken with diffeomorphic=True: the exponential of a velocity field does not fold")
+        self.folding_weight, self.folding_threshold = folding_weight, folding_threshold
         squarings = _squarings(squarings)
         if diffeomorphic:
             if not (mode == 'flow' and flow_model == 'bspline'):
@@ -131,7 +145,8 @@ class Register():
         kw = dict(mode='bilinear', n=n, lr=lr, max_epochs=max_epochs, optimizer=self.optimizer, smooth_weight=self.smooth_weight,
                   flow_model=self.flow_model)
         if self.flow_model == 'bspline':
-            kw.update(spacing=self.spacing, bending_weight=self.bending_weight, diffeomorphic=self.diffeomorphic, squarings=self.squarings)
+            kw.update(spacing=self.spacing, bending_weight=self.bending_weight, diffeomorphic=self.diffeomorphic, squarings=self.squarings,
+                      folding_weight=self.folding_weight, folding_threshold=self.folding_threshold)
         if self.criterion is not None and self.weight is not None:           # ref:torchregister.py:71-73
             kw.update(criterions=self.criterion, weights=self.weight)
         elif self.weight is not None:                                         # ref:torchregister.py:74-76
@@ -406,6 +421,18 @@ class Register():
         if interpolation == 'linear':
             return self.warp(self.theta.detach(), moving)
         return resample(moving, theta=self.theta.detach(), size=self.target_shape, interpolation=interpolation)
+
+    def jacobian(self):
+        '''
+        The Jacobian determinant map [B,1,x,y(,z)] of the deformation in .theta (mode='flow', any flow model, after optim): jacobian_determinant of
+        the flow.  det <= 0 marks a fold; reg.jacobian().amin() and (reg.jacobian() <= 0).float().mean() are the usual summaries.  With
+        optim(initial=...) multiply by the constant determinant of the affine for the whole transform.
+        '''
+        if self.mode != 'flow':
+            raise ValueError("jacobian() is the determinant map of mode='flow': a rigid / affine transform has one constant determinant, that of reg.theta[:, :, :-1]")
+        if self.theta is None:
+            raise RuntimeError("call optim() first")
+        return jacobian_determinant(self.theta)
 
     def inverse(self, x, interpolation='linear'):
         '''

@@ -526,11 +526,14 @@ class flow_register(nn.Module):
     optimize(..., initial=theta) (keyword-only extension, flow_model='bspline' with MILoss alone; ValueError(INITIAL_SUPPORT) otherwise): the
     deformation is composed with the effective theta of a rigid / affine stage and the moving image - on a lattice of its own - is sampled ONCE,
     at theta applied to voxel + flow (_engine.affine_flow_warp; the loop runs in trx_bspline_mi_run_grids).  `.flow`, `.control` and mask stay on
-    the target lattice, in target voxels; `.deform(x)` warps any [B,c,*moving spatial] onto it; `.initial` keeps the theta."""
+    the target lattice, in target voxels; `.deform(x)` warps any [B,c,*moving spatial] onto it; `.initial` keeps the theta.
+    folding_weight = w > 0, folding_threshold = eps (keyword-only extension, flow_model='bspline' without diffeomorphic; ValueError otherwise):
+    w * _engine.folding_penalty(flow, eps) - the mean of max(0, eps - det)^2 over the Jacobian determinant map of the total flow - joins each pair's
+    loss on every route of the B-spline loop (fused criteria, MILoss, initial=, mask=, overlap=, bending_weight); `.losses` and stop_crit see the total."""
 
     def __init__(self, img_size, mode="bilinear", in_c=1, n=1, criterions=None, weights=[0.33, 0.33, 0.33], lr=1E-3,
                  max_epochs=2000, stop_crit=1E-4, *, flow_model="unet", optimizer="sgd", smooth_weight=0.0, spacing=None,
-                 bending_weight=0.0, diffeomorphic=False, squarings=6):
+                 bending_weight=0.0, diffeomorphic=False, squarings=6, folding_weight=0.0, folding_threshold=0.3):
         super().__init__()
         if flow_model not in ("unet", "direct", "bspline"):
             raise ValueError("flow_model must be 'unet', 'direct' or 'bspline'")
@@ -547,6 +550,13 @@ class flow_register(nn.Module):
         self.bending_weight = _engine._bending_weight(bending_weight)
         if flow_model != "bspline" and self.bending_weight != 0:
             raise ValueError(f"bending_weight is the bending-energy penalty of flow_model='bspline'; flow_model={flow_model!r} has no control lattice")
+        self.folding_weight, self.folding_threshold = _engine._folding_weight(folding_weight), _engine._folding_threshold(folding_threshold)
+        if self.folding_weight != 0:
+            if flow_model != "bspline":
+                raise ValueError(f"folding_weight is the folding penalty of flow_model='bspline'; flow_model={flow_model!r} takes none "
+                                 "(autograd users have folding_penalty)")
+            if self.diffeomorphic:
+                raise ValueError("folding_weight is not taken with diffeomorphic=True: the exponential of a velocity field does not fold")
         self.spacing = None
         if flow_model == "bspline":
             self.spacing = _engine._spacing3(8 if spacing is None else spacing, len(self.img_size))[3 - len(self.img_size):]
@@ -671,7 +681,7 @@ class flow_register(nn.Module):
         solver = BSplineSolver(moving, target, self.spacing, loss=spec, mi=mi, optimizer=self.optimizer_kind, lr=self.lr, init=self.init_control,
                                base=self.base_flow, capacity=max(1, self.max_epochs), stop_crit=self.stop_crit, keep_last=True,
                                bending_weight=self.bending_weight, squarings=self.squarings if self.diffeomorphic else None, mask=mask, initial=initial,
-                               overlap=overlap, moving_mask=moving_mask)
+                               overlap=overlap, moving_mask=moving_mask, folding_weight=self.folding_weight, folding_threshold=self.folding_threshold)
         self.initial = initial
         solver.run(self.max_epochs)
         done = solver.step.cpu()
