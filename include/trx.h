@@ -65,7 +65,9 @@ extern "C" {
  *        workspace query - no entry point changed its signature.
  *        Later addition under the same number: trx_flow_jacobian, trx_flow_folding and its workspace query, trx_fold_cfg, trx_bspline_run_fold,
  *        trx_bspline_mi_run_fold and their workspace queries (the Jacobian determinant map of a dense flow and a folding penalty on it, alone and
- *        inside the free-form deformation loops) - new entry points and one new struct only. */
+ *        inside the free-form deformation loops) - new entry points and one new struct only.
+ *        Later addition under the same number: trx_flow_compose, trx_flow_invert (composition of two dense flows and the fixed-point inverse of one) -
+ *        new entry points only. */
 #define TRX_VERSION 240
 #define TRX_PSTRIDE 12  /* floats per pair in theta / param / adam / best_theta arrays */
 
@@ -854,6 +856,36 @@ size_t trx_bspline_mi_fold_workspace_bytes(int ndim, int B, int D, int H, int W,
 int trx_bspline_mi_run_fold(const trx_volumes *vol, const trx_moving_grid *mg /*[host], nullable*/, const float *theta /*nullable*/, const trx_mi_cfg *cfg,
                             const trx_opt_cfg *opt, const trx_bspline_state *st, const int *spacing /*[host]*/, const trx_fold_cfg *fold /*[host]*/, int iters,
                             void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- Composition and fixed-point inversion of dense flows.  Extension: the reference has neither.  Later addition under
+ * TRX_VERSION 240: new entry points only.  CPU restatement: tests/flowops_ref.py.
+ * Fields are [B][ndim][D][H][W] fp32 contiguous in voxel units, channel a along spatial axis a (trx_svf_exp's convention; 2-D: D = 1); a warp is
+ * warped(x) = image(x + flow(x)).  A position is ONE fp32 add of the voxel index and the displacement.  Two samplers of a field f at a position p:
+ *   S0(f, p)  trx_svf_exp's: bi / trilinear, i0 = floor(p), t = p - i0, corners outside the volume contribute zero.
+ *   Sb(f, p)  border extension.  Per axis pc = min(max(p, 0), S - 1), i0 = min(floor(pc), max(S - 2, 0)), t = pc - i0, corners i0 and
+ *             min(i0 + 1, S - 1), weights 1 - t and t (an axis of one voxel: t = 0).  Sb is continuous in p and its Lipschitz constant is that of f -
+ *             the fixed-point iteration below needs that at the faces, where S0 ramps to zero over one voxel.
+ * Compose:  c = compose(first, second),  c(x) = second(x) + S(first, x + second(x)),  S = Sb for padding 1, S0 for padding 0.
+ *           image(x + c(x)) is flow_warp(flow_warp(image, first), second) up to the second interpolation: one resampling in place of two.  With padding 0,
+ *           compose(u, u) is one squaring: the bits of trx_svf_exp(2u, squarings = 1).
+ * Invert:   v = invert(u) is the right inverse on the lattice, (id + u) o (id + v) = id, that is v(y) = -Sb(u, y + v(y)).  Per voxel y:
+ *             v_0 = init(y) (init NULL: 0);  v_{k+1} = -Sb(u, y + v_k);  r = max_a |v_{k+1,a} - v_{k,a}|;
+ *           the voxel stops after the first update with r <= tol, or after `iterations` updates; residual(y) = the r of its last update, so a voxel
+ *           has converged exactly when residual <= tol.  tol = 0 runs the fixed count, except for a voxel that reaches a bit-exact fixed point.
+ *           Nothing in a voxel's result depends on another voxel's iteration, on the call or on the batch.  A non-finite value, the voxel's own v_k or
+ *           a sampled one, ends the voxel at once with NaN in every channel of v and in residual.  A folded u has no inverse where it folds: there
+ *           the iteration need not converge, the outputs stay finite and residual says where.  No damping, no convergence guarantee beyond that report.
+ * Neither operator is differentiable.  One launch each, a gather per voxel: no workspace, no atomics, no host sync, no allocation.  Refusals before any
+ * HIP call: TRX_ERR_NDIM (ndim not 2 or 3; ndim 2 with D != 1); TRX_ERR_ARG (a NULL pointer other than init / residual, a size < 1, B outside
+ * 1 .. 65535, more than 2^31 voxels, padding not 0 or 1, iterations outside 1 .. 1000, tol negative or not finite, out == first, inverse == flow). */
+/* out = compose(first, second).  out may be `second` itself (second is read at the voxel's own index only); out must not overlap first. */
+int trx_flow_compose(const float *first, const float *second, float *out, int ndim, int B, int D, int H, int W, int padding /*0 zeros, 1 border*/,
+                     void *stream);
+/* inverse = invert(flow) from init (NULL: zero); residual NULL or [B][D][H][W].  inverse may be `init` itself (a voxel reads its own init before it
+ * writes), so a run can be continued in place: K1 updates followed by K2 from that result are the bits of K1 + K2 at tol = 0.  inverse and residual
+ * must not overlap flow. */
+int trx_flow_invert(const float *flow, const float *init /*NULL: zero*/, float *inverse, float *residual /*NULL or [B][N]*/, int ndim, int B, int D, int H,
+                    int W, int iterations /*1..1000*/, float tol /*finite, >= 0*/, void *stream);
 
 #ifdef __cplusplus
 }

@@ -732,6 +732,72 @@ def folding_penalty(flow, threshold=0.3):
     return folding_penalty_grad(flow, threshold, need_grad=False)[0]
 
 
+_FLOW_PADDING = {"zeros": 0, "border": 1}
+
+
+def _invert_args(iterations, tol):
+    """(iterations, tol) of invert_flow: an int in 1 .. 1000 and a finite float >= 0, or ValueError."""
+    if isinstance(iterations, bool) or not isinstance(iterations, int) or not 1 <= iterations <= 1000:
+        raise ValueError(f"iterations must be an int in 1 .. 1000, got {iterations!r}")
+    try:
+        t = float(tol)
+    except (TypeError, ValueError):
+        raise ValueError(f"tol must be a finite number >= 0, got {tol!r}") from None
+    if isinstance(tol, bool) or not (t >= 0.0) or t == float("inf"):
+        raise ValueError(f"tol must be a finite number >= 0, got {tol!r}")
+    return iterations, t
+
+
+def _same_field(a, b, what):
+    if not isinstance(a, torch.Tensor) or not isinstance(b, torch.Tensor):
+        raise TypeError(f"{what} must be torch.Tensors")
+    if a.shape != b.shape:
+        raise ValueError(f"{what} must have one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+
+
+def compose_flows(first, second, padding="border"):
+    """c = compose(first, second) for two dense flows [B, nd, *spatial] of one shape (fp32, GPU; voxel units, channel a along spatial axis a):
+    c(x) = second(x) + first(x + second(x)) (trx_flow_compose), so that flow_warp(image, c) is flow_warp(flow_warp(image, first), second) with one
+    interpolation of the image in place of two.  padding='border' (the default) samples `first` with border extension - a position outside the volume
+    takes the value of the nearest face; 'zeros' is svf_exp's sampler, corners outside the volume contributing zero: compose_flows(u, u, 'zeros') is
+    one squaring, the bits of svf_exp(2 * u, 1).  Not differentiable."""
+    if padding not in _FLOW_PADDING:
+        raise ValueError(f"padding must be 'border' or 'zeros', got {padding!r}")
+    _same_field(first, second, "first and second")
+    lib, f, nd, geom = _dense_flow(first, "first")
+    _, s, _, _ = _dense_flow(second, "second")
+    f, s = f.to(torch.float32), s.to(torch.float32)
+    out = torch.empty_like(s)
+    with torch.cuda.device(f.device):
+        rc = lib.trx_flow_compose(_lib.ptr(f), _lib.ptr(s), _lib.ptr(out), *geom, _FLOW_PADDING[padding], _lib.current_stream(f.device))
+    _lib.check(rc, "trx_flow_compose")
+    return out
+
+
+def invert_flow(flow, iterations=30, tol=1e-3, init=None, return_residual=False):
+    """v = the right inverse of a dense flow u [B, nd, *spatial] (fp32, GPU; voxel units) on its lattice: (id + u) o (id + v) = id, by the fixed-point
+    iteration v <- -u(y + v) with border extension (trx_flow_invert; one launch, every update of a voxel in registers).  A voxel stops after the first
+    update that moves no channel by more than `tol` voxels, or after `iterations` updates; tol=0 runs the fixed count.  init (the flow's shape): the
+    starting v, zero when None - a run can be continued from an earlier result.  return_residual=True: (v, residual [B, 1, *spatial]), the size of
+    each voxel's last update; a voxel has converged exactly when residual <= tol.  Where u folds it has no inverse: the iteration need not converge
+    there, v stays finite, and residual says where - (residual > tol).float().mean() and residual.amax() are the usual summaries.  A non-finite value
+    gives NaN in v and residual at the voxels that meet it.  Carry x from the target back: resample(x, flow=invert_flow(u)).  Not differentiable."""
+    iterations, tol = _invert_args(iterations, tol)
+    if init is not None:
+        _same_field(flow, init, "flow and init")
+    lib, u, nd, geom = _dense_flow(flow)
+    u = u.to(torch.float32)
+    v0 = None
+    if init is not None:
+        v0 = _dense_flow(init, "init")[1].to(torch.float32)
+    v = torch.empty_like(u)
+    res = torch.empty((u.shape[0], 1) + tuple(u.shape[2:]), dtype=torch.float32, device=u.device) if return_residual else None
+    with torch.cuda.device(u.device):
+        rc = lib.trx_flow_invert(_lib.ptr(u), _lib.ptr(v0), _lib.ptr(v), _lib.ptr(res), *geom, iterations, tol, _lib.current_stream(u.device))
+    _lib.check(rc, "trx_flow_invert")
+    return (v, res) if return_residual else v
+
+
 class BSplineSolver:
     """Cubic B-spline free-form deformation (extension): the control lattice `ctrl` [B, nd, *grid] is the parameter, the displacement field
     is base + expand(ctrl); the whole loop (expand, fused loss and dL/dflow, reduce, SGD / Adam, early stop) runs in trx_bspline_run.

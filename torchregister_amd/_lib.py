@@ -204,6 +204,8 @@ SIGNATURES = {
     "trx_bspline_mi_fold_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 9 + [ctypes.POINTER(MovingGrid)]),
     "trx_bspline_mi_run_fold": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), _P, ctypes.POINTER(MICfg), ctypes.POINTER(OptCfg),
                                                ctypes.POINTER(BSplineState), c_int_p, ctypes.POINTER(FoldCfg), ctypes.c_int, _P, ctypes.c_size_t, _P]),
+    "trx_flow_compose": (ctypes.c_int, [_P, _P, _P] + [ctypes.c_int] * 6 + [_P]),
+    "trx_flow_invert": (ctypes.c_int, [_P, _P, _P, _P] + [ctypes.c_int] * 6 + [ctypes.c_float, _P]),
 }
 
 _lib = None

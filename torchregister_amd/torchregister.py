@@ -9,7 +9,7 @@ U-Net-generated flow, 'direct' = the flow field itself is the parameter), levels
 import torch
 from torch import cat
 
-from ._engine import _bending_weight, _folding_threshold, _folding_weight, jacobian_determinant, _mask_u8, _squarings, affine_warp, check_interpolation, grid_scale, overlap_args, resample, world_setup
+from ._engine import _bending_weight, _folding_threshold, _folding_weight, _invert_args, invert_flow, jacobian_determinant, _mask_u8, _squarings, affine_warp, check_interpolation, grid_scale, overlap_args, resample, world_setup
 from .pyramid import level_theta, pyramid, pyramid_masks, pyramid_shapes, upsample_flow
 from .warpings import (GRIDS_SUPPORT, INITIAL_SUPPORT, MASK_SUPPORT, OVERLAP_SUPPORT, WORLD_SUPPORT, affine_register, device_loop_settings, flow_register, get_affine_warp, resolve_initial, rigid_register,
                        two_lattices)
@@ -433,6 +433,23 @@ class Register():
         if self.theta is None:
             raise RuntimeError("call optim() first")
         return jacobian_determinant(self.theta)
+
+    def invert_flow(self, iterations=30, tol=1e-3):
+        '''
+        (v, residual): the inverse [B,nd,x,y(,z)] of the deformation in .theta on its own lattice (mode='flow', any flow model, after optim) by the
+        fixed-point iteration of invert_flow, and each voxel's last update [B,1,x,y(,z)] - a voxel has converged exactly when residual <= tol; where
+        the deformation folds (reg.jacobian() <= 0) it has no inverse and residual says so.  resample(labels_on_target, flow=v,
+        interpolation='nearest') carries a label map from the target back onto the moving image.  Not with optim(initial=...): the whole
+        transform's inverse lives on the moving lattice and is not built.  diffeomorphic=True has .inverse_flow, the exponential of -velocity.
+        '''
+        iterations, tol = _invert_args(iterations, tol)
+        if self.mode != 'flow':
+            raise ValueError("invert_flow() inverts the dense flow of mode='flow': a rigid / affine transform has a closed-form inverse, that of the matrix reg.theta")
+        if self.theta is None:
+            raise RuntimeError("call optim() first")
+        if self.initial is not None:
+            raise ValueError("invert_flow() is not built for optim(initial=...): the inverse of the whole transform lives on the moving lattice")
+        return invert_flow(self.theta, iterations, tol, return_residual=True)
 
     def inverse(self, x, interpolation='linear'):
         '''

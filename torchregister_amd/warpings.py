@@ -762,6 +762,16 @@ class flow_register(nn.Module):
             return self._deform(x, self.flow)
         return _engine.resample(x, theta=None if self.initial is None else self.initial.to(x.device), flow=self.flow, interpolation=interpolation)
 
+    def invert_flow(self, iterations=30, tol=1e-3):
+        """(v, residual): the inverse of `.flow` on its own lattice by _engine.invert_flow, and each voxel's last update (converged exactly where
+        residual <= tol).  RuntimeError before optimize(); ValueError after optimize(initial=...): that transform's inverse lives on the moving lattice."""
+        iterations, tol = _engine._invert_args(iterations, tol)
+        if self.flow is None:
+            raise RuntimeError("invert_flow() needs a finished optimize()")
+        if self.initial is not None:
+            raise ValueError("invert_flow() is not built for optimize(initial=...): the inverse of the whole transform lives on the moving lattice")
+        return _engine.invert_flow(self.flow, iterations, tol, return_residual=True)
+
     def inverse(self, x, interpolation="linear"):
         """x warped with exp(-velocity), the inverse of the deformation `deform` applies (diffeomorphic=True only).  interpolation: as for deform."""
         _engine.check_interpolation(interpolation)
