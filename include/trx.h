@@ -67,7 +67,9 @@ extern "C" {
  *        trx_bspline_mi_run_fold and their workspace queries (the Jacobian determinant map of a dense flow and a folding penalty on it, alone and
  *        inside the free-form deformation loops) - new entry points and one new struct only.
  *        Later addition under the same number: trx_flow_compose, trx_flow_invert (composition of two dense flows and the fixed-point inverse of one) -
- *        new entry points only. */
+ *        new entry points only.
+ *        Later addition under the same number: trx_transform_points, trx_affine_then_flow_resample (points and target-space images through the whole
+ *        transform, in both chain orders) - new entry points only. */
 #define TRX_VERSION 240
 #define TRX_PSTRIDE 12  /* floats per pair in theta / param / adam / best_theta arrays */
 
@@ -886,6 +888,45 @@ int trx_flow_compose(const float *first, const float *second, float *out, int nd
  * must not overlap flow. */
 int trx_flow_invert(const float *flow, const float *init /*NULL: zero*/, float *inverse, float *residual /*NULL or [B][N]*/, int ndim, int B, int D, int H,
                     int W, int iterations /*1..1000*/, float tol /*finite, >= 0*/, void *stream);
+
+/* ---- Points and target-space images through the whole transform, both ways.  Extension: the reference moves no point and has no
+ * inverse.  Later addition under TRX_VERSION 240: new entry points only.  CPU restatement: tests/chain_ref.py.
+ * Lattices have sizes S = (D, H, W), 2-D: D = 1.  Points and flows use the flow convention above: voxel-index units, component a along spatial axis a
+ * (tensor order z, y, x in 3-D, y, x in 2-D).  theta is an EFFECTIVE theta [B][TRX_PSTRIDE] between normalised cubes, rows and columns in x, y, z order:
+ * what trx_transform_resample takes with mg->scale = 1.  These entry points take no scale and no world record; callers convert on the host.
+ * Normalise and un-normalise are trx_affine_flow_warp's closed forms, n_c = (2 p_c + 1) / S_c - 1 and i_r = ((m_r + 1) S_r - 1) / 2.  S(f, p) is a flow
+ * sampled at a float position p: Sb (padding 1, border extension) or S0 (padding 0), the pair of trx_flow_compose.  Border is the natural choice: a
+ * displacement should continue past the face, S0 ramps to zero there.  Two chains from a start lattice S_a to an end lattice S_b:
+ *   chain 0, flow then affine.  The flow lives on S_a.  p' = p + S(flow, p), one fp32 add per axis; out = unnorm_b(theta . (norm_a(p'), 1)).  theta NULL:
+ *            out = p' and S_b is not read.  These are the positions trx_affine_flow_warp samples at, for any p, not only at lattice points.
+ *   chain 1, affine then flow.  The flow lives on S_b.  q = unnorm_b(theta . (norm_a(p), 1)); out = q + S(flow, q).  flow NULL: out = q.  theta NULL: the
+ *            two lattices must be equal and q = p.
+ * With T(p) = theta_eff(p + u(p)) the map of a registration (target voxels to moving voxels: chain 0 from the target lattice to the moving one), its
+ * inverse is chain 1 from the moving lattice to the target one with theta_eff^-1 and v = trx_flow_invert(u): T^-1(q) = r + v(r), r = theta_eff^-1 q.
+ * Both entry points: one launch, a gather per point / output voxel, no workspace, no atomics, no host sync, the same bits on every call, a pair's result
+ * does not depend on its batch; every flow gather index is clamped into its axis in float before any conversion to int, every image gather is predicated
+ * or clamped by the sampler it reuses, and no unbounded float is converted to an integer.  Not differentiable.  Refusals before any HIP call: TRX_ERR_NDIM
+ * (ndim not 2 or 3, checked first; ndim 2 with a lattice whose D != 1); TRX_ERR_ARG (a NULL that is not nullable, theta and flow both NULL, theta NULL with
+ * unequal lattices in chain 1, a size < 1, B outside 1 .. 65535, P < 1, a lattice of >= 2^31 voxels, channels < 1, src_stride < channels voxels of S_b,
+ * order not 0, 1 or 3, padding not 0 or 1, chain not 0 or 1, out overlapping src or flow, out overlapping points without being points). */
+/* out[B][P][ndim] = the chain's image of points[B][P][ndim].  out may be `points` itself (a point is read before it is written).  from_size / to_size:
+ * host, {D, H, W} of S_a / S_b; to_size may be NULL in chain 0 without theta.  A non-finite component of a point gives NaN in every component of that
+ * point only, and no address is formed from it; a finite point however far outside is sampled by S as the definition says. */
+int trx_transform_points(const float *points, float *out, int ndim, int B, int P, const float *theta /*nullable*/, const float *flow /*nullable*/,
+                         const int *from_size /*[host] [3]*/, const int *to_size /*[host] [3]*/, int chain /*0 flow then affine, 1 affine then flow*/,
+                         int padding /*0 zeros, 1 border*/, void *stream);
+/* out[B][channels][*S_a] (S_a = out_size): for every voxel y of the output lattice, the sample of src [B][channels][*S_b] (S_b = src_size; src_stride
+ * elements between batch items) at chain 1's position of y, the flow [B][ndim][*S_b] living on src's lattice.  The resampler in the other chain order:
+ * trx_transform_resample and trx_affine_flow_warp do the flow first, then the affine.  `order` selects the sampler, zero padding in every order:
+ *   order 0: rint per axis, half to even; 0 where a rounded index lies outside (trx_transform_resample's rule).
+ *   order 1: trx_flow_warp's bi- / trilinear sampler, corners outside the volume contributing zero, at the position clamped into [-2, S + 1] per axis
+ *            (beyond -1 and S every corner lies outside, so every finite position keeps its value).
+ *   order 3: src holds trx_spline_coefficients; taps, mirror rule and the 0 beyond half a voxel outside the field of view are trx_transform_resample's.
+ * A NaN position (a non-finite theta or flow value) yields 0 in every order: orders 0 and 3 by the existing rule, order 1 because the clamp sends a NaN to
+ * -2.  `padding` is the flow sampler's (S above), not the image's.  Channels share positions and weights.  out must not overlap src or flow. */
+int trx_affine_then_flow_resample(const float *src, size_t src_stride, const int *src_size /*[host] [3]*/, const float *theta /*nullable*/,
+                                  const float *flow /*nullable*/, int ndim, int B, int channels, const int *out_size /*[host] [3]*/, int order /*0, 1, 3*/,
+                                  int padding /*0 zeros, 1 border*/, float *out, void *stream);
 
 #ifdef __cplusplus
 }

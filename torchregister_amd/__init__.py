@@ -8,6 +8,7 @@ __version__ = "0.2.3"   # = the reference package version this host layer mirror
 
 from ._engine import (AffineMISolver, AffineSolver, BSplineSolver, FlowSolver, LossSpec, SlabFlowSolver, SlabPeers, bspline_bending, bspline_expand, bspline_grid, bspline_reduce, svf_exp, svf_exp_backward,  # noqa: F401
                       folding_penalty, folding_penalty_grad, jacobian_determinant, compose_flows, invert_flow,
+                      invert_theta, points_from_world, points_to_world, resample_affine_then_flow, transform_points,
                       affine_flow_valid, affine_flow_warp, affine_flow_warp_backward, affine_mi_loss_grad, grid_scale, resample, run_slabs_lockstep, spline_coefficients,
                       WorldGeometry, affine_world_theta, image_moments, theta_from_world, world_from_theta, world_geometry, world_setup)
 from .pyramid import pyramid, pyramid_shapes, upsample_flow  # noqa: F401

@@ -2306,6 +2306,178 @@ def resample(x, *, theta=None, flow=None, size=None, scale=None, interpolation="
     return out
 
 
+CHAINS = {"flow_then_affine": 0, "affine_then_flow": 1}
+_ORDERS = {"nearest": 0, "linear": 1, "cubic": 3}
+
+
+def invert_theta(theta):
+    """The effective theta [B,nd,nd+1] (or [nd,nd+1]) of the inverse map: theta maps lattice a's normalised cube to lattice b's, the result maps b's to
+    a's - what resample(x_on_target, theta=invert_theta(reg.theta), size=moving_shape) and chain 'affine_then_flow' take.  fp64 on the homogeneous
+    matrix, returned as fp64 on the CPU.  ValueError for a wrong shape and for a singular or non-finite matrix."""
+    if not isinstance(theta, torch.Tensor) or theta.dim() not in (2, 3) or tuple(theta.shape[-2:]) not in ((2, 3), (3, 4)):
+        raise ValueError(f"expected theta [B,nd,nd+1] or [nd,nd+1] with nd 2 or 3, got {tuple(theta.shape) if isinstance(theta, torch.Tensor) else type(theta).__name__}")
+    nd = theta.shape[-2]
+    H = _homogeneous(theta, nd)
+    if not bool(torch.isfinite(H).all()):
+        raise ValueError("theta has a non-finite entry: it has no inverse")
+    sv = torch.linalg.svdvals(H[:, :nd, :nd])
+    if bool((sv[:, -1] <= 1e-12 * sv[:, 0]).any()) or bool((sv[:, 0] == 0).any()):
+        raise ValueError("theta's matrix part is singular: it has no inverse")
+    inv = torch.linalg.inv(H)[:, :nd]
+    return inv if theta.dim() == 3 else inv[0]
+
+
+def _world_points(points, affine, name):
+    if not isinstance(points, torch.Tensor) or points.dim() not in (2, 3) or points.shape[-1] not in (2, 3):
+        raise ValueError(f"expected points [B,P,nd] or [P,nd] with nd 2 or 3, got {tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__}")
+    nd = points.shape[-1]
+    A = _world_affine(affine, nd, name, points.shape[0] if points.dim() == 3 else 1)
+    p = points.detach().to(torch.float64)
+    return p, (A if p.dim() == 3 else A[0]).to(p.device), nd
+
+
+def points_to_world(points, affine):
+    """Voxel positions [B,P,nd] / [P,nd] in the tensor's axis order (z, y, x / y, x) -> world positions (x, y(, z)) in mm under a voxel-to-world matrix of
+    optim's convention (columns in the tensor's axis order, rows world x, y(, z); [nd+1,nd+1] or [B,nd+1,nd+1]).  fp64 torch arithmetic on the points'
+    device, no kernel: (points_to_world(a, A) - points_to_world(b, A)).norm(dim=-1) is a target registration error in mm."""
+    p, A, nd = _world_points(points, affine, "affine")
+    return p @ A[..., :nd, :nd].transpose(-1, -2) + A[..., None, :nd, nd]
+
+
+def points_from_world(points, affine):
+    """The inverse of points_to_world: world positions (x, y(, z)) in mm -> voxel positions in the tensor's axis order, fp64."""
+    p, A, nd = _world_points(points, affine, "affine")
+    Ai = torch.linalg.inv(A)
+    return p @ Ai[..., :nd, :nd].transpose(-1, -2) + Ai[..., None, :nd, nd]
+
+
+def _chain_theta(theta, B, nd, what):
+    if not isinstance(theta, torch.Tensor) or theta.dim() != 3 or tuple(theta.shape[1:]) != (nd, nd + 1) or theta.shape[0] not in (1, B):
+        raise ValueError(f"{what}: expected theta of shape {(B, nd, nd + 1)} or {(1, nd, nd + 1)}, got {tuple(theta.shape) if isinstance(theta, torch.Tensor) else type(theta).__name__}")
+
+
+def _chain_shape(shape, nd, name):
+    try:
+        shape = tuple(int(s) for s in shape)
+    except TypeError:
+        raise ValueError(f"{name} must be {nd} positive sizes, got {shape!r}") from None
+    if len(shape) != nd or min(shape) < 1:
+        raise ValueError(f"{name} must be {nd} positive sizes, got {shape}")
+    return shape
+
+
+def _points_args(points, theta, flow, from_shape, to_shape, chain, padding):
+    """What transform_points refuses, on the host, before any device work: returns (B, P, nd, from shape, to shape)."""
+    if chain not in CHAINS:
+        raise ValueError(f"chain must be 'flow_then_affine' or 'affine_then_flow', got {chain!r}")
+    if padding not in _FLOW_PADDING:
+        raise ValueError(f"padding must be 'border' or 'zeros', got {padding!r}")
+    if not isinstance(points, torch.Tensor) or points.dim() not in (2, 3) or points.shape[-1] not in (2, 3) or points.shape[-2] < 1:
+        raise ValueError(f"expected points [B,P,nd] or [P,nd] with nd 2 or 3 and P >= 1, got {tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__}")
+    if theta is None and flow is None:
+        raise ValueError("transform_points needs a transform: theta, flow or both")
+    nd, P, B = points.shape[-1], points.shape[-2], (points.shape[0] if points.dim() == 3 else 1)
+    if theta is not None:
+        _chain_theta(theta, B, nd, "transform_points")
+    lattice = None
+    if flow is not None:
+        if not isinstance(flow, torch.Tensor) or flow.dim() != nd + 2 or flow.shape[1] != nd or flow.shape[0] not in (1, B):
+            raise ValueError(f"expected flow [{B}|1,{nd},*spatial], got {tuple(flow.shape) if isinstance(flow, torch.Tensor) else type(flow).__name__}")
+        lattice = tuple(flow.shape[2:])
+    # the flow lives on the start lattice in chain 0 and on the end lattice in chain 1: that shape defaults from it
+    own, other = ("from_shape", "to_shape") if CHAINS[chain] == 0 else ("to_shape", "from_shape")
+    shapes = {"from_shape": None if from_shape is None else _chain_shape(from_shape, nd, "from_shape"),
+              "to_shape": None if to_shape is None else _chain_shape(to_shape, nd, "to_shape")}
+    if lattice is not None:
+        if shapes[own] is not None and shapes[own] != lattice:
+            raise ValueError(f"{own} {shapes[own]} is not the flow's lattice {lattice} (chain {chain!r})")
+        shapes[own] = lattice
+    if theta is None:
+        if shapes[other] is not None and shapes[other] != shapes[own]:
+            raise ValueError(f"without theta both lattices are the flow's {shapes[own]}, got {other} {shapes[other]}")
+        shapes[other] = shapes[own]
+    if shapes["from_shape"] is None or shapes["to_shape"] is None:
+        raise ValueError("theta acts between two lattices: give from_shape and to_shape (the flow's lattice is taken from the flow)")
+    return B, P, nd, shapes["from_shape"], shapes["to_shape"]
+
+
+def transform_points(points, *, theta=None, flow=None, from_shape=None, to_shape=None, chain="flow_then_affine", padding="border"):
+    """Points [B,P,nd] or [P,nd] (fp32, GPU; voxel positions in the tensor's axis order) carried through an effective theta [B|1,nd,nd+1], a dense flow
+    [B|1,nd,*spatial] or both (extension, include/trx.h: trx_transform_points) -> the same shape.  From the lattice from_shape to the lattice to_shape:
+      chain='flow_then_affine': p' = p + S(flow, p) with the flow on from_shape, then theta between the normalised cubes - target voxels to moving
+          voxels under a registration's theta_eff(p + u(p)): transform_points(p, theta=reg.initial, flow=reg.theta, to_shape=moving spatial);
+      chain='affine_then_flow': theta first, then q + S(flow, q) with the flow on to_shape - the inverse map with invert_theta(theta) and
+          invert_flow(flow).
+    The flow's lattice is taken from the flow; without theta both lattices are that one.  padding: 'border' (default; the displacement continues past
+    a face) or 'zeros' (compose_flows' pair).  A non-finite point comes back as NaN.  Not differentiable.  ValueError before any device work for an
+    unknown chain or padding, neither theta nor flow, and shapes that do not fit."""
+    B, P, nd, fs, ts = _points_args(points, theta, flow, from_shape, to_shape, chain, padding)
+    _require_gpu(points, "points")
+    if flow is not None:
+        _require_gpu(flow, "flow")
+    lib = _lib.load()
+    dev = points.device
+    pts = points.detach().reshape(B, P, nd).to(torch.float32).contiguous()
+    th = None if theta is None else _initial_theta(theta, B, nd, dev)
+    fl = None if flow is None else flow.detach().to(torch.float32).expand(B, *flow.shape[1:]).contiguous()
+    out = torch.empty_like(pts)
+    with torch.cuda.device(dev):
+        rc = lib.trx_transform_points(_lib.ptr(pts), _lib.ptr(out), nd, B, P, _lib.ptr(th), _lib.ptr(fl), (ctypes.c_int * 3)(*_dhw(fs)),
+                                      (ctypes.c_int * 3)(*_dhw(ts)), CHAINS[chain], _FLOW_PADDING[padding], _lib.current_stream(dev))
+    _lib.check(rc, "trx_transform_points")
+    return out.reshape(points.shape)
+
+
+def _chain_resample_args(x, theta, flow, size, interpolation, padding):
+    """What resample_affine_then_flow refuses, on the host, before any device work: returns the output lattice."""
+    check_interpolation(interpolation)
+    if padding not in _FLOW_PADDING:
+        raise ValueError(f"padding must be 'border' or 'zeros', got {padding!r}")
+    if not isinstance(x, torch.Tensor) or x.dim() not in (4, 5):
+        raise ValueError(f"expected x [B,C,H,W] or [B,C,D,H,W], got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+    if theta is None and flow is None:
+        raise ValueError("resample_affine_then_flow needs a transform: theta, flow or both")
+    nd, B = x.dim() - 2, x.shape[0]
+    if theta is not None:
+        _chain_theta(theta, B, nd, "resample_affine_then_flow")
+    if flow is not None:
+        if not isinstance(flow, torch.Tensor) or flow.dim() != x.dim() or flow.shape[1] != nd or flow.shape[0] not in (1, B):
+            raise ValueError(f"expected flow [{B}|1,{nd},*x's spatial], got {tuple(flow.shape) if isinstance(flow, torch.Tensor) else type(flow).__name__}")
+        if tuple(flow.shape[2:]) != tuple(x.shape[2:]):
+            raise ValueError(f"the flow lives on x's lattice {tuple(x.shape[2:])} (the affine comes first), got a flow on {tuple(flow.shape[2:])}")
+    size = _chain_shape(size, nd, "size")
+    if theta is None and size != tuple(x.shape[2:]):
+        raise ValueError(f"without theta the output lattice is x's own {tuple(x.shape[2:])}, got size {size}")
+    return size
+
+
+def resample_affine_then_flow(x, *, theta=None, flow=None, size, interpolation="cubic", padding="border"):
+    """x [B,C,*spatial] (fp32, GPU) resampled onto the lattice `size` in the chain order resample() does not have: the affine first, then a flow that
+    lives on x's own lattice (extension, include/trx.h: trx_affine_then_flow_resample) -> [B,C,*size].  Output voxel y samples x at q + S(flow, q),
+    q = theta applied to y between the normalised cubes of `size` and of x's lattice (theta None: q = y, size = x's lattice; flow None: q itself).
+    With theta = invert_theta(theta_eff) and flow = invert_flow(u) it carries an image from the target lattice of a registration run with
+    optim(initial=...) back onto the moving lattice: Register.to_moving.  interpolation as for resample ('cubic' runs spline_coefficients first);
+    padding is the FLOW sampler's, 'border' or 'zeros' - the image is zero padded in every interpolation.  Not differentiable."""
+    size = _chain_resample_args(x, theta, flow, size, interpolation, padding)
+    _require_gpu(x, "x")
+    if flow is not None:
+        _require_gpu(flow, "flow")
+    lib = _lib.load()
+    B, C, nd, dev = x.shape[0], x.shape[1], x.dim() - 2, x.device
+    src = x.detach().to(torch.float32).contiguous()
+    if interpolation == "cubic":
+        src = spline_coefficients(src)
+    th = None if theta is None else _initial_theta(theta, B, nd, dev)
+    fl = None if flow is None else flow.detach().to(torch.float32).expand(B, *flow.shape[1:]).contiguous()
+    out = torch.empty((B, C) + size, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.trx_affine_then_flow_resample(_lib.ptr(src), src[0].numel(), (ctypes.c_int * 3)(*_dhw(tuple(src.shape[2:]))), _lib.ptr(th), _lib.ptr(fl), nd, B, C,
+                                               (ctypes.c_int * 3)(*_dhw(size)), _ORDERS[interpolation], _FLOW_PADDING[padding], _lib.ptr(out),
+                                               _lib.current_stream(dev))
+    _lib.check(rc, "trx_affine_then_flow_resample")
+    return out
+
+
 def _world_record(world, B, dev):
     """The records [B, 32] (a WorldGeometry or a tensor) as a contiguous fp64 tensor on `dev`."""
     rec = world.record if isinstance(world, WorldGeometry) else torch.as_tensor(world)

@@ -206,6 +206,8 @@ SIGNATURES = {
                                                ctypes.POINTER(BSplineState), c_int_p, ctypes.POINTER(FoldCfg), ctypes.c_int, _P, ctypes.c_size_t, _P]),
     "trx_flow_compose": (ctypes.c_int, [_P, _P, _P] + [ctypes.c_int] * 6 + [_P]),
     "trx_flow_invert": (ctypes.c_int, [_P, _P, _P, _P] + [ctypes.c_int] * 6 + [ctypes.c_float, _P]),
+    "trx_transform_points": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 3 + [_P, _P, c_int_p, c_int_p, ctypes.c_int, ctypes.c_int, _P]),
+    "trx_affine_then_flow_resample": (ctypes.c_int, [_P, ctypes.c_size_t, c_int_p, _P, _P] + [ctypes.c_int] * 3 + [c_int_p, ctypes.c_int, ctypes.c_int, _P, _P]),
 }
 
 _lib = None

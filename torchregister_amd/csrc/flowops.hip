@@ -4,7 +4,8 @@
 // Definition: fields [B][nd][D][H][W] fp32 in voxels, channel a along spatial axis a; a warp is warped(x) = image(x + flow(x)); a position is ONE fp32
 // add of the voxel index and the displacement.  S0(f, p) is svf.hip's sampler (svf_sample.h: corners outside the volume contribute zero); Sb(f, p) is
 // border extension, per axis pc = min(max(p, 0), S - 1), i0 = min(floor(pc), max(S - 2, 0)), t = pc - i0, corners i0 and min(i0 + 1, S - 1): continuous
-// in p with the Lipschitz constant of f, which the fixed-point iteration needs at the faces (S0 ramps to zero over one voxel there).
+// in p with the Lipschitz constant of f, which the fixed-point iteration needs at the faces (S0 ramps to zero over one voxel there).  Both samplers
+// live in flow_sample.h, which chain.hip shares.
 //   compose   c(x) = second(x) + S(first, x + second(x)), S = Sb (padding 1) or S0 (padding 0).  With S0, compose(u, u) is svf_square_kernel's
 //             arithmetic statement for statement: the bits of trx_svf_exp(2u, squarings = 1).
 //   invert    v_0 = init or 0; v_{k+1}(y) = -Sb(u, y + v_k(y)); r = max_a |v_{k+1,a} - v_{k,a}|; the voxel stops after the first update with r <= tol
@@ -17,49 +18,11 @@
 //                                  update gathers 2^nd nd floats of u through L1 / L2 - all indices clamped, no load predicated - and a lane leaves the loop
 //                                  when it has converged (a wave runs as long as its slowest lane).  One store of v and one of residual; no workspace,
 //                                  no atomics, nothing shared between voxels: a voxel's result depends on u and its own init alone.
-#include "svf_sample.h"
+#include "flow_sample.h"
 
 #include <cmath>
 
 namespace trx {
-
-// Border extension on one axis: the two corner indices (both inside the axis, whatever p) and t.  A NaN position takes the first voxel; the kernels
-// that must tell (the inversion) test their values for finiteness themselves.
-__device__ __forceinline__ void flo_axis(float p, int S, int (&c)[2], float &t)
-{
-    const float pc = fminf(fmaxf(p, 0.f), (float)(S - 1));
-    c[0] = min((int)floorf(pc), max(S - 2, 0));
-    t = pc - (float)c[0];
-    c[1] = min(c[0] + 1, S - 1);
-}
-
-// acc = Sb(f, x + d) for the nd channels of f (d in the flow's channel order: 3-D z, y, x; 2-D y, x)
-template <int ND>
-__device__ __forceinline__ void flo_sample_border(const float *__restrict__ f, unsigned N, int D, int H, int W, const int (&x)[3], const float (&d)[ND],
-                                                  float (&acc)[ND])
-{
-    const int S[3] = {D, H, W};
-    int c[3][2];
-    float t[3];
-    c[0][0] = c[0][1] = 0;
-    t[0] = 0.f;
-#pragma unroll
-    for (int a = 3 - ND; a < 3; a++) flo_axis((float)x[a] + d[a - (3 - ND)], S[a], c[a], t[a]);
-#pragma unroll
-    for (int ch = 0; ch < ND; ch++) acc[ch] = 0.f;
-#pragma unroll
-    for (int kz = 0; kz < (ND == 3 ? 2 : 1); kz++)
-#pragma unroll
-        for (int ky = 0; ky < 2; ky++)
-#pragma unroll
-            for (int kx = 0; kx < 2; kx++) {
-                float w = (ky ? t[1] : 1.f - t[1]) * (kx ? t[2] : 1.f - t[2]);
-                if constexpr (ND == 3) w *= kz ? t[0] : 1.f - t[0];
-                const size_t off = ((size_t)c[0][kz] * H + c[1][ky]) * W + c[2][kx];
-#pragma unroll
-                for (int ch = 0; ch < ND; ch++) acc[ch] = fmaf(w, f[(size_t)ch * N + off], acc[ch]);
-            }
-}
 
 // c(x) = second(x) + S(first, x + second(x)); pairs along blockIdx.y.  second and out may be the same buffer: no __restrict__ on them.
 template <int ND, int PAD>
@@ -76,23 +39,9 @@ __global__ __launch_bounds__(TRX_BLOCK) void flow_compose_kernel(const float *__
 #pragma unroll
     for (int c = 0; c < ND; c++) ux[c] = s[(size_t)c * N + i];
     if constexpr (PAD == 0) {      // svf_square_kernel's body with two fields
-#pragma unroll
-        for (int c = 0; c < ND; c++) acc[c] = 0.f;
         SvfAxis ax[3];
         svf_axes<ND>(x, ux, D, H, W, ax);
-#pragma unroll
-        for (int kz = 0; kz < (ND == 3 ? 2 : 1); kz++)
-#pragma unroll
-            for (int ky = 0; ky < 2; ky++)
-#pragma unroll
-                for (int kx = 0; kx < 2; kx++) {
-                    const bool ok = ax[0].ok[kz] & ax[1].ok[ky] & ax[2].ok[kx];
-                    float w = (ky ? ax[1].t : 1.f - ax[1].t) * (kx ? ax[2].t : 1.f - ax[2].t);
-                    if constexpr (ND == 3) w *= kz ? ax[0].t : 1.f - ax[0].t;
-                    const size_t off = ((size_t)ax[0].c[kz] * H + ax[1].c[ky]) * W + ax[2].c[kx];
-#pragma unroll
-                    for (int c = 0; c < ND; c++) acc[c] = fmaf(w, ok ? u[(size_t)c * N + off] : 0.f, acc[c]);
-                }
+        flo_sample_zeros_axes<ND>(u, N, H, W, ax, acc);
     } else {
         flo_sample_border<ND>(u, N, D, H, W, x, ux, acc);
     }

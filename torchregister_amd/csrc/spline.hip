@@ -25,6 +25,7 @@
 #include <cstdint>
 
 #include "affine_host.h"
+#include "spline_sample.h"
 
 namespace trx {
 
@@ -36,16 +37,6 @@ constexpr int kSplRun = 8;                    // the y and z passes: consecutive
 struct SplTaps {
     float h[kSplReach + 1];
 };
-
-// whole-sample mirror of any index into 0 .. n-1
-__device__ __forceinline__ int spl_mirror(long long k, int n)
-{
-    if ((unsigned long long)k < (unsigned long long)n) return (int)k;
-    if (n == 1) return 0;
-    const long long top = 2LL * (n - 1);
-    while (k < 0 || k >= n) k = k < 0 ? -k : top - k;
-    return (int)k;
-}
 
 // The x pass.  src / dst: N volumes of `rows` lines of W voxels, vol_stride elements apart.  W == 1: a copy (an axis of one voxel is left alone).
 __global__ __launch_bounds__(kSplTile * kSplRows) void spl_x_kernel(const float *__restrict__ src, float *__restrict__ dst, int rows, int W, size_t vol_stride,
@@ -110,37 +101,6 @@ __global__ __launch_bounds__(TRX_BLOCK) void spl_axis_kernel(const float *__rest
     }
 }
 
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));   // a 4-byte aligned quad: one global_load_dwordx4 at any voxel
-
-// The tensor-product sum of one channel over the 4^ND taps: x innermost, then y, then z.  RUN: the x taps are idx[0][0] .. idx[0][0] + 3.
-template <int ND, bool RUN>
-__device__ __forceinline__ float spl_taps(const float *__restrict__ m, const int (&idx)[ND][4], const float (&w)[ND][4], int H, int W)
-{
-    float acc = 0.f;
-#pragma unroll
-    for (int kz = 0; kz < (ND == 3 ? 4 : 1); kz++) {
-        float az = 0.f;
-#pragma unroll
-        for (int ky = 0; ky < 4; ky++) {
-            const float *__restrict__ r = m + ((size_t)(ND == 3 ? idx[ND - 1][kz] : 0) * H + idx[1][ky]) * W;
-            float c[4];
-            if constexpr (RUN) {
-                const f4u q = *(const f4u *)(r + idx[0][0]);
-                c[0] = q.x; c[1] = q.y; c[2] = q.z; c[3] = q.w;
-            } else {
-#pragma unroll
-                for (int kx = 0; kx < 4; kx++) c[kx] = r[idx[0][kx]];
-            }
-            float ax = w[0][0] * c[0];
-#pragma unroll
-            for (int kx = 1; kx < 4; kx++) ax = fmaf(w[0][kx], c[kx], ax);
-            az = fmaf(w[1][ky], ax, az);
-        }
-        acc = ND == 3 ? fmaf(w[ND - 1][kz], az, acc) : az;
-    }
-    return acc;
-}
-
 // mg: the SAMPLED lattice and the scales (the host fills in the target's own and ones where the caller gave none).  chan_stride: sampled voxels
 // between channels.  theta NULL: the flow-only chain; flow NULL: zero flow.
 template <int ND, int ORDER>
@@ -176,45 +136,7 @@ __global__ __launch_bounds__(TRX_BLOCK) void transform_resample_kernel(trx_volum
     }
     float *__restrict__ o = out + (size_t)b * channels * nvox + i;
 
-    if constexpr (ORDER == 0) {
-        bool in = true;
-        size_t src = 0;
-#pragma unroll
-        for (int a = ND - 1; a >= 0; a--) {
-            const float r = rintf(ic[a]);
-            in = in && (r >= 0.f) && (r < (float)S[a]);      // NaN compares false: zeros
-            src = src * (size_t)S[a] + (size_t)(in ? (int)r : 0);
-        }
-        for (int ch = 0; ch < channels; ch++) __builtin_nontemporal_store(in ? mov[ch * chan_stride + src] : 0.f, o + ch * nvox);
-    } else {
-        bool in = true;
-#pragma unroll
-        for (int a = 0; a < ND; a++) in = in && (ic[a] >= -0.5f) && (ic[a] <= (float)S[a] - 0.5f);      // NaN: outside
-        if (!in) {
-            for (int ch = 0; ch < channels; ch++) __builtin_nontemporal_store(0.f, o + ch * nvox);
-            return;
-        }
-        float w[ND][4];
-        int idx[ND][4];
-#pragma unroll
-        for (int a = 0; a < ND; a++) {
-            const float fl = floorf(ic[a]);
-            const float r = ic[a] - fl, r2 = r * r, r3 = r2 * r, u = 1.f - r;
-            const int i0 = (int)fl;                          // -1 .. S - 1 inside the field of view
-            w[a][0] = u * u * u * (1.f / 6.f);
-            w[a][1] = (3.f * r3 - 6.f * r2 + 4.f) * (1.f / 6.f);
-            w[a][2] = (-3.f * r3 + 3.f * r2 + 3.f * r + 1.f) * (1.f / 6.f);
-            w[a][3] = r3 * (1.f / 6.f);
-#pragma unroll
-            for (int k = 0; k < 4; k++) idx[a][k] = spl_mirror((long long)i0 - 1 + k, S[a]);
-        }
-        const bool run = idx[0][3] - idx[0][0] == 3;      // the four x taps are neighbours in memory (no mirror along x): one 16-byte load per row
-        for (int ch = 0; ch < channels; ch++) {
-            const float *__restrict__ m = mov + ch * chan_stride;
-            const float acc = run ? spl_taps<ND, true>(m, idx, w, S[1], S[0]) : spl_taps<ND, false>(m, idx, w, S[1], S[0]);
-            __builtin_nontemporal_store(acc, o + ch * nvox);
-        }
-    }
+    spl_sample_store<ND, ORDER>(mov, chan_stride, channels, ic, S, o, nvox);
 }
 
 // what both coefficient entry points refuse about a geometry

@@ -41,15 +41,24 @@ template <int ND> __device__ __forceinline__ void svf_coords(unsigned i, int H, 
     }
 }
 
-// The axes of the sample at voxel x displaced by u (channel order of `flow`: 3-D z, y, x; 2-D y, x), in slots 3 - ND .. 2
-template <int ND> __device__ __forceinline__ void svf_axes(const int (&x)[3], const float (&u)[ND], int D, int H, int W, SvfAxis (&ax)[3])
+// The axes of the sample at the float position p (channel order of `flow`: 3-D z, y, x; 2-D y, x), in slots 3 - ND .. 2
+template <int ND> __device__ __forceinline__ void svf_axes_at(const float (&p)[ND], int D, int H, int W, SvfAxis (&ax)[3])
 {
     const int S[3] = {D, H, W};
     if constexpr (ND == 2) {
         ax[0].i0 = 0; ax[0].c[0] = ax[0].c[1] = 0; ax[0].ok[0] = true; ax[0].ok[1] = false; ax[0].t = 0.f;
     }
 #pragma unroll
-    for (int a = 3 - ND; a < 3; a++) ax[a] = svf_axis((float)x[a] + u[a - (3 - ND)], S[a]);
+    for (int a = 3 - ND; a < 3; a++) ax[a] = svf_axis(p[a - (3 - ND)], S[a]);
+}
+
+// ... at voxel x displaced by u: the position is ONE fp32 add per axis
+template <int ND> __device__ __forceinline__ void svf_axes(const int (&x)[3], const float (&u)[ND], int D, int H, int W, SvfAxis (&ax)[3])
+{
+    float p[ND];
+#pragma unroll
+    for (int a = 3 - ND; a < 3; a++) p[a - (3 - ND)] = (float)x[a] + u[a - (3 - ND)];
+    svf_axes_at<ND>(p, D, H, W, ax);
 }
 
 }  // namespace trx

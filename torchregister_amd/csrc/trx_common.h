@@ -209,14 +209,17 @@ __device__ __forceinline__ void affine_coord(const float *__restrict__ th, float
 // The composed warp's sample coordinate (x, y, z order) of the target voxel at (x, y, z) displaced by f (the flow's channel order: z, y, x; 2-D: y, x):
 // the closed-form base coordinate at the non-integer position, then affine_coord with the MOVING sizes.  One statement for trx_affine_flow_warp, its
 // backward and trx_transform_resample, which are checked against each other.
+// n = (2 p + 1) / S - 1: the closed form of affine_grid's base coordinate at a float voxel position p of an axis of S voxels
+__device__ __forceinline__ float af_norm(float p, int S) { return fmaf(2.0f, p, 1.0f) / (float)S - 1.0f; }
+
 template <int ND>
 __device__ __forceinline__ void af_coord(const float (&te)[ND * (ND + 1)], const float (&f)[ND], int x, int y, int z, int D, int H, int W, int Dm, int Hm,
                                          int Wm, float (&ic)[ND])
 {
-    const float xn = fmaf(2.0f, (float)x + f[ND - 1], 1.0f) / (float)W - 1.0f;
-    const float yn = fmaf(2.0f, (float)y + f[ND - 2], 1.0f) / (float)H - 1.0f;
+    const float xn = af_norm((float)x + f[ND - 1], W);
+    const float yn = af_norm((float)y + f[ND - 2], H);
     float zn = 0.f;
-    if constexpr (ND == 3) zn = fmaf(2.0f, (float)z + f[0], 1.0f) / (float)D - 1.0f;
+    if constexpr (ND == 3) zn = af_norm((float)z + f[0], D);
     affine_coord<ND>(te, xn, yn, zn, Dm, Hm, Wm, ic);
 }
 

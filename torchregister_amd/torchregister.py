@@ -9,7 +9,7 @@ U-Net-generated flow, 'direct' = the flow field itself is the parameter), levels
 import torch
 from torch import cat
 
-from ._engine import _bending_weight, _folding_threshold, _folding_weight, _invert_args, invert_flow, jacobian_determinant, _mask_u8, _squarings, affine_warp, check_interpolation, grid_scale, overlap_args, resample, world_setup
+from ._engine import _bending_weight, _folding_threshold, _folding_weight, _invert_args, invert_flow, invert_theta, jacobian_determinant, resample_affine_then_flow, transform_points, _mask_u8, _squarings, affine_warp, check_interpolation, grid_scale, overlap_args, resample, world_setup
 from .pyramid import level_theta, pyramid, pyramid_masks, pyramid_shapes, upsample_flow
 from .warpings import (GRIDS_SUPPORT, INITIAL_SUPPORT, MASK_SUPPORT, OVERLAP_SUPPORT, WORLD_SUPPORT, affine_register, device_loop_settings, flow_register, get_affine_warp, resolve_initial, rigid_register,
                        two_lattices)
@@ -138,6 +138,7 @@ class Register():
         self.world_init = None      # optim(moving_affine=, target_affine=): T0 [B,nd+1,nd+1] fp64, the fixed world transform in front of what was optimised
         self.world_center = None    # ... and c [B,nd] fp64, the centre (world mm) theta acted about; world_matrix is then T0 Tr(c) Theta Tr(-c)
         self.target_shape = None    # the spatial shape of the lattice optim registered onto: what reg(x) returns
+        self.moving_shape = None    # the spatial shape of the moving image optim ran on (the finest level's): what to_moving(x) returns
         self.initial = None         # optim(initial=...): the effective theta [B,nd,nd+1] the deformation is composed with
         self.valid_fraction = None  # optim(overlap=True / moving_mask=...): [B], N_valid / (target-mask voxels or N) at the returned transform
 
@@ -278,6 +279,7 @@ class Register():
         '''
         self.valid_fraction = None
         overlap, moving_mask = self._check_overlap(overlap, moving_mask, moving, initial)
+        self.moving_shape = tuple(moving.shape[2:])
         headers = moving_affine is not None or target_affine is not None or world_init is not None
         if initial is not None:
             if headers:
@@ -440,7 +442,8 @@ class Register():
         fixed-point iteration of invert_flow, and each voxel's last update [B,1,x,y(,z)] - a voxel has converged exactly when residual <= tol; where
         the deformation folds (reg.jacobian() <= 0) it has no inverse and residual says so.  resample(labels_on_target, flow=v,
         interpolation='nearest') carries a label map from the target back onto the moving image.  Not with optim(initial=...): the whole
-        transform's inverse lives on the moving lattice and is not built.  diffeomorphic=True has .inverse_flow, the exponential of -velocity.
+        transform's inverse lives on the moving lattice - to_moving(x), transform_points(p, inverse=True) and inverse_transform() build it.
+        diffeomorphic=True has .inverse_flow, the exponential of -velocity.
         '''
         iterations, tol = _invert_args(iterations, tol)
         if self.mode != 'flow':
@@ -450,6 +453,69 @@ class Register():
         if self.initial is not None:
             raise ValueError("invert_flow() is not built for optim(initial=...): the inverse of the whole transform lives on the moving lattice")
         return invert_flow(self.theta, iterations, tol, return_residual=True)
+
+    def _whole_transform(self):
+        '''(effective theta or None, flow or None, target lattice, moving lattice) of the transform optim found: T(p) = theta(p + flow(p)) takes
+        target-lattice voxels to moving-lattice voxels (theta between the normalised cubes; a missing piece is the identity).'''
+        if self.theta is None:
+            raise RuntimeError("call optim() first")
+        if self.mode == 'flow':
+            flow = self.theta.detach()
+            lattice = tuple(flow.shape[2:])
+            return (None if self.initial is None else self.initial.detach()), flow, lattice, (self.moving_shape or lattice)
+        lattice = self.target_shape or self.moving_shape
+        return self.theta.detach(), None, lattice, (self.moving_shape or lattice)
+
+    def inverse_transform(self, iterations=30, tol=1e-3):
+        '''
+        (theta_inv, flow_inv, residual): the pieces of the inverse of the whole transform, moving-lattice voxels to target-lattice voxels,
+        T^-1(q) = r + flow_inv(r) with r = theta_inv q (chain 'affine_then_flow' of transform_points / resample_affine_then_flow).  theta_inv is
+        invert_theta of reg.theta (mode 'rigid' / 'affine') or of .initial (None without one), fp64; flow_inv [B,nd,x,y(,z)] on the target lattice is
+        invert_flow(reg.theta, iterations, tol) with each voxel's last update in residual [B,1,x,y(,z)] - or .inverse_flow, the exponential of
+        -velocity, under diffeomorphic=True (residual None); both None for mode 'rigid' / 'affine'.  For callers who keep the pieces:
+        transform_points(inverse=True) and to_moving() build them on every call.
+        '''
+        iterations, tol = _invert_args(iterations, tol)
+        theta, flow, _, _ = self._whole_transform()
+        theta_inv = None if theta is None else invert_theta(theta)
+        if flow is None:
+            return theta_inv, None, None
+        if self.inverse_flow is not None:
+            return theta_inv, self.inverse_flow.detach(), None
+        flow_inv, residual = invert_flow(flow, iterations, tol, return_residual=True)
+        return theta_inv, flow_inv, residual
+
+    def transform_points(self, points, inverse=False, iterations=30, tol=1e-3):
+        '''
+        Points [B,P,nd] or [P,nd] (fp32, GPU; voxel positions in the tensor's axis order) through the transform optim found (transform_points).
+        inverse=False: target-lattice voxels to moving-lattice voxels, T(p) = theta(p + flow(p)) - reg.theta for 'rigid' / 'affine', the flow for
+        'flow', the flow and then .initial after optim(initial=...).  inverse=True: moving to target through inverse_transform(iterations, tol).
+        With the headers, (points_to_world(reg.transform_points(p), A_moving) - points_to_world(q, A_moving)).norm(dim=-1) is the target
+        registration error in mm of landmarks p (target) and q (moving).
+        '''
+        iterations, tol = _invert_args(iterations, tol)
+        theta, flow, tshape, mshape = self._whole_transform()
+        if not inverse:
+            return transform_points(points, theta=theta, flow=flow, from_shape=tshape, to_shape=mshape, chain='flow_then_affine')
+        theta_inv, flow_inv, _ = self.inverse_transform(iterations, tol)
+        return transform_points(points, theta=theta_inv, flow=flow_inv, from_shape=mshape, to_shape=tshape, chain='affine_then_flow')
+
+    def to_moving(self, x, interpolation='linear', iterations=30, tol=1e-3):
+        '''
+        x [B,c,*target lattice] carried onto the moving lattice (.moving_shape) through the inverse of the whole transform - a label map drawn on
+        the target back onto the moving image with interpolation='nearest'.  'rigid' / 'affine': resample with invert_theta(reg.theta); 'flow':
+        resample with the inverted flow; 'flow' after optim(initial=...): resample_affine_then_flow, the inverse affine first and then the inverted
+        flow on the target lattice, one interpolation.  The inverted flow is inverse_transform(iterations, tol)'s.
+        '''
+        check_interpolation(interpolation)
+        iterations, tol = _invert_args(iterations, tol)
+        _, _, _, mshape = self._whole_transform()
+        theta_inv, flow_inv, _ = self.inverse_transform(iterations, tol)
+        if flow_inv is None:
+            return resample(x, theta=theta_inv.to(torch.float32), size=mshape, interpolation=interpolation)
+        if theta_inv is None:
+            return resample(x, flow=flow_inv, interpolation=interpolation)
+        return resample_affine_then_flow(x, theta=theta_inv, flow=flow_inv, size=mshape, interpolation=interpolation)
 
     def inverse(self, x, interpolation='linear'):
         '''
