@@ -69,7 +69,9 @@ extern "C" {
  *        Later addition under the same number: trx_flow_compose, trx_flow_invert (composition of two dense flows and the fixed-point inverse of one) -
  *        new entry points only.
  *        Later addition under the same number: trx_transform_points, trx_affine_then_flow_resample (points and target-space images through the whole
- *        transform, in both chain orders) - new entry points only. */
+ *        transform, in both chain orders) - new entry points only.
+ *        Later addition under the same number: trx_affine_workspace_carry_offset (diagnostics: where the carry buffers of trx_affine_run's one-launch
+ *        iterations sit in the workspace) - one new host-only entry point, no device code, no existing signature or struct changed. */
 #define TRX_VERSION 240
 #define TRX_PSTRIDE 12  /* floats per pair in theta / param / adam / best_theta arrays */
 
@@ -181,6 +183,12 @@ size_t trx_affine_workspace_bytes(const trx_volumes *vol /*[host]*/);
  * launch wrote for each pair.  The step kernels pick a kernel body per pair from theta (tile geometry / z-streaming) and each body has its
  * own row count, so this tells a test or a profiler which body ran; the step's own reduction reads the same array. */
 size_t trx_affine_workspace_rows_offset(const trx_volumes *vol /*[host]*/);
+
+/* Diagnostics: byte offset, inside the affine workspace, of the two carry buffers float[2][B][64] that the one-launch iterations of
+ * trx_affine_run alternate between (per pair theta[12] | param[12] | Adam m[12] | Adam v[12] | step (int) | 15 unused floats).  Nothing else writes
+ * them, so a test that fills them with a sentinel before a run reads afterwards whether the run took the one-launch form.  0 for a refused
+ * volume and for 2-D (the form does not exist there).  No device work. */
+size_t trx_affine_workspace_carry_offset(const trx_volumes *vol /*[host]*/);
 
 /* [host] 1 if a step of this batch at the given thetas (HOST memory, [B][TRX_PSTRIDE]) would run entirely on the z-streaming kernel's tiles - the
  * test that kernel evaluates per pair on the device - i.e. if TRX_FLAG_ONE_KERNEL costs nothing at these poses; 0 otherwise (also for 2-D and

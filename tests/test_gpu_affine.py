@@ -299,7 +299,7 @@ def test_graph_capture_and_side_stream(eng):
         s.run(4)                       # eager, on a side stream
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, stream=side):
-            s.run(4)                   # captured: 8 kernel nodes, nothing executes yet
+            s.run(4)                   # captured: 5 kernel nodes (the carry form: 4 step launches + the flush; 8 under TRX_FLAG_NO_CARRY), nothing executes yet
         g.replay()
         g.replay()
     side.synchronize()

@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 import torch
 
+import carry_ref as cr
 import traj_workers as tw
 from conftest import bar
 
@@ -112,8 +113,11 @@ def test_cfg2_affine_ncc_128_200_iterations(eng, refs, optimizer, zs):
     th0 = torch.from_numpy(tw.theta0_np(seed=0))
     s = eng.AffineSolver(mov.cuda(), tgt.cuda(), mode="affine", loss=eng.LossSpec(w_ncc=1.0), optimizer=optimizer, lr=lr, init=th0[None], capacity=iters,
                          flags=_lib.FLAG_ZSTREAM if zs else _lib.FLAG_NO_ZSTREAM)
+    cr.fill_sentinel(s)
     s.run(iters)
     torch.cuda.synchronize()
+    if not zs:   # "tiles" is the carry form of trx_affine_run (one launch per iteration): observed, not assumed (tests/carry_ref.py)
+        assert cr.carry_ran(s, 0, iters)
     r32, r64 = refs[("cfg2", optimizer, "float32")], refs[("cfg2", optimizer, "float64")]
     check_affine(s.losses[0].cpu().numpy().astype(np.float64), s.theta[0, :12].cpu().numpy().reshape(3, 4), r32, r64, (optimizer, zs))
     # best = first strict minimum of the recorded curve, theta of that forward (ref:warpings.py:85-93)

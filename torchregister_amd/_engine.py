@@ -290,6 +290,18 @@ class AffineSolver(_AffineParams):
         v = self._rows_notes()
         return [self.BODIES.get(int(x), "?") for x in ((v.abs() >> 24) & 15).tolist()]
 
+    CARRY_STRIDE, CARRY_THETA, CARRY_PARAM, CARRY_M, CARRY_V, CARRY_STEP = 64, 0, 12, 24, 36, 48   # csrc/affine_finalize.h: kCarryStride and the record's fields
+
+    def carry_state(self):
+        """The two carry buffers of trx_affine_run's one-launch iterations, viewed from the workspace (no copy, no sync): a pair of [B, 64] float
+        tensors - per pair theta[12] | param[12] | Adam m[12] | Adam v[12] | step (int bits) | 15 unused floats.  Only launches of the carry form write
+        them; 3-D only.  Diagnostics / tests."""
+        off = int(self.lib.trx_affine_workspace_carry_offset(ctypes.byref(self.vol)))
+        if off == 0:
+            raise _lib.TrxError("this batch has no carry buffers (trx_affine_workspace_carry_offset: 2-D or a refused volume)")
+        n = 4 * self.batch.B * self.CARRY_STRIDE
+        return tuple(self.workspace[off + k * n:off + (k + 1) * n].view(torch.float32).view(self.batch.B, self.CARRY_STRIDE) for k in (0, 1))
+
     def accumulate_only(self, walk_down=False):
         """Launch only the streaming F1 kernel (partials into the workspace); used for kernel timing.  walk_down: this launch walks the
         z-streaming columns downward (TRX_FLAG_WALK_DOWN) - what every second iteration of run() does."""

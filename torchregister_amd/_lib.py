@@ -94,6 +94,7 @@ SIGNATURES = {
     "trx_status_string": (ctypes.c_char_p, [ctypes.c_int]),
     "trx_affine_workspace_bytes": (ctypes.c_size_t, [ctypes.POINTER(Volumes)]),
     "trx_affine_workspace_rows_offset": (ctypes.c_size_t, [ctypes.POINTER(Volumes)]),
+    "trx_affine_workspace_carry_offset": (ctypes.c_size_t, [ctypes.POINTER(Volumes)]),
     "trx_affine_near_identity": (ctypes.c_int, [ctypes.POINTER(Volumes), _P]),
     "trx_affine_step": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(LossCfg), ctypes.POINTER(OptCfg),
                                        ctypes.POINTER(AffineState), _P, ctypes.c_size_t, _P]),

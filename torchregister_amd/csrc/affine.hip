@@ -940,6 +940,12 @@ extern "C" size_t trx_affine_workspace_rows_offset(const trx_volumes *vol)
     return affine_ws(*vol).off_rows_used;
 }
 
+extern "C" size_t trx_affine_workspace_carry_offset(const trx_volumes *vol)
+{
+    if (check_vol(vol, false) != TRX_OK || vol->ndim != 3) return 0;
+    return affine_ws(*vol).off_carry;
+}
+
 // [host] Would a step of this batch run entirely on the z-streaming kernel's two tiles at these (HOST) thetas?  The same test the kernel
 // evaluates per pair on the device (zs_nsub), for callers that decide about TRX_FLAG_ONE_KERNEL from values they hold on the host.
 extern "C" int trx_affine_near_identity(const trx_volumes *vol, const float *theta_host)

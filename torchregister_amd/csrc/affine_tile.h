@@ -180,7 +180,13 @@ constexpr int kTileThreads = GeomA::Threads;   // block size of the primary kern
 __device__ __forceinline__ int trx_lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 __device__ __forceinline__ int trx_wave_index() { return __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6); }
 
-template <int NV, int NW>
+// F64 = false: the 64 lane partials of a wave, then the NW wave sums, are summed in one fp32 chain each (the z-streaming and exact-footprint kernels:
+// they run only in launches of hundreds of blocks, whose rows the finalise sums in fp64, so the chains' errors average out).
+// F64 = true (the tile bodies, the only step kernels a small volume runs): fp64 accumulators in eight independent chains, the wave sums handed over
+// as a float pair (hi + lo), so that only the threads' own sums and one rounding of the row are fp32.  Where a volume is ONE block the fp64 row
+// sums behind this have nothing to average: 8 x 16 x 32 at NCC = 0.99 had its loss off by 2.8e-5 with the fp32 chains, 8.6e-6 with these
+// (tests/test_gpu_carry.py [one-tile]).  Cost and the A/B against the fp32 chains: DESIGN.md 4.1f (3).
+template <int NV, int NW, bool F64 = false>
 __device__ __forceinline__ void block_reduce_store_nw(const float (&vals)[NV], float *__restrict__ out, float *smem, int wave)
 {
     // smem: >= NW*16*65 + NW*16 floats of scratch (aliases the tile box); wave: this wave's index in the block (uniform)
@@ -195,17 +201,36 @@ __device__ __forceinline__ void block_reduce_store_nw(const float (&vals)[NV], f
             if (c0 + j < NV) red[wave][j][lane] = vals[c0 + j];
         __syncthreads();
         if (lane < CH && c0 + lane < NV) {
-            float s = 0.f;
+            if constexpr (F64) {
+                double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};   // (one chain of 64 fp64 adds: measured +1 us per block)
+#pragma unroll
+                for (int i = 0; i < 64; i += 8)
+#pragma unroll
+                    for (int k = 0; k < 8; k++) a[k] += (double)red[wave][lane][i + k];
+                const double s = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+                const float hi = (float)s;
+                wsum[wave][lane] = hi;
+                red[wave][lane][64] = (float)(s - (double)hi);   // (column 64 of a row: the padding of the 65-float pitch, read by nobody else)
+            } else {
+                float s = 0.f;
 #pragma unroll 16
-            for (int i = 0; i < 64; i++) s += red[wave][lane][i];
-            wsum[wave][lane] = s;
+                for (int i = 0; i < 64; i++) s += red[wave][lane][i];
+                wsum[wave][lane] = s;
+            }
         }
         __syncthreads();
         if (tid < CH && c0 + tid < NV) {
-            float s = 0.f;
+            if constexpr (F64) {
+                double hi = 0.0, lo = 0.0;
 #pragma unroll
-            for (int w = 0; w < NW; w++) s += wsum[w][tid];
-            out[c0 + tid] = s;
+                for (int w = 0; w < NW; w++) { hi += (double)wsum[w][tid]; lo += (double)red[w][tid][64]; }
+                out[c0 + tid] = (float)(hi + lo);
+            } else {
+                float s = 0.f;
+#pragma unroll
+                for (int w = 0; w < NW; w++) s += wsum[w][tid];
+                out[c0 + tid] = s;
+            }
         }
         __syncthreads();
     }
@@ -918,6 +943,6 @@ __device__ __forceinline__ void tile_body(const trx_volumes &vol, const float *_
             const float a = acc.AB[q][c].x;
             vals[o++] = xn * a; vals[o++] = acc.AB[q][c].y; vals[o++] = zn * a; vals[o++] = a;
         }
-    block_reduce_store_nw<NP, kTileWaves>(vals, partials + ((size_t)by * rows_stride + bx) * NP, box, wave);
+    block_reduce_store_nw<NP, kTileWaves, true>(vals, partials + ((size_t)by * rows_stride + bx) * NP, box, wave);
 }
 #pragma clang diagnostic pop
