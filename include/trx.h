@@ -71,7 +71,9 @@ extern "C" {
  *        Later addition under the same number: trx_transform_points, trx_affine_then_flow_resample (points and target-space images through the whole
  *        transform, in both chain orders) - new entry points only.
  *        Later addition under the same number: trx_affine_workspace_carry_offset (diagnostics: where the carry buffers of trx_affine_run's one-launch
- *        iterations sit in the workspace) - one new host-only entry point, no device code, no existing signature or struct changed. */
+ *        iterations sit in the workspace) - one new host-only entry point, no device code, no existing signature or struct changed.
+ *        Later addition under the same number: trx_image_moments2 and its workspace query (the second intensity moments behind the principal-axes
+ *        initialiser) - new entry points only. */
 #define TRX_VERSION 240
 #define TRX_PSTRIDE 12  /* floats per pair in theta / param / adam / best_theta arrays */
 
@@ -707,6 +709,18 @@ int trx_affine_world_theta(const trx_moving_grid *mg /*[host]*/, int ndim, int B
 size_t trx_image_moments_workspace_bytes(int ndim, int N, int D, int H, int W);
 int trx_image_moments(const float *x, const unsigned char *mask /*nullable*/, const float *offset /*nullable*/, int ndim, int N, int D, int H, int W,
                       double *out /*[N][1 + ndim]*/, void *workspace, size_t workspace_bytes, void *stream);
+/* The same with the second moments (the principal-axes initialiser of DESIGN.md section 4.21).  Later addition under TRX_VERSION 240.
+ * out [N][ncol] fp64, ncol = 1 + ndim + ndim (ndim + 1) / 2:
+ *   3-D  sum w, sum w x, sum w y, sum w z, sum w xx, sum w xy, sum w yy, sum w xz, sum w yz, sum w zz
+ *   2-D  sum w, sum w x, sum w y, sum w xx, sum w xy, sum w yy
+ * w, x, y, z as above; a product of two indices is formed in fp64, where it is exact, and enters by one fma like a first moment.  The reduction is
+ * trx_image_moments' own (the kernel body is shared, a template on the order): the first 1 + ndim columns are its bits on the same input, the same
+ * bits on every call, a volume's sums do not depend on N.  Ten fp64 accumulators per thread instead of four; the traffic is the same.  Workspace:
+ * trx_image_moments2_workspace_bytes (partial rows of ten doubles; 0 = arguments rejected, as above).  Refusals before any HIP call: those of
+ * trx_image_moments. */
+size_t trx_image_moments2_workspace_bytes(int ndim, int N, int D, int H, int W);
+int trx_image_moments2(const float *x, const unsigned char *mask /*nullable*/, const float *offset /*nullable*/, int ndim, int N, int D, int H, int W,
+                       double *out /*[N][ncol]*/, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- A deformation composed with an initial affine, sampled ONCE (what elastix, NiftyReg and ANTs do with the transform of the
  * stage before).  Extension.  Later addition under TRX_VERSION 240.  vol describes the TARGET lattice S_t = (D, H, W); vol->moving holds

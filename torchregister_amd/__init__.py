@@ -10,7 +10,8 @@ from ._engine import (AffineMISolver, AffineSolver, BSplineSolver, FlowSolver, L
                       folding_penalty, folding_penalty_grad, jacobian_determinant, compose_flows, invert_flow,
                       invert_theta, points_from_world, points_to_world, resample_affine_then_flow, transform_points,
                       affine_flow_valid, affine_flow_warp, affine_flow_warp_backward, affine_mi_loss_grad, grid_scale, resample, run_slabs_lockstep, spline_coefficients,
-                      WorldGeometry, affine_world_theta, image_moments, theta_from_world, world_from_theta, world_geometry, world_setup)
+                      WorldGeometry, affine_world_theta, image_moments, theta_from_world, world_from_theta, world_geometry, world_setup,
+                      WorldSearch, image_covariance, principal_axes_candidates, rotation_grid, world_search)
 from .pyramid import pyramid, pyramid_shapes, upsample_flow  # noqa: F401
 from .sharding import register_sharded  # noqa: F401
 from .torchregister import Register  # noqa: F401

@@ -1845,6 +1845,7 @@ class WorldGeometry:
     def __init__(self, record, center, init, extent):
         self.record, self.center, self.init, self.extent = record, center, init, extent
         self.B, self.nd = center.shape
+        self.search = None       # world_setup(world_init='principal_axes' / 'search'): the WorldSearch behind init
 
     def __iter__(self):
         return iter((self.record, self.center))
@@ -2011,19 +2012,284 @@ def image_moments(x, mask=None):
     return mass, (out[:, 1:] / mass[:, None]).flip(1)
 
 
-WORLD_INITS = (None, "centers", "moments")
+def image_covariance(x, mask=None):
+    """(mass [B], centre [B, nd], cov [B, nd, nd]) fp64 on the CPU (include/trx.h: trx_image_moments2): x, mask and the weights
+    w = v - the volume's minimum over the counted voxels as image_moments; centre and covariance in voxel indices, the TENSOR's axis order.  The kernel
+    hands out the raw sums; the central moments cov = sum w p p^T / m - c c^T are formed here, on the host, in fp64.  ValueError where image_moments
+    raises it.  Deterministic; reads the result back."""
+    _require_gpu(x, "x")
+    if x.dim() not in (4, 5) or x.shape[1] != 1:
+        raise ValueError(f"expected [B,1,H,W] or [B,1,D,H,W], got {tuple(x.shape)}")
+    lib = _lib.load()
+    vol = x.detach().float().contiguous()
+    B, nd, dev = vol.shape[0], vol.dim() - 2, vol.device
+    D, H, W = _dhw(tuple(vol.shape[2:]))
+    flat = vol.reshape(B, -1)
+    m8 = None
+    if mask is not None:
+        m8 = _mask_u8(mask, vol)
+        if bool((m8.reshape(B, -1).sum(1) == 0).any()):
+            raise ValueError("image_covariance: a mask is empty")
+        offset = torch.where(m8.reshape(B, -1) != 0, flat, torch.full_like(flat, float("inf"))).amin(1).contiguous()
+    else:
+        offset = flat.amin(1).contiguous()
+    ws_bytes = lib.trx_image_moments2_workspace_bytes(nd, B, D, H, W)
+    if ws_bytes == 0:
+        raise _lib.TrxError(f"trx_image_moments2_workspace_bytes rejected {B} x {tuple(vol.shape[2:])}")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(B, 1 + nd + nd * (nd + 1) // 2, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = lib.trx_image_moments2(_lib.ptr(vol), _lib.ptr(m8), _lib.ptr(offset), nd, B, D, H, W, _lib.ptr(out), _lib.ptr(ws), ws_bytes, _lib.current_stream(dev))
+    _lib.check(rc, "trx_image_moments2")
+    return covariance_from_sums(out.cpu(), nd, "image_covariance")
 
 
-def world_setup(moving, target, moving_affine, target_affine, world_init=None, mask=None, moving_mask=None):
+def covariance_from_sums(sums, nd, what="covariance_from_sums"):
+    """trx_image_moments2's rows [B, ncol] (fp64, host) -> (mass [B], centre [B, nd], cov [B, nd, nd]) in the TENSOR's axis order.  The rows are in x, y(, z)
+    order with the products as xx, xy, yy(, xz, yz, zz)."""
+    sums = sums.to("cpu", torch.float64)
+    mass = sums[:, 0]
+    if bool((mass <= 0).any()) or not bool(torch.isfinite(sums).all()):
+        raise ValueError(f"{what}: a volume has no contrast over the counted voxels (or a non-finite voxel)")
+    c = sums[:, 1:1 + nd] / mass[:, None]
+    M2 = torch.zeros(sums.shape[0], nd, nd, dtype=torch.float64)
+    k = 1 + nd
+    for j in range(nd):          # xx | xy yy | xz yz zz: column j of the upper triangle, rows 0 .. j
+        for i in range(j + 1):
+            M2[:, i, j] = M2[:, j, i] = sums[:, k]
+            k += 1
+    cov = M2 / mass[:, None, None] - c[:, :, None] * c[:, None, :]
+    return mass, c.flip(1), cov.flip(1).flip(2)
+
+
+def _sign_matrices(nd):
+    """The 2^nd diagonals of +-1 in the documented order: itertools.product((1, -1), repeat=nd) - the first axis slowest, +1 before -1."""
+    import itertools
+    return [torch.tensor(s, dtype=torch.float64) for s in itertools.product((1.0, -1.0), repeat=nd)]
+
+
+def principal_axes(cov):
+    """(eigenvalues [B, nd] ascending, axes [B, nd, nd] in columns) of symmetric matrices [B, nd, nd]: torch.linalg.eigh, each eigenvector's sign fixed
+    so that its entry of largest magnitude (the first such) is positive - the candidates' order must not depend on LAPACK's choice."""
+    w, V = torch.linalg.eigh(cov.to("cpu", torch.float64))
+    pick = V.abs().argmax(dim=1, keepdim=True)
+    sgn = torch.sign(torch.gather(V, 1, pick))
+    return w, V * torch.where(sgn == 0, torch.ones_like(sgn), sgn)
+
+
+def _about(R, c_t, c_m):
+    """Homogeneous [..., nd+1, nd+1] fp64 of p_m = R (p_t - c_t) + c_m: R [..., nd, nd], the centres [..., nd] broadcasting against it."""
+    nd = R.shape[-1]
+    T = torch.zeros(R.shape[:-2] + (nd + 1, nd + 1), dtype=torch.float64)
+    T[..., :nd, :nd] = R
+    T[..., :nd, nd] = c_m - (R @ c_t[..., None])[..., 0]
+    T[..., nd, nd] = 1.0
+    return T
+
+
+def principal_axes_candidates(cov_m, centre_m, cov_t, centre_t):
+    """The principal-axes candidates T0 [B, K, nd+1, nd+1] fp64 (host) from the two images' WORLD covariances [B, nd, nd]
+    (A[:nd,:nd] C A[:nd,:nd]^T of image_covariance's C) and world centres of mass [B, nd], rows x, y(, z) in mm:
+    T0_k : p_m = R_k (p_t - c_t) + c_m,  R_k = V_m S_k V_t^T, V = principal_axes (eigenvalues ascending, signs fixed), S_k = diag(+-1) with det R_k = +1.
+    K = 4 in 3-D, 2 in 2-D; the order is that of itertools.product((1, -1), repeat=nd) over the diagonal of S, those with det R = -1 left out.
+    No degeneracy threshold: near-equal eigenvalues make the axes meaningless - the mutual information of world_search is what rejects a candidate."""
+    cov_m, cov_t = (torch.as_tensor(c).detach().to("cpu", torch.float64) for c in (cov_m, cov_t))
+    c_m, c_t = (torch.as_tensor(c).detach().to("cpu", torch.float64) for c in (centre_m, centre_t))
+    if cov_m.dim() != 3 or cov_m.shape != cov_t.shape or cov_m.shape[1] not in (2, 3) or cov_m.shape[1] != cov_m.shape[2] or \
+            tuple(c_m.shape) != tuple(cov_m.shape[:2]) or c_t.shape != c_m.shape:
+        raise ValueError(f"expected covariances [B,nd,nd] and centres [B,nd], got {tuple(cov_m.shape)}, {tuple(c_m.shape)}, {tuple(cov_t.shape)}, {tuple(c_t.shape)}")
+    nd = cov_m.shape[1]
+    Vm, Vt = principal_axes(cov_m)[1], principal_axes(cov_t)[1]
+    out = []
+    for b in range(cov_m.shape[0]):
+        Rs = [Vm[b] @ torch.diag(s) @ Vt[b].T for s in _sign_matrices(nd)]
+        Rs = torch.stack([R for R in Rs if float(torch.linalg.det(R)) > 0.0])
+        out.append(_about(Rs, c_t[b], c_m[b]))
+    return torch.stack(out)
+
+
+def rotation_grid(nd, step_deg):
+    """Rotations [C, nd, nd] fp64 on a regular Euler grid.  3-D: Rz(gamma) Ry(beta) Rx(alpha) with alpha, gamma in {-180, -180 + step,
+    ... < 180} and beta in {-90, ..., 90}, C = (360 / step)^2 (180 / step + 1); 2-D: the rotation by gamma alone, C = 360 / step.  The identity is
+    candidate 0; the others follow in the order alpha (slowest), beta, gamma.  Duplicates at beta = +-90 degrees stay.  ValueError unless step divides 90."""
+    step = float(step_deg)
+    if nd not in (2, 3) or not (step > 0.0) or abs(90.0 / step - round(90.0 / step)) > 1e-9:
+        raise ValueError(f"rotation_grid: nd must be 2 or 3 and the step must divide 90 degrees, got nd = {nd}, step = {step_deg}")
+    n = int(round(360.0 / step))
+    full = [-180.0 + step * i for i in range(n)]
+    half = [-90.0 + step * i for i in range(n // 2 + 1)]
+
+    def rot(axis, deg):
+        a = math.radians(deg)
+        c, s = math.cos(a), math.sin(a)
+        if nd == 2:
+            return torch.tensor([[c, -s], [s, c]], dtype=torch.float64)
+        return torch.tensor({0: [[1, 0, 0], [0, c, -s], [0, s, c]], 1: [[c, 0, s], [0, 1, 0], [-s, 0, c]], 2: [[c, -s, 0], [s, c, 0], [0, 0, 1]]}[axis],
+                            dtype=torch.float64)
+    if nd == 2:
+        angles = [(g,) for g in full]
+        mats = [rot(2, g) for g in full]
+    else:
+        angles = [(a, b, g) for a in full for b in half for g in full]
+        mats = [rot(2, g) @ rot(1, b) @ rot(0, a) for a, b, g in angles]
+    first = angles.index((0.0,) * (1 if nd == 2 else 3))
+    mats[first] = torch.eye(nd, dtype=torch.float64)
+    return torch.stack([mats[first]] + mats[:first] + mats[first + 1:])
+
+
+class WorldSearch:
+    """What world_search found, all on the CPU: init [B,nd+1,nd+1] fp64 (the chosen candidate after its refinement, p_moving = init p_target), center [B,nd]
+    (the world point theta acted about), candidates [B,K,nd+1,nd+1], scores [B,K] fp32 (the mutual-information loss of every candidate), kept [B,keep]
+    (indices of the lowest scores, ascending score, ties by index), refined [B,keep] fp32 (their best losses over the refinement), chosen [B] (the
+    candidate index behind init) and eigenvalues (moving [B,nd], target [B,nd]; ascending, mm^2; None for a caller's candidates) - near-equal ones say
+    that the principal axes carried no information."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+SEARCH_CHUNK = 64       # candidates per evaluation call (the batch axis of trx_affine_mi_loss_grad_grids)
+
+
+def world_moments(x, affine, mask=None):
+    """(centre [B,nd], cov [B,nd,nd]) fp64 on the CPU of x [B,1,*spatial] in WORLD mm under its voxel-to-world matrices [nd+1,nd+1] / [B,nd+1,nd+1]:
+    A c + t and A[:nd,:nd] C A[:nd,:nd]^T of image_covariance's centre and covariance."""
+    nd = x.dim() - 2
+    A = _world_affine(affine, nd, "affine", x.shape[0]).expand(x.shape[0], nd + 1, nd + 1)
+    _, ctr, cov = image_covariance(x, mask)
+    lin = A[:, :nd, :nd]
+    return (lin @ ctr[:, :, None])[:, :, 0] + A[:, :nd, nd], lin @ cov @ lin.transpose(1, 2)
+
+
+def world_search(moving, target, moving_affine, target_affine, candidates="principal_axes", mask=None, moving_mask=None, overlap=None, mi=None, step=45.0,
+                 keep=8, iters=30, lr=0.01, optimizer="adam", moments=None):
+    """A rigid starting transform for world-geometry registration when the headers' orientation cannot be trusted: candidates
+    scored by the mutual information of the fused evaluation, the best few refined by the rigid device loop.  Returns a WorldSearch.
+    moving / target [B,1,*spatial] fp32 on the GPU with voxel-to-world matrices as world_geometry takes them; mask / moving_mask / overlap / mi as
+    AffineMISolver.  candidates: 'principal_axes' - the K of principal_axes_candidates from the two images' second moments (image_covariance inside
+    mask / moving_mask); 'search' - those K, then the centre-of-mass alignment composed with every rotation of rotation_grid(nd, step) about the target's
+    centre of mass; or a tensor [K,nd+1,nd+1] / [B,K,nd+1,nd+1] of world transforms p_moving = T0 p_target.  moments: (centre_m, cov_m, centre_t, cov_t)
+    in world mm taken elsewhere (world_setup takes them on the full-resolution images and searches on a coarse level) instead of image_covariance here.
+    Every candidate is scored at theta = identity, loss only, by trx_affine_mi_loss_grad_grids: per pair, the candidates along the batch axis in chunks
+    of SEARCH_CHUNK with image strides 0 - the images are not copied; records, masks and the pair's own intensity ranges are replicated per chunk.  The
+    `keep` lowest are refined together by `iters` iterations of ONE rigid AffineMISolver (each with its own record and theta; optimizer, lr), and
+    init = T0_k Tr(c) Theta_best Tr(-c) of the candidate whose best loss is lowest, c = the target's centre of mass (a caller's candidates: its geometric
+    centre).  iters = 0: the best-scored candidate as it is.  Always rigid."""
+    _require_gpu(moving, "moving")
+    _require_gpu(target, "target")
+    if moving.dim() not in (4, 5) or target.dim() != moving.dim() or moving.shape[1] != 1 or target.shape[1] != 1 or moving.shape[0] != target.shape[0]:
+        raise ValueError(f"expected two [B,1,*spatial] tensors of one batch size, got {tuple(moving.shape)} and {tuple(target.shape)}")
+    ms, ts, nd = _world_shapes(moving.shape[2:], target.shape[2:])
+    B, dev, n1 = target.shape[0], target.device, nd + 1
+    keep, iters = int(keep), int(iters)
+    if keep < 1 or iters < 0:
+        raise ValueError(f"world_search: keep must be at least 1 and iters at least 0, got {keep} and {iters}")
+    Am = _world_affine(moving_affine, nd, "moving_affine", B).expand(B, n1, n1)
+    At = _world_affine(target_affine, nd, "target_affine", B).expand(B, n1, n1)
+    if mask is not None:
+        mask = _mask_u8(mask, target)
+    overlap, moving_mask = overlap_args(overlap, moving_mask, moving)
+    mi = {} if mi is None else dict(mi)
+    eig = None
+    if isinstance(candidates, str):
+        if candidates not in ("principal_axes", "search"):
+            raise ValueError(f"candidates must be 'principal_axes', 'search' or a tensor of world transforms, got {candidates!r}")
+        if moments is None:
+            (cm, Cm), (ct, Ct) = world_moments(moving, Am, moving_mask), world_moments(target, At, mask)
+        else:
+            cm, Cm, ct, Ct = (torch.as_tensor(t).detach().to("cpu", torch.float64) for t in moments)
+        eig = (principal_axes(Cm)[0], principal_axes(Ct)[0])
+        T0 = principal_axes_candidates(Cm, cm, Ct, ct)
+        if candidates == "search":
+            grid = rotation_grid(nd, step)
+            T0 = torch.cat([T0, torch.stack([_about(grid, ct[b], cm[b]) for b in range(B)])], dim=1)
+        center = ct
+    else:
+        T0 = torch.as_tensor(candidates).detach().to("cpu", torch.float64)
+        if T0.dim() == 3:
+            T0 = T0[None].expand(B, *T0.shape)
+        if T0.dim() != 4 or T0.shape[0] != B or T0.shape[1] < 1 or tuple(T0.shape[2:]) != (n1, n1):
+            raise ValueError(f"candidates must be [K,{n1},{n1}] or [{B},K,{n1},{n1}], got {tuple(T0.shape)}")
+        T0 = _world_affine(T0.reshape(-1, n1, n1), nd, "candidates").reshape(B, -1, n1, n1)
+        center = lattice_center(ts, At).expand(B, nd)
+    K = T0.shape[1]
+    keep = min(keep, K)
+    lib = _lib.load()
+    mov, tgt = moving.detach().contiguous(), target.detach().contiguous()
+    tables = base_tables(ts, dev)
+    scores = torch.empty(B, K)
+    kept, refined, chosen, init = torch.empty(B, keep, dtype=torch.long), torch.empty(B, keep), torch.empty(B, dtype=torch.long), torch.empty(B, n1, n1, dtype=torch.float64)
+    for b in range(B):
+        geo = world_geometry(ms, ts, Am[b], At[b], T0[b], center[b])               # K records of one pair
+        mk_b = None if mask is None else mask[b:b + 1]
+        mm_b = None if moving_mask is None else moving_mask[b:b + 1].to(dev)
+        cfg1, rng1, _ = _mi_cfg(mi, tgt[b:b + 1], mov[b:b + 1], mk_b, overlap, mm_b)      # the run's own ranges: fitted once to (target, moving)
+        rec = geo.record.to(dev)
+        for k0 in range(0, K, SEARCH_CHUNK):
+            n = min(SEARCH_CHUNK, K - k0)
+            vol = _volumes(mov[b:b + 1], tgt[b:b + 1], 0, 0, ts, tables=tables)     # strides 0: every candidate reads the same two images
+            vol.B = n
+            rng = rng1.expand(n, 4).contiguous()
+            mk = None if mk_b is None else mk_b.expand(n, *mk_b.shape[1:]).contiguous()
+            mm = None if mm_b is None else mm_b.expand(n, *mm_b.shape[1:]).contiguous()
+            cfg = _mi_cfg_c(cfg1.bins, cfg1.alpha, cfg1.normalized, rng, mk)
+            recs = rec[k0:k0 + n].contiguous()
+            mg = _moving_grid(ms, None, overlap, mm, recs)
+            th = pad_theta(torch.eye(nd, n1, device=dev).repeat(n, 1, 1), nd)
+            ws_bytes = lib.trx_affine_mi_workspace_bytes(ctypes.byref(vol), cfg.bins)
+            if ws_bytes == 0:
+                raise _lib.TrxError(f"trx_affine_mi_workspace_bytes rejected {n} x {ts} with {cfg.bins} bins")
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            loss = torch.empty(n, device=dev)
+            with torch.cuda.device(dev):
+                rc = lib.trx_affine_mi_loss_grad_grids(ctypes.byref(vol), ctypes.byref(mg), ctypes.byref(cfg), _lib.ptr(th), _lib.ptr(loss), None, _lib.ptr(ws),
+                                                       ws_bytes, _lib.current_stream(dev))
+            _lib.check(rc, "trx_affine_mi_loss_grad_grids")
+            scores[b, k0:k0 + n] = loss.cpu()             # (the copy waits for the call: its tensors may go)
+        kept[b] = torch.sort(scores[b], stable=True).indices[:keep]
+        if iters == 0:
+            refined[b], chosen[b], init[b] = scores[b, kept[b]], kept[b, 0], T0[b, kept[b, 0]]
+            continue
+        sub = WorldGeometry(geo.record[kept[b]], geo.center[kept[b]], geo.init[kept[b]], geo.extent[kept[b]])
+        rep = lambda t: None if t is None else t.expand(keep, *t.shape[1:])  # noqa: E731
+        solver = AffineMISolver(rep(mov[b:b + 1]), rep(tgt[b:b + 1]), mode="rigid", mi=mi, optimizer=optimizer, lr=lr, init=torch.zeros(keep, 6 if nd == 3 else 3),
+                                capacity=iters, mask=rep(mk_b), overlap=overlap, moving_mask=rep(mm_b), world=sub)
+        solver.run(iters)
+        refined[b] = solver.best_loss.cpu()
+        j = int(torch.sort(refined[b], stable=True).indices[0])
+        chosen[b], init[b] = kept[b, j], sub.matrix(solver.best)[j]
+    return WorldSearch(init=init, center=center.clone(), candidates=T0, scores=scores, kept=kept, refined=refined, chosen=chosen, eigenvalues=eig)
+
+
+_run_world_search = world_search      # (world_setup and the solvers have a keyword of the same name)
+WORLD_INITS = (None, "centers", "moments", "principal_axes", "search")
+SEARCH_KEYS = ("step", "keep", "iters")
+
+
+def world_setup(moving, target, moving_affine, target_affine, world_init=None, mask=None, moving_mask=None, world_search=None, overlap=None, mi=None,
+                search_on=None):
     """WorldGeometry of a pair of tensors [B,1,*spatial] from their headers and world_init: None (trust the headers: T0 = I, c = the target's geometric
     centre), 'centers' (T0 = the translation between the geometric centres), 'moments' (T0 = the translation between the intensity centres of mass -
-    image_moments inside mask / moving_mask where given - and c = the target's centre of mass) or a world matrix [nd+1, nd+1] / [B, nd+1, nd+1]."""
+    image_moments inside mask / moving_mask where given - and c = the target's centre of mass) or a world matrix [nd+1, nd+1] / [B, nd+1, nd+1].
+    'principal_axes' / 'search' (DESIGN.md section 4.21): T0 = world_search(candidates=world_init).init, c = the target's centre of mass, the record in
+    `.search` of the result.  world_search: dict of step / keep / iters for it; overlap, mi: the run's, handed to it.  The moments are taken on these
+    (full-resolution) images; search_on = (moving, target, mask, moving_mask) are the images the candidates are scored and refined on - the first
+    level of a coarse-to-fine run - and default to the images themselves."""
     ms, ts, nd = _world_shapes(moving.shape[2:], target.shape[2:])
     B = target.shape[0]
     if isinstance(world_init, str) and world_init not in WORLD_INITS:
-        raise ValueError(f"world_init must be None, 'centers', 'moments' or a matrix, got {world_init!r}")
+        raise ValueError(f"world_init must be None, 'centers', 'moments', 'principal_axes', 'search' or a matrix, got {world_init!r}")
+    searching = isinstance(world_init, str) and world_init in ("principal_axes", "search")
+    if world_search is not None and (not searching or not isinstance(world_search, dict) or set(world_search) - set(SEARCH_KEYS)):
+        raise ValueError(f"world_search is a dict of {SEARCH_KEYS} for world_init='principal_axes' / 'search', got {world_search!r} with world_init = {world_init!r}")
     Am, At = _world_affine(moving_affine, nd, "moving_affine", B), _world_affine(target_affine, nd, "target_affine", B)
-    if isinstance(world_init, str) and world_init == "moments":
+    if searching:
+        (cm, Cm), (ct, Ct) = world_moments(moving, Am, moving_mask), world_moments(target, At, mask)
+        lm, lt, lmask, lmmask = (moving, target, mask, moving_mask) if search_on is None else search_on
+        found = _run_world_search(lm, lt, level_affine(Am, ms, tuple(lm.shape[2:])), level_affine(At, ts, tuple(lt.shape[2:])), candidates=world_init, mask=lmask,
+                                  moving_mask=lmmask, overlap=overlap, mi=mi, moments=(cm, Cm, ct, Ct), **(world_search or {}))
+        geo = world_geometry(ms, ts, Am, At, found.init, ct)
+    elif isinstance(world_init, str) and world_init == "moments":
         def com(x, A, m):
             ctr = image_moments(x, m)[1].cpu()                                       # voxel indices, the tensor's axis order: A's columns
             return (A[:, :nd, :nd] @ ctr[:, :, None])[:, :, 0] + A[:, :nd, nd]
@@ -2037,6 +2303,8 @@ def world_setup(moving, target, moving_affine, target_affine, world_init=None, m
         raise ValueError(f"the headers describe {geo.B} pairs, the batch has {B}")
     if geo.B != B:
         geo = WorldGeometry(*(t.expand(B, *t.shape[1:]).contiguous() for t in (geo.record, geo.center, geo.init, geo.extent)))
+    if searching:
+        geo.search = found
     return geo
 
 
@@ -2589,14 +2857,20 @@ class AffineMISolver(_AffineParams):
     or a world matrix; world_setup): world geometry, DESIGN.md section 4.17 - theta acts in world millimetres about a centre behind a fixed
     initial transform, whatever the origins and axis directions of the two headers.  `.world` is the WorldGeometry used (T0 = .world.init, c =
     .world.center), `.world_record` its records on the device (kept alive for the loop); world= takes a prepared WorldGeometry instead (the levels
-    of a pyramid share one).  .effective(theta) then goes through trx_affine_world_theta and .world_matrix(theta) is T."""
+    of a pyramid share one).  .effective(theta) then goes through trx_affine_world_theta and .world_matrix(theta) is T.
+    world_init 'principal_axes' / 'search' (world_search: dict of step / keep / iters): T0 is found by world_search - principal-axes
+    candidates, with 'search' also a grid of rotations, scored by this criterion and refined rigidly - for a pair whose orientation the headers do not
+    give; `.world_search` is its record."""
 
     def __init__(self, moving, target, mode="affine", mi=None, optimizer="sgd", lr=1e-5, init=None, capacity=1000, betas=(0.9, 0.999), eps=1e-8, mask=None,
-                 moving_voxel=None, target_voxel=None, overlap=None, moving_mask=None, moving_affine=None, target_affine=None, world_init=None, world=None):
+                 moving_voxel=None, target_voxel=None, overlap=None, moving_mask=None, moving_affine=None, target_affine=None, world_init=None, world=None,
+                 world_search=None):
         if mask is not None:
             mask = _mask_u8(mask, target)
         self.overlap, moving_mask = overlap_args(overlap, moving_mask, moving)
         headers = moving_affine is not None or target_affine is not None
+        if world_search is not None and not headers:
+            raise ValueError("world_search (the settings of world_init='principal_axes' / 'search') needs moving_affine and target_affine")
         if headers and (moving_affine is None or target_affine is None):
             raise ValueError("moving_affine and target_affine go together: give both voxel-to-world matrices or neither")
         if (headers or world is not None) and (moving_voxel is not None or target_voxel is not None):
@@ -2607,8 +2881,9 @@ class AffineMISolver(_AffineParams):
             raise ValueError("world is the prepared geometry of moving_affine / target_affine / world_init: give one or the other")
         self.lib = _lib.load()
         if headers:      # (its ValueErrors - and, for 'moments', two launches of trx_image_moments - before the solver allocates anything)
-            world = world_setup(moving, target, moving_affine, target_affine, world_init, mask, moving_mask)
+            world = world_setup(moving, target, moving_affine, target_affine, world_init, mask, moving_mask, world_search, self.overlap, mi)
         self.world = world                 # WorldGeometry (host, fp64) or None
+        self.world_search = getattr(world, "search", None)      # world_init='principal_axes' / 'search': the WorldSearch behind world.init
         two = self.overlap or world is not None or moving_voxel is not None or target_voxel is not None or (
             isinstance(moving, torch.Tensor) and isinstance(target, torch.Tensor) and moving.shape[2:] != target.shape[2:])
         self.batch = _GridPair(moving, target, None, moving_voxel, target_voxel) if two else _mi_pair_batch(moving, target)

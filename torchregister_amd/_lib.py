@@ -181,6 +181,8 @@ SIGNATURES = {
     "trx_affine_world_theta": (ctypes.c_int, [ctypes.POINTER(MovingGrid), ctypes.c_int, ctypes.c_int, _P, _P, _P]),
     "trx_image_moments_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
     "trx_image_moments": (ctypes.c_int, [_P, _P, _P] + [ctypes.c_int] * 5 + [_P, _P, ctypes.c_size_t, _P]),
+    "trx_image_moments2_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "trx_image_moments2": (ctypes.c_int, [_P, _P, _P] + [ctypes.c_int] * 5 + [_P, _P, ctypes.c_size_t, _P]),
     "trx_affine_flow_warp": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), _P, _P, ctypes.c_int, _P, _P]),
     "trx_affine_flow_warp_backward": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), _P, _P, ctypes.c_int, _P, _P, _P]),
     "trx_bspline_mi_run_grids": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), _P, ctypes.POINTER(MICfg), ctypes.POINTER(OptCfg),

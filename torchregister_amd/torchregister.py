@@ -9,7 +9,7 @@ U-Net-generated flow, 'direct' = the flow field itself is the parameter), levels
 import torch
 from torch import cat
 
-from ._engine import _bending_weight, _folding_threshold, _folding_weight, _invert_args, invert_flow, invert_theta, jacobian_determinant, resample_affine_then_flow, transform_points, _mask_u8, _squarings, affine_warp, check_interpolation, grid_scale, overlap_args, resample, world_setup
+from ._engine import _bending_weight, _folding_threshold, _folding_weight, _invert_args, invert_flow, invert_theta, jacobian_determinant, resample_affine_then_flow, transform_points, _mask_u8, _squarings, affine_warp, check_interpolation, grid_scale, overlap_args, resample, world_setup, world_geometry, SEARCH_KEYS
 from .pyramid import level_theta, pyramid, pyramid_masks, pyramid_shapes, upsample_flow
 from .warpings import (GRIDS_SUPPORT, INITIAL_SUPPORT, MASK_SUPPORT, OVERLAP_SUPPORT, WORLD_SUPPORT, affine_register, device_loop_settings, flow_register, get_affine_warp, resolve_initial, rigid_register,
                        two_lattices)
@@ -136,6 +136,7 @@ class Register():
         self.level_shapes = None
         self.world_matrix = None    # device_loop with voxel sizes: [B,nd+1,nd+1], the best theta as moving_mm = M target_mm (rows / columns x, y(, z))
         self.world_init = None      # optim(moving_affine=, target_affine=): T0 [B,nd+1,nd+1] fp64, the fixed world transform in front of what was optimised
+        self.world_search = None    # optim(world_init='principal_axes' / 'search'): the WorldSearch record behind world_init (candidates, scores, kept, refined, chosen, eigenvalues)
         self.world_center = None    # ... and c [B,nd] fp64, the centre (world mm) theta acted about; world_matrix is then T0 Tr(c) Theta Tr(-c)
         self.target_shape = None    # the spatial shape of the lattice optim registered onto: what reg(x) returns
         self.moving_shape = None    # the spatial shape of the moving image optim ran on (the finest level's): what to_moving(x) returns
@@ -200,11 +201,12 @@ class Register():
             raise ValueError(OVERLAP_SUPPORT)
         return overlap_args(overlap, moving_mask, moving)
 
-    def _check_world(self, moving, target, moving_affine, target_affine, world_init, moving_voxel, target_voxel, mask, moving_mask):
+    def _check_world(self, moving, target, moving_affine, target_affine, world_init, moving_voxel, target_voxel, mask, moving_mask, overlap=False,
+                     world_search=None):
         '''moving_affine=... / target_affine=... / world_init=... of optim: ValueError unless the loop is the fused mutual-information loop of mode
         'rigid' / 'affine' (device_loop=True) - GRIDS_SUPPORT's rule - and for every malformed header, before any device work (world_init='moments'
         then runs trx_image_moments on each image).  Returns the WorldGeometry, made once from the full-resolution headers, or None.'''
-        if moving_affine is None and target_affine is None and world_init is None:
+        if moving_affine is None and target_affine is None and world_init is None and world_search is None:
             return None
         if self.mode == 'flow' or not self.device_loop or moving.dim() != target.dim():
             raise ValueError(WORLD_SUPPORT)
@@ -212,18 +214,31 @@ class Register():
             raise ValueError("moving_affine and target_affine go together: give both voxel-to-world matrices or neither")
         if moving_voxel is not None or target_voxel is not None:
             raise ValueError("a voxel-to-world matrix carries the voxel sizes: give moving_affine / target_affine or moving_voxel / target_voxel, not both")
-        return world_setup(moving, target, moving_affine, target_affine, world_init, mask, moving_mask)
+        if not (isinstance(world_init, str) and world_init in ('principal_axes', 'search')):
+            return world_setup(moving, target, moving_affine, target_affine, world_init, mask, moving_mask, world_search)
+        # the candidates are scored and refined on the first level the run will use, with the run's own criterion settings
+        mi = device_loop_settings(self.criterion, self.weight)
+        world_geometry(moving.shape[2:], target.shape[2:], moving_affine, target_affine)      # (the headers' ValueErrors, before the pyramid touches the device)
+        if world_search is not None and (not isinstance(world_search, dict) or set(world_search) - set(SEARCH_KEYS)):
+            raise ValueError(f"world_search is a dict of {SEARCH_KEYS}, got {world_search!r}")
+        on = None
+        if self.levels > 1:
+            L = self.levels
+            on = (pyramid(moving, L)[0], pyramid(target, L)[0], None if mask is None else pyramid_masks(mask, L)[0],
+                  None if moving_mask is None else pyramid_masks(moving_mask.to(moving.device), L)[0])
+        return world_setup(moving, target, moving_affine, target_affine, world_init, mask, moving_mask, world_search, overlap, mi, on)
 
     def _set_grids(self, grids, target, info):
         '''After a rigid / affine optim: the warp behind __call__ (two lattices: onto the target lattice, forward only) and the new attributes.'''
         self.target_shape = tuple(target.shape[2:])
         self.world_matrix = info.get('world_matrix')
         self.world_init, self.world_center = info.get('world_init'), info.get('world_center')
+        self.world_search = info.get('world_search')
         size = self.target_shape
         self.warp = (lambda theta, x: affine_warp(theta, x, size=size)) if grids else get_affine_warp
 
     def optim(self, moving, target, lr=1E-5, max_epochs=1000, n=32, per=0.1, *, mask=None, moving_voxel=None, target_voxel=None, initial=None,
-              overlap=None, moving_mask=None, moving_affine=None, target_affine=None, world_init=None):
+              overlap=None, moving_mask=None, moving_affine=None, target_affine=None, world_init=None, world_search=None):
         '''
         Optimisation loop: moving, target [1,1,x,y(,z)] float32 GPU tensors (a leading batch > 1 of
         independent pairs is an extension).  Sets self.theta (best theta [B,nd,nd+1], or the flow
@@ -276,11 +291,19 @@ class Register():
             thetas as with voxel sizes, .world_matrix [B,nd+1,nd+1] fp64 is T = T0 Tr(c) Theta Tr(-c) at the best theta (p_moving = T p_target),
             .world_init and .world_center are T0 and c, .final_pose keeps its meaning; ffd.optim(moving, target, initial=reg) and
             reg(x, interpolation=) work as before - they only ever see the effective theta.
+            world_init='principal_axes' / 'search'  are for a pair whose orientation cannot be trusted - prone against supine, a
+            specimen placed differently, a wrong header: 'principal_axes' takes the four (2-D: two) proper rotations that align the principal axes of the
+            two intensity distributions (second moments inside mask / moving_mask, about the centres of mass), 'search' adds the centre-of-mass
+            alignment composed with a regular grid of rotations; every candidate is scored by the mutual information of this run's criterion, the best
+            few are refined by a short rigid loop, and T0 is the winner, c the target's centre of mass.  Scoring and refinement run on the coarsest level
+            of `levels`.  world_search : dict of step (degrees of the grid, a divisor of 90; 45), keep (candidates refined; 8) and iters (iterations of the
+            refinement; 30).  .world_search holds the record (candidates, scores, kept, refined, chosen, eigenvalues - near-equal eigenvalues mean the
+            principal axes carried no information).  Always rigid, whatever the mode.
         '''
         self.valid_fraction = None
         overlap, moving_mask = self._check_overlap(overlap, moving_mask, moving, initial)
         self.moving_shape = tuple(moving.shape[2:])
-        headers = moving_affine is not None or target_affine is not None or world_init is not None
+        headers = moving_affine is not None or target_affine is not None or world_init is not None or world_search is not None
         if initial is not None:
             if headers:
                 raise ValueError(WORLD_SUPPORT)
@@ -292,7 +315,8 @@ class Register():
         self.initial = initial
         if mask is not None:
             mask = self._check_mask(mask, target)
-        world = self._check_world(moving, target, moving_affine, target_affine, world_init, moving_voxel, target_voxel, mask, moving_mask) if headers else None
+        world = self._check_world(moving, target, moving_affine, target_affine, world_init, moving_voxel, target_voxel, mask, moving_mask, overlap,
+                                  world_search) if headers else None
         if self.levels > 1:
             return self._optim_levels(moving, target, lr, max_epochs, n, per, mask, moving_voxel, target_voxel, initial, overlap, moving_mask, world)
         okw = dict(overlap=True, moving_mask=moving_mask) if overlap else {}

@@ -342,9 +342,9 @@ def device_loop_settings(criterions, weights):
 
 def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, weights, grad_edges, honor_criterion,
                    optimizer, init, info, device_loop=False, mask=None, moving_voxel=None, target_voxel=None, overlap=None, moving_mask=None,
-                   moving_affine=None, target_affine=None, world_init=None, world=None):
+                   moving_affine=None, target_affine=None, world_init=None, world=None, world_search=None):
     mi = device_loop_settings(criterions, weights) if device_loop else None      # (before anything else: a refused list touches no tensor)
-    headers = moving_affine is not None or target_affine is not None or world_init is not None or world is not None
+    headers = moving_affine is not None or target_affine is not None or world_init is not None or world is not None or world_search is not None
     if headers and mi is None:
         raise ValueError(WORLD_SUPPORT)
     grids = headers or two_lattices(moving, target, moving_voxel, target_voxel)
@@ -378,7 +378,8 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
         init_b = None if init is None else (init.reshape(-1, npose).expand(B, -1) if mode == "rigid" else init.reshape(-1, nd, nd + 1).expand(B, nd, nd + 1))
         solver = AffineMISolver(moving, target, mode=mode, mi=mi, optimizer=optimizer, lr=lr, init=init_b, capacity=max(1, epochs), mask=mask,
                                 moving_voxel=moving_voxel, target_voxel=target_voxel, overlap=overlap, moving_mask=moving_mask,
-                                moving_affine=moving_affine, target_affine=target_affine, world_init=world_init, world=world)
+                                moving_affine=moving_affine, target_affine=target_affine, world_init=world_init, world=world,
+                                world_search=world_search)
         solver.run(epochs)
         final_theta, best_theta = solver.current_theta, solver.best
         if epochs == 0:
@@ -398,6 +399,8 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
             res.update(final_unscaled_theta=final_unscaled, world_matrix=world_mat)
             if solver.world is not None:
                 res.update(world=solver.world, world_init=solver.world.init.clone(), world_center=solver.world.center.clone())
+                if solver.world_search is not None:
+                    res.update(world_search=solver.world_search)
         if valid is not None:
             res.update(valid_fraction=valid)
         if mode == "rigid":
@@ -432,7 +435,7 @@ def _affine_family(mode, moving, target, lr, epochs, device, debug, criterions, 
 def affine_register(moving, target, lr=1E-5, epochs=1000, per=0.1, device="cpu", debug=True, criterions=None,
                     weights=[0.33, 0.33, 0.33], grad_edges=True, *, honor_criterion=False, optimizer="sgd", init=None, info=None,
                     device_loop=False, mask=None, moving_voxel=None, target_voxel=None, overlap=None, moving_mask=None, moving_affine=None,
-                    target_affine=None, world_init=None, world=None):
+                    target_affine=None, world_init=None, world=None, world_search=None):
     """ref:warpings.py:30-113.  Returns ([final_warped, best_warped], [final_theta, best_theta]).
 
     NOTE: like the reference, grad_edges defaults to True here when called directly (and then
@@ -454,21 +457,23 @@ def affine_register(moving, target, lr=1E-5, epochs=1000, per=0.1, device="cpu",
     rigid_register; not with voxel sizes): voxel-to-world matrices of the two images and the initial world transform (_engine.world_setup) - theta
     acts in world millimetres about a centre, whatever the origins and axis directions; the returns are those of voxel sizes, info's world_matrix is
     T = T0 Tr(c) Theta Tr(-c) at the best theta, and info gains world (the WorldGeometry), world_init (T0) and world_center (c).  world: a prepared
-    WorldGeometry instead of the three (the levels of a pyramid share one)."""
+    WorldGeometry instead of the three (the levels of a pyramid share one).  world_init='principal_axes' / 'search' with world_search (a dict of
+    step / keep / iters): T0 from _engine.world_search, for a pair whose orientation the headers do not give; info gains
+    world_search, its record."""
     return _affine_family("affine", moving, target, lr, epochs, device, debug, criterions, weights, grad_edges,
                           honor_criterion, optimizer, init, info, device_loop, mask, moving_voxel, target_voxel, overlap, moving_mask,
-                          moving_affine, target_affine, world_init, world)
+                          moving_affine, target_affine, world_init, world, world_search)
 
 
 def rigid_register(moving, target, lr=1E-5, epochs=1000, per=0.1, device="cpu", debug=True, criterions=None,
                    weights=[0.33, 0.33, 0.33], grad_edges=True, *, honor_criterion=False, optimizer="sgd", init=None, info=None,
                    device_loop=False, mask=None, moving_voxel=None, target_voxel=None, overlap=None, moving_mask=None, moving_affine=None,
-                   target_affine=None, world_init=None, world=None):
+                   target_affine=None, world_init=None, world=None, world_search=None):
     """ref:warpings.py:117-174.  `init` = initial pose (default torch.rand on the tensors' device).  moving_voxel / target_voxel: see
     affine_register - with them Theta(pose) is a rigid motion in millimetres whatever the voxel sizes."""
     return _affine_family("rigid", moving, target, lr, epochs, device, debug, criterions, weights, grad_edges,
                           honor_criterion, optimizer, init, info, device_loop, mask, moving_voxel, target_voxel, overlap, moving_mask,
-                          moving_affine, target_affine, world_init, world)
+                          moving_affine, target_affine, world_init, world, world_search)
 
 
 class _FlowLossFn(torch.autograd.Function):
