@@ -73,7 +73,10 @@ extern "C" {
  *        Later addition under the same number: trx_affine_workspace_carry_offset (diagnostics: where the carry buffers of trx_affine_run's one-launch
  *        iterations sit in the workspace) - one new host-only entry point, no device code, no existing signature or struct changed.
  *        Later addition under the same number: trx_image_moments2 and its workspace query (the second intensity moments behind the principal-axes
- *        initialiser) - new entry points only. */
+ *        initialiser) - new entry points only.
+ *        Later addition under the same number: trx_distance_transform and its workspace query, trx_mask_surface, trx_label_overlap (the exact Euclidean
+ *        distance transform of a binary mask in millimetres, the surface voxels of a mask and the overlap counts of two label maps: what Dice and
+ *        the surface distances are computed from) - new entry points only. */
 #define TRX_VERSION 240
 #define TRX_PSTRIDE 12  /* floats per pair in theta / param / adam / best_theta arrays */
 
@@ -949,6 +952,38 @@ int trx_transform_points(const float *points, float *out, int ndim, int B, int P
 int trx_affine_then_flow_resample(const float *src, size_t src_stride, const int *src_size /*[host] [3]*/, const float *theta /*nullable*/,
                                   const float *flow /*nullable*/, int ndim, int B, int channels, const int *out_size /*[host] [3]*/, int order /*0, 1, 3*/,
                                   int padding /*0 zeros, 1 border*/, float *out, void *stream);
+
+/* ---- Euclidean distance transform, mask surface and label overlap.  Extension: the reference has none of them.  Later addition
+ * under TRX_VERSION 240: new entry points only.  CPU restatement: tests/distance_ref.py.
+ * Volumes are [B][D][H][W] contiguous, 2-D: ndim == 2 with D == 1.  A mask is unsigned char, non-zero = set (a feature).
+ *   dist2(x) = min over features y of sum_a (voxel_a (x_a - y_a))^2 - the SQUARED distance from the centre of voxel x to the centre of the nearest feature,
+ *   in mm^2; voxel NULL: in voxels^2.  0 on a feature.  voxel: host, ndim floats in the tensor's axis order, (dz, dy, dx) or (dy, dx).
+ * A pair without any feature gets +inf everywhere (and -1 in `nearest`) and leaves the other pairs of the batch alone.  nearest (nullable,
+ * int [B][ndim][D][H][W]): the index of a feature that attains the minimum, channel a along spatial axis a (the flow convention); of several equidistant
+ * features the same one on every call (per pass: the smaller axis distance, then the lower index).  The distance recomputed from it is dist2.
+ * voxel == NULL: all arithmetic in integers (every size <= 16384 keeps d^2 below 2^30), dist2 is that integer correctly rounded into fp32 - exact below
+ * 2^24.  With voxel sizes: fp32, weights w_a = voxel_a^2 rounded once, per pass min_j f(j) + w_a (i - j)^2 with (i - j)^2 an exact integer converted to fp32.
+ * The transform is separable, one pass per axis (csrc/distance.hip): a ballot scan along x, an exact outward search along y and z inside the range of rows
+ * / planes that hold a feature at all; its cost grows with the distance to the nearest feature within that range, O(n^2) per line at worst.  No atomics, no floating-point sums: the same bits on every call, a
+ * pair's bits do not depend on the batch around it.  No host sync, no allocation.  Refusals before any HIP call: TRX_ERR_ARG (a NULL mask, dist2,
+ * workspace, surface, label map or counts; a size < 1 or > 16384; B outside 1 .. 65535; >= 2^31 voxels; a voxel size that is not finite or <= 0;
+ * L outside 1 .. 4096; label_bytes not 1 or 4), TRX_ERR_NDIM (ndim not 2 or 3, ndim == 2 with D != 1), TRX_ERR_WORKSPACE. */
+/* Bytes of workspace trx_distance_transform accepts: one 4-byte value per voxel of the batch (4 B N bytes), ndim - 1 int16 index maps (2 B N bytes each),
+ * one byte per row (B D H) and one per plane (B D), each part rounded up to 256, whether or not `nearest` is asked for.  0 = arguments rejected. */
+size_t trx_distance_workspace_bytes(int ndim, int B, int D, int H, int W);
+/* dist2 [B][D][H][W] fp32 and, if not NULL, nearest [B][ndim][D][H][W].  3 launches in 3-D, 2 in 2-D.  dist2 serves as scratch between the passes; mask
+ * must not overlap dist2, nearest or the workspace. */
+int trx_distance_transform(const unsigned char *mask, int ndim, int B, int D, int H, int W, const float *voxel /*[host] [ndim], nullable*/, float *dist2,
+                           int *nearest /*nullable*/, void *workspace, size_t workspace_bytes, void *stream);
+/* surface [B][D][H][W] unsigned char, 0 / 1: 1 where the voxel is set and at least one of its 2 ndim face neighbours is not set or lies outside the volume -
+ * mask & ~binary_erosion(mask, border_value = 0) with the face-connected structuring element, MedPy's surface.  (ndim == 3 with D == 1: both z
+ * neighbours lie outside, every set voxel is a surface voxel.)  One launch, no workspace.  surface must not overlap mask. */
+int trx_mask_surface(const unsigned char *mask, int ndim, int B, int D, int H, int W, unsigned char *surface, void *stream);
+/* counts [B][L][3] = |a = l|, |b = l|, |a = l and b = l| for l in [0, L) of two label maps [B][D][H][W], label_bytes 1: unsigned char, 4: int.  A label
+ * outside [0, L) counts nowhere.  The entry point zeroes counts itself, on the stream.  Per-block 32-bit counters in LDS, flushed with 64-bit integer
+ * adds: integer sums, the same bits on every call.  One memset and one launch, no workspace. */
+int trx_label_overlap(const void *a, const void *b, int label_bytes /*1 or 4*/, int ndim, int B, int D, int H, int W, int L /*1 .. 4096*/,
+                      unsigned long long *counts, void *stream);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@ from ._engine import (AffineMISolver, AffineSolver, BSplineSolver, FlowSolver, L
                       affine_flow_valid, affine_flow_warp, affine_flow_warp_backward, affine_mi_loss_grad, grid_scale, resample, run_slabs_lockstep, spline_coefficients,
                       WorldGeometry, affine_world_theta, image_moments, theta_from_world, world_from_theta, world_geometry, world_setup,
                       WorldSearch, image_covariance, principal_axes_candidates, rotation_grid, world_search)
+from .metrics import SurfaceDistances, dilate_mask, distance_transform, erode_mask, label_overlap, mask_surface, signed_distance, surface_distances  # noqa: F401
 from .pyramid import pyramid, pyramid_shapes, upsample_flow  # noqa: F401
 from .sharding import register_sharded  # noqa: F401
 from .torchregister import Register  # noqa: F401

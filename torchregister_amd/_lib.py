@@ -211,6 +211,10 @@ SIGNATURES = {
     "trx_flow_invert": (ctypes.c_int, [_P, _P, _P, _P] + [ctypes.c_int] * 6 + [ctypes.c_float, _P]),
     "trx_transform_points": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 3 + [_P, _P, c_int_p, c_int_p, ctypes.c_int, ctypes.c_int, _P]),
     "trx_affine_then_flow_resample": (ctypes.c_int, [_P, ctypes.c_size_t, c_int_p, _P, _P] + [ctypes.c_int] * 3 + [c_int_p, ctypes.c_int, ctypes.c_int, _P, _P]),
+    "trx_distance_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "trx_distance_transform": (ctypes.c_int, [_P] + [ctypes.c_int] * 5 + [c_float_p, _P, _P, _P, ctypes.c_size_t, _P]),
+    "trx_mask_surface": (ctypes.c_int, [_P] + [ctypes.c_int] * 5 + [_P, _P]),
+    "trx_label_overlap": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 7 + [_P, _P]),
 }
 
 _lib = None
