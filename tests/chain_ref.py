@@ -118,6 +118,38 @@ def resample(x, theta, flow, out_shape, order, padding="border", dtype=torch.flo
     return F.grid_sample(x.to(dtype), (2.0 * pos + 1.0) / S - 1.0, mode="bilinear", padding_mode="zeros", align_corners=False)
 
 
+def check_image(got, r64, r32, pos, src_shape, order, value_range, figures=None):
+    """What an image through the chain is held to, shared by tests/test_gpu_chain.py (the fixed cases) and tests/fuzz_ops.py (the random ones):
+    (messages of what does not hold, the number of kept voxels outside the field of view).  got [B,C,*out] fp32 on the CPU against the restatement's
+    r64 / r32 at the fp64 positions pos [B,*out,nd].  Orders 1 and 3: within max(1e-5 x value_range, twice the restatement's own fp32 - fp64 gap) on the
+    kept voxels (spline_ref.kept); order 0: no kept voxel differs; voxels outside the field of view (orders 0, 3: beyond half a voxel; order 1: beyond a
+    whole voxel, where the last corner has left) are exactly 0.  figures: a dict that receives image_err, image_bar, image_fp32_gap."""
+    msgs = []
+    keep1 = sr.kept(pos, src_shape, nearest=order == 0)
+    keep = keep1[:, None].expand_as(got)
+    if order == 0:
+        bad = int((got[keep].double() != r64[keep]).sum())
+        if figures is not None:
+            figures.update(nearest_unequal=bad)
+        if bad:
+            msgs.append(f"image order 0: {bad} kept voxels differ")
+        outside = sr.outside(pos, src_shape)
+    else:
+        some = bool(keep1.any())
+        gap = (r32.double() - r64)[keep].abs().max().item() if some else 0.0
+        err, limit = (got.double() - r64)[keep].abs().max().item() if some else 0.0, max(1e-5 * value_range, 2.0 * gap) if some else 0.0
+        if figures is not None:
+            figures.update(image_err=err, image_bar=limit, image_fp32_gap=gap)
+        if not err <= limit:
+            msgs.append(f"image order {order}: err {err:.3e} bar {limit:.3e}")
+        S = torch.tensor(tuple(src_shape)[::-1], dtype=torch.float64)
+        outside = sr.outside(pos, src_shape) if order == 3 else ((pos < -1.0 - 1e-4) | (pos > S + 1e-4)).any(-1)
+    outside = (outside & keep1)[:, None].expand_as(got)
+    if bool(got[outside].any()):
+        msgs.append(f"image order {order}: {int((got[outside] != 0).sum())} voxels outside the field of view are not 0")
+    return msgs, int(outside.sum())
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # the cases: B = 2 with a theta per pair, 2 channels.  name -> (output lattice S_a, source lattice S_b, has theta, flow amplitude in voxels or
 # None, seed).  The flow lives on S_b.  tests/test_chain_host.py asserts that spline_ref.kept removes at most 1 % of the voxels of every case.

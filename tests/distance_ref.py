@@ -85,6 +85,72 @@ def dist2_from_index(idx, voxel=None):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
+# what a transform is held to: shared by tests/test_gpu_distance.py (the fixed cases) and tests/fuzz_ops.py (the random ones)
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def run_reference(mask, voxel):
+    """dict(int, f32) without voxel sizes, dict(f64, f32) with them, of a mask [B, *spatial]: the keys of reference()."""
+    if voxel is None:
+        g = dist2(mask)
+        return dict(int=g, f32=np.where(g >= NONE_INT, np.float32(np.inf), g.astype(np.float32)).astype(np.float32))
+    return dict(f64=dist2(mask, voxel, np.float64), f32=dist2(mask, voxel, np.float32))
+
+
+def d2_bar(r, b):
+    """|delta d^2| <= max(1e-6 max d^2, twice the restatement's own fp32 - fp64 gap) of a pair with voxel sizes.  The floor covers about 16 fp32 roundings;
+    the value needs one rounding of each squared voxel size, three products and two sums, and a near-tie that picks the other candidate costs no more."""
+    return max(1e-6 * float(r["f64"][b].max()), 2.0 * float(np.max(np.abs(r["f32"][b].astype(np.float64) - r["f64"][b]))))
+
+
+def check_transform(got, near, mask, voxel, r, worst=None, report=None):
+    """got [B, *spatial] fp32 (the squared distance), near [B, nd, *spatial] int32 against the runs r of the mask [B, *spatial]: the messages of what does
+    not hold, none when all does.  Without voxel sizes the squared distance is the int64 restatement cast to fp32, bit for bit; with them it is within
+    d2_bar of the fp64 one.  0 on every feature.  A pair without a feature is +inf with nearest == -1.  nearest, without assuming a tie rule: in range, on
+    a feature, and the distance recomputed from it is dist2 (equal integers / within the bar).  worst: a dict that receives the largest error / bar and
+    counts of unequal voxels; report: called with one line per pair that has voxel sizes."""
+    msgs = []
+    worst = {} if worst is None else worst
+
+    def up(key, value):
+        worst[key] = max(worst.get(key, 0.0), float(value))
+
+    sp = mask.shape[1:]
+    for b in range(mask.shape[0]):
+        feat = mask[b] != 0
+        if not feat.any():
+            if not (np.isposinf(got[b]).all() and (near[b] == -1).all()):
+                msgs.append(f"pair {b} (empty): not all +inf / -1")
+            continue
+        if not (got[b][feat] == 0).all():
+            msgs.append(f"pair {b}: d^2 != 0 on {int((got[b][feat] != 0).sum())} features")
+        if not all((near[b, a] >= 0).all() and (near[b, a] < s).all() for a, s in enumerate(sp)):
+            msgs.append(f"pair {b}: nearest out of range")
+            continue
+        if not feat[tuple(near[b])].all():
+            msgs.append(f"pair {b}: nearest is no feature at {int((~feat[tuple(near[b])]).sum())} voxels")
+        back = dist2_from_index(near[b:b + 1], voxel)[0]
+        if voxel is None:
+            bad, bad_back = int((got[b] != r["f32"][b]).sum()), int((back != r["int"][b]).sum())
+            up("iso-unequal", bad)
+            up("iso-nearest-unequal", bad_back)
+            if bad or bad_back:
+                at = tuple(int(v) for v in np.argwhere((got[b] != r["f32"][b]) | (back != r["int"][b]))[0])
+                msgs.append(f"pair {b}: {bad} voxels differ from the integer run, {bad_back} through nearest; first at {at}: "
+                            f"got {got[b][at]}, want {r['f32'][b][at]}, nearest {near[b][(slice(None),) + at].tolist()}")
+        else:
+            limit = d2_bar(r, b)
+            e, e_back = float(np.abs(got[b] - r["f64"][b]).max()), float(np.abs(back - got[b].astype(np.float64)).max())
+            ratio = lambda v: 0.0 if v == 0 else (np.inf if limit == 0 else v / limit)  # noqa: E731
+            up("d2", ratio(e))
+            up("d2-from-nearest", ratio(e_back))
+            if report is not None:
+                report(f"pair {b}: max d^2 {r['f64'][b].max():.4f} err {e:.3e}, recomputed from nearest {e_back:.3e}, bar {limit:.3e} "
+                       f"(restatement fp32-fp64 {np.abs(r['f32'][b] - r['f64'][b]).max():.3e})")
+            if not (e <= limit and e_back <= limit):
+                msgs.append(f"pair {b}: d^2 err {e:.3e}, recomputed from nearest {e_back:.3e}, bar {limit:.3e}")
+    return msgs
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
 # surface, overlap, surface distances
 # ---------------------------------------------------------------------------------------------------------------------------------------
 def surface(mask):

@@ -68,6 +68,19 @@ def invert(u, iterations=ITERATIONS, tol=TOL, init=None):
     return v, r, n
 
 
+def lipschitz_bound(u):
+    """[B] fp64: an upper bound of the Lipschitz constant of p -> Sb(u, p) in the maximum norm.  Sb is multilinear between lattice points and constant
+    outside, so along axis a no channel changes faster than the largest difference of two neighbours on that axis, and a step of |dp|_inf <= 1 moves
+    every axis at once: the sum over the axes of max_{x, c} |u_c(x + e_a) - u_c(x)|.  Below one, v -> -Sb(u, y + v) is a contraction."""
+    u64 = u.double()
+    B = u64.shape[0]
+    total = torch.zeros(B, dtype=torch.float64)
+    for a in range(2, u64.dim()):
+        if u64.shape[a] > 1:
+            total = total + u64.diff(dim=a).abs().reshape(B, -1).amax(1)
+    return total
+
+
 def right_residual(u, v):
     """|v + Sb(u, y + v)| per voxel (the largest channel) in fp64: how far v is from the right inverse of u.  [B, *spatial]."""
     u64, v64 = u.double(), v.double()

@@ -179,18 +179,24 @@ def directions(case, inverse, n=8, eps=1e-4, amplitude=0.01, candidates=32):
     adjoint, which equals autograd to 1e-14, meets the identity to 1e-6 relative: the quotient is then clean."""
     key = (case, bool(inverse), n, eps, amplitude)
     if key not in _DIRECTIONS:
-        B, spatial, K, _ = CASES[case]
         v, g = case_inputs(case, inverse)
-        v64, g64 = v.double(), g.double()
-        b64 = exp_backward(v, g, K, inverse)
-        kept = []
-        for j in range(candidates):
-            d = amplitude * smooth_field(B, spatial, 1.0, 9000 + j, noise=0.0).double()
-            rhs = (g64 * (exp(v64 + eps * d, K, inverse) - exp(v64 - eps * d, K, inverse)) / (2 * eps)).sum().item()
-            lhs = (b64 * d).sum().item()
-            if abs(lhs - rhs) <= 1e-6 * max(abs(lhs), abs(rhs)):
-                kept.append((d, rhs))
-            if len(kept) == n:
-                break
-        _DIRECTIONS[key] = kept
+        _DIRECTIONS[key] = directions_for(v, g, CASES[case][2], inverse, n, eps, amplitude, candidates)
     return _DIRECTIONS[key]
+
+
+def directions_for(v, g, K, inverse, n=8, eps=1e-4, amplitude=0.01, candidates=32, b64=None):
+    """directions() for any velocity v and dflow g: the first n of the candidates (seeds 9000, 9001, ...) that the fp64 adjoint b64 (made here when it
+    is not given) meets the identity on to 1e-6 relative."""
+    B, spatial = v.shape[0], tuple(v.shape[2:])
+    v64, g64 = v.double(), g.double()
+    b64 = exp_backward(v, g, K, inverse) if b64 is None else b64
+    kept = []
+    for j in range(candidates):
+        d = amplitude * smooth_field(B, spatial, 1.0, 9000 + j, noise=0.0).double()
+        rhs = (g64 * (exp(v64 + eps * d, K, inverse) - exp(v64 - eps * d, K, inverse)) / (2 * eps)).sum().item()
+        lhs = (b64 * d).sum().item()
+        if abs(lhs - rhs) <= 1e-6 * max(abs(lhs), abs(rhs)):
+            kept.append((d, rhs))
+        if len(kept) == n:
+            break
+    return kept

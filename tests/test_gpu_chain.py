@@ -137,19 +137,12 @@ def test_images_against_the_restatement(tr, name, order, padding):
     r64, r32 = cr.reference(name, order, padding)
     got = _run(tr, name, order, padding)
     pos = _positions(name, padding)
-    keep = sr.kept(pos, src_shape, nearest=order == 0)[:, None].expand_as(got)
     assert got.shape == (2, 2) + out_shape and bool(torch.isfinite(got).all())
-    if order == 0:
-        assert torch.equal(got[keep].double(), r64[keep])
-        outside = sr.outside(pos, src_shape)
-    else:
-        err, limit = (got.double() - r64)[keep].abs().max().item(), bar(r32[keep].numpy(), r64[keep].numpy(), 1e-5 * (x.max() - x.min()).item())
-        print(f"{name} order {order} {padding}: {err:.3e} bar {limit:.3e}")
-        assert err <= limit
-        S = torch.tensor(src_shape[::-1], dtype=torch.float64)
-        outside = sr.outside(pos, src_shape) if order == 3 else ((pos < -1.0 - 1e-4) | (pos > S + 1e-4)).any(-1)
-    outside = (outside[:, None] & keep[:, :1]).expand_as(got)
-    assert bool(outside.any()) and not bool(got[outside].any())
+    fig = {}
+    msgs, n_outside = cr.check_image(got, r64, r32, pos, src_shape, order, (x.max() - x.min()).item(), fig)
+    print(f"{name} order {order} {padding}: {fig}")
+    assert not msgs, msgs
+    assert n_outside > 0
 
 
 @pytest.mark.parametrize("name", ["9x11x13", "2d", "flow-only"])

@@ -24,12 +24,6 @@ def _gpu(a):
     return torch.from_numpy(np.array(a, order="C")).cuda()      # a copy: the references are read-only
 
 
-def _d2_bar(r, b):
-    """|delta d^2| <= max(1e-6 max d^2, twice the restatement's own fp32 - fp64 gap) of a pair with voxel sizes.  The floor covers about 16 fp32 roundings;
-    the value needs one rounding of each squared voxel size, three products and two sums, and a near-tie that picks the other candidate costs no more."""
-    return bar(r["f32"][b], r["f64"][b], 1e-6 * r["f64"][b].max())
-
-
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # 1. the transform
 # ---------------------------------------------------------------------------------------------------------------------------------------
@@ -43,23 +37,8 @@ def test_squared_distance_and_nearest_feature(tr, case):
     m = _gpu(r["mask"])
     d2, idx = tr.distance_transform(m, voxel, squared=True, return_indices=True)
     assert d2.shape == (B, 1) + sp and d2.dtype == torch.float32 and idx.shape == (B, len(sp)) + sp and idx.dtype == torch.int32
-    got, near = d2[:, 0].cpu().numpy(), idx.cpu().numpy()
-    for b in range(B):
-        feat = r["mask"][b] != 0
-        if not feat.any():
-            assert np.isposinf(got[b]).all() and (near[b] == -1).all()
-            continue
-        assert (got[b][feat] == 0).all()
-        assert all((near[b, a] >= 0).all() and (near[b, a] < s).all() for a, s in enumerate(sp))
-        assert feat[tuple(near[b])].all()
-        back = dr.dist2_from_index(near[b:b + 1], voxel)[0]
-        if voxel is None:
-            assert np.array_equal(got[b], r["f32"][b]) and np.array_equal(back, r["int"][b])
-        else:
-            e, e_back, bb = np.abs(got[b] - r["f64"][b]).max(), np.abs(back - got[b].astype(np.float64)).max(), _d2_bar(r, b)
-            print(f"{name} pair {b}: max d^2 {r['f64'][b].max():.4f} err {e:.3e}, recomputed from nearest {e_back:.3e}, bar {bb:.3e} "
-                  f"(restatement fp32-fp64 {np.abs(r['f32'][b] - r['f64'][b]).max():.3e})")
-            assert e <= bb and e_back <= bb
+    msgs = dr.check_transform(d2[:, 0].cpu().numpy(), idx.cpu().numpy(), r["mask"], voxel, r, report=lambda line: print(f"{name} {line}"))
+    assert not msgs, msgs
     again, idx2 = tr.distance_transform(m, voxel, squared=True, return_indices=True)
     assert torch.equal(again, d2) and torch.equal(idx2, idx)
     assert torch.equal(tr.distance_transform(m, voxel, squared=True), d2)      # the bits do not depend on whether nearest is asked for

@@ -42,6 +42,27 @@ def raw_moments(x, mask=None, offset=None):
     return terms.sum(1), terms.abs().sum(1)
 
 
+def check_raw_moments(got, first_order, want, mag, nvox, worst=None):
+    """What trx_image_moments2's rows are held to, shared by tests/test_gpu_world_search.py (the fixed shapes) and tests/fuzz_ops.py (the random ones): the
+    messages of what does not hold.  got [B, ncol] fp64 against raw_moments' (want, mag): finite, and per column within nvox 2^-52 sum |term| - the
+    worst-case error of an fp64 sum of nvox terms in any order; first_order [B, 1 + nd], trx_image_moments' rows of the same input: got's first columns,
+    bit for bit.  worst: a dict whose 'raw sums' receives the largest error / bar."""
+    msgs = []
+    err, limit = (got - want).abs(), nvox * 2.0 ** -52 * mag
+    ok = err <= limit
+    if worst is not None:
+        ratio = torch.where(err == 0, torch.zeros_like(err), err / limit).max().item()
+        worst["raw sums"] = max(worst.get("raw sums", 0.0), ratio)
+    if not bool(torch.isfinite(got).all()):
+        msgs.append("a raw sum is not finite")
+    if not bool(ok.all()):
+        b, c = (int(v) for v in torch.nonzero(~ok)[0])
+        msgs.append(f"raw sums: volume {b} column {c} err {err[b, c]:.3e} bar {limit[b, c]:.3e}")
+    if not torch.equal(got[:, :first_order.shape[1]], first_order):
+        msgs.append("the order-1 columns are not trx_image_moments' bits")
+    return msgs
+
+
 def min_offset(x, mask=None):
     """[B] fp32: the minimum over the counted voxels, the offset image_covariance hands to the kernel."""
     B = x.shape[0]
