@@ -985,6 +985,31 @@ int trx_mask_surface(const unsigned char *mask, int ndim, int B, int D, int H, i
 int trx_label_overlap(const void *a, const void *b, int label_bytes /*1 or 4*/, int ndim, int B, int D, int H, int W, int L /*1 .. 4096*/,
                       unsigned long long *counts, void *stream);
 
+/* ---- Gaussian smoothing and resampling between grid sizes.  Extension: the reference has no image filter.  Later addition
+ * under TRX_VERSION 240: new entry points only.  CPU restatement: tests/gaussian_ref.py.
+ * in: N volumes [D][H][W], out: N volumes [Do][Ho][Wo], both contiguous fp32 (2-D: ndim 2, D = Do = 1); out must not overlap in or the workspace.
+ * sigma: host, ndim floats in VOXELS OF `in`, in the tensor's axis order, (z, y, x) or (y, x).  Separable, one pass per axis whose radius is above 0
+ * or whose size changes.  Along an axis of S voxels with sigma > 0:
+ *   R = (int)(truncate sigma + 0.5)    (scipy.ndimage.gaussian_filter's radius; R == 0: the axis is not filtered)
+ *   g_t = exp(-((t - R) / sigma)^2 / 2) / sum g, t = 0 .. 2R: formed and normalised in fp64 on the host, used as fp32
+ *   s(i) = sum_t g_t x(i - R + t), indices clamped to [0, S - 1] (padding 1, scipy's mode 'nearest') or out-of-range taps left out (padding 0,
+ *   scipy's mode 'constant': the operator is then symmetric, its own adjoint when no size changes)
+ * and output j is (1 - l) s(i0) + l s(i1) at trx_resample's position u (F.interpolate's; u in fp64, i0 = floor(u), i1 = min(i0 + 1, S - 1),
+ * l = u - i0); an axis that keeps its size has u = j: out = s.  sigma 0 on every axis and no size change: one copy.
+ * TRX_GAUSSIAN_MAX_RADIUS: the largest R (sigma = 32 voxels at truncate 4).  Taps are summed in fp32 in the order t = 0 .. 2R, s(i0) before s(i1), without
+ * atomics: the same bits on every call, and a volume's bits do not depend on N.  Passes run strongest shrink first; intermediates go through the
+ * workspace a chunk of volumes at a time, as trx_resample's do.  No host sync, no allocation.  Refusals before any HIP call: trx_resample's
+ * (TRX_ERR_NDIM; TRX_ERR_ARG: a NULL pointer, a size < 1, >= 2^31 voxels, align_corners not 0 / 1) and TRX_ERR_ARG for sigma NULL, a sigma that is
+ * negative or not finite, truncate <= 0 or not finite, R > TRX_GAUSSIAN_MAX_RADIUS, padding not 0 / 1; TRX_ERR_WORKSPACE for a workspace below the
+ * query's bytes - one byte short is refused, whatever the sigmas. */
+#define TRX_GAUSSIAN_MAX_RADIUS 128
+/* Bytes of workspace trx_gaussian_resample accepts for this geometry: the intermediates of up to three passes, whichever axes the sigmas select.
+ * 0 = arguments rejected, as trx_resample_workspace_bytes. */
+size_t trx_gaussian_workspace_bytes(int ndim, int N, int D, int H, int W, int Do, int Ho, int Wo);
+int trx_gaussian_resample(const float *in, float *out, int ndim, int N, int D, int H, int W, int Do, int Ho, int Wo,
+                          const float *sigma /*[host] [ndim], voxels of `in`*/, float truncate, int align_corners, int padding /*0 zeros, 1 border*/,
+                          void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,8 +12,9 @@ from ._engine import (AffineMISolver, AffineSolver, BSplineSolver, FlowSolver, L
                       affine_flow_valid, affine_flow_warp, affine_flow_warp_backward, affine_mi_loss_grad, grid_scale, resample, run_slabs_lockstep, spline_coefficients,
                       WorldGeometry, affine_world_theta, image_moments, theta_from_world, world_from_theta, world_geometry, world_setup,
                       WorldSearch, image_covariance, principal_axes_candidates, rotation_grid, world_search)
+from .gaussian import gaussian_resample, gaussian_smooth, pyramid_schedule  # noqa: F401
 from .metrics import SurfaceDistances, dilate_mask, distance_transform, erode_mask, label_overlap, mask_surface, signed_distance, surface_distances  # noqa: F401
-from .pyramid import pyramid, pyramid_shapes, upsample_flow  # noqa: F401
+from .pyramid import pyramid, pyramid_masks, pyramid_shapes, upsample_flow  # noqa: F401
 from .sharding import register_sharded  # noqa: F401
 from .torchregister import Register  # noqa: F401
 from .utils import (EPSILON, Attention_UNet, K_gauss, LocalNCCLoss, MILoss, NCCLoss, NMI, NMILoss, PDF, PDF_xis, Regressor, SpatialTransformer, SSDLoss,  # noqa: F401

@@ -215,6 +215,8 @@ SIGNATURES = {
     "trx_distance_transform": (ctypes.c_int, [_P] + [ctypes.c_int] * 5 + [c_float_p, _P, _P, _P, ctypes.c_size_t, _P]),
     "trx_mask_surface": (ctypes.c_int, [_P] + [ctypes.c_int] * 5 + [_P, _P]),
     "trx_label_overlap": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 7 + [_P, _P]),
+    "trx_gaussian_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 8),
+    "trx_gaussian_resample": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 8 + [c_float_p, ctypes.c_float, ctypes.c_int, ctypes.c_int, _P, ctypes.c_size_t, _P]),
 }
 
 _lib = None

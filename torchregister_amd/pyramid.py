@@ -85,10 +85,18 @@ def resample(x, size, align_corners=False, channel_scale=None):
     return out
 
 
-def pyramid(x, levels, align_corners=False):
+def pyramid(x, levels, align_corners=False, shrink=None, sigma=None):
     """[coarsest, ..., finest] levels of x [B, C, *sp] (GPU): each level is trx_resample of the level directly above it; the finest entry
-    is x itself."""
+    is x itself.
+    shrink (a schedule: `levels` tuples of per-axis integer factors, coarsest first, the finest all ones - pyramid_schedule makes one from the
+    voxel sizes): level k has shape ceil(S / f_k) and is gaussian_resample of the FULL-resolution x, with sigma[k] in x's voxels (None: f / 2
+    where f > 1, elastix's default) and border padding; a level with factors all 1 and sigma all 0 is x itself."""
     _require_gpu(x, "x")
+    if shrink is not None:
+        from .gaussian import scheduled_pyramid
+        return scheduled_pyramid(x, levels, align_corners, shrink, sigma)
+    if sigma is not None:
+        raise ValueError("sigma goes with shrink: the halving pyramid has its fixed [1,4,6,4,1]/16 blur")
     shapes = pyramid_shapes(x.shape[2:], levels)
     out = [x]
     for s in shapes[-2::-1]:
@@ -96,12 +104,13 @@ def pyramid(x, levels, align_corners=False):
     return out[::-1]
 
 
-def pyramid_masks(mask, levels, align_corners=False):
+def pyramid_masks(mask, levels, align_corners=False, shrink=None, sigma=None):
     """[coarsest, ..., finest] uint8 masks of a region-of-interest mask [B, 1, *sp] (GPU, non-zero = the voxel counts): the mask as 0.0 / 1.0
     floats through the pyramid() call that makes the target's levels (same blur, same positions, same align_corners), a voxel of a level counting
-    where the result is >= 0.5.  ValueError if some pair's mask is empty at some level (level 1 = the coarsest); one host sync per level."""
+    where the result is >= 0.5.  ValueError if some pair's mask is empty at some level (level 1 = the coarsest); one host sync per level.
+    shrink, sigma: pyramid()'s schedule - the same rule through the same call."""
     out = []
-    for k, m in enumerate(pyramid((mask != 0).float(), levels, align_corners)):
+    for k, m in enumerate(pyramid((mask != 0).float(), levels, align_corners, shrink, sigma)):
         m8 = (m >= 0.5).to(torch.uint8).contiguous()
         empty = (m8.flatten(1).amax(1) == 0).nonzero().flatten().tolist()
         if empty:

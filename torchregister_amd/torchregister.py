@@ -10,6 +10,7 @@ import torch
 from torch import cat
 
 from ._engine import _bending_weight, _folding_threshold, _folding_weight, _invert_args, invert_flow, invert_theta, jacobian_determinant, resample_affine_then_flow, transform_points, _mask_u8, _squarings, affine_warp, check_interpolation, grid_scale, overlap_args, resample, world_setup, world_geometry, SEARCH_KEYS
+from .gaussian import _factors, _level_sigmas, pyramid_schedule, schedule_shapes
 from .pyramid import level_theta, pyramid, pyramid_masks, pyramid_shapes, upsample_flow
 from .warpings import (GRIDS_SUPPORT, INITIAL_SUPPORT, MASK_SUPPORT, OVERLAP_SUPPORT, WORLD_SUPPORT, affine_register, device_loop_settings, flow_register, get_affine_warp, resolve_initial, rigid_register,
                        two_lattices)
@@ -27,7 +28,8 @@ def _per_level(value, levels, name):
 class Register():
     def __init__(self, mode='rigid', device='cpu', criterion=None, weight=None, grad_edges=False, debug=False, *,
                  optimizer='sgd', honor_criterion=False, init=None, smooth_weight=0.0, flow_model='unet', levels=1, spacing=None,
-                 bending_weight=0.0, device_loop=False, diffeomorphic=False, squarings=6, folding_weight=0.0, folding_threshold=0.3):
+                 bending_weight=0.0, device_loop=False, diffeomorphic=False, squarings=6, folding_weight=0.0, folding_threshold=0.3,
+                 shrink=None, smoothing=None, moving_shrink=None, moving_smoothing=None):
         '''
         Numerical registration on an AMD GPU (MI355X) behind the TorchRegister API.
 
@@ -72,6 +74,17 @@ class Register():
             otherwise, here) and optim runs the whole loop on the device (trx_affine_mi_run: the warp fused into the histogram and gradient passes
             of the mutual information, no host sync per iteration); honor_criterion is implied, a batch is B independent pairs, and with levels > 1
             each level fits its intensity ranges to that level's images.  False (default): every route as before.
+        shrink, smoothing, moving_shrink, moving_smoothing : (keyword-only extension, levels > 1 only) the pyramid's schedule.
+            All None (default): today's pyramid - every axis halved per level behind a fixed [1,4,6,4,1]/16 blur.  shrink=[...]: `levels` tuples of
+            per-axis integer factors, coarsest first, the finest all ones - level k has shape ceil(S / f_k) and is the full-resolution image behind
+            a Gaussian of smoothing[k] (voxels of the full image, per axis; None: f / 2 where f > 1, elastix's default) sampled at that size
+            (pyramid(x, levels, shrink=, sigma=)).  The schedule is the target's and also the moving image's unless moving_shrink /
+            moving_smoothing give that one its own - possible where the two images may lie on lattices of their own (mode 'rigid' / 'affine' with
+            device_loop=True; the B-spline mutual-information loop, there with optim(initial=...)), ValueError elsewhere.  shrink='voxel': each image
+            gets pyramid_schedule of its own shape and its own voxel sizes (optim's moving_voxel / target_voxel, or the column norms of
+            moving_affine / target_affine - of a batch of matrices, their mean), so that an anisotropic CT is not shrunk along its thick slices
+            while an isotropic MR is; optim raises ValueError without voxel sizes for both images.  Masks follow their image's schedule.  After
+            optim, .level_schedule = ((shrink, sigma) of the target, (shrink, sigma) of the moving image), None without a schedule.
         '''
         if mode not in ('rigid', 'affine', 'flow'):
             raise ValueError("mode must be 'rigid', 'affine' or 'flow'")
@@ -81,6 +94,7 @@ class Register():
             device_loop_settings(criterion, weight)     # raises unless the list is exactly [MILoss] with a non-zero weight
         if not isinstance(levels, int) or isinstance(levels, bool) or levels < 1:
             raise ValueError(f"levels must be an int >= 1, got {levels!r}")
+        self._init_schedule(mode, criterion, weight, flow_model, levels, device_loop, diffeomorphic, shrink, smoothing, moving_shrink, moving_smoothing)
         if levels > 1 and mode == 'flow' and flow_model not in ('direct', 'bspline'):
             raise ValueError("levels > 1 needs flow_model='direct': the U-Net is built for one image size")
         if spacing is not None and not (mode == 'flow' and flow_model == 'bspline'):
@@ -134,6 +148,7 @@ class Register():
         self.final_pose = None      # mode='rigid' on the device paths: the pose [B,6] (3-D) / [B,3] (2-D) behind final_theta
         self.level_losses = None
         self.level_shapes = None
+        self.level_schedule = None  # levels > 1 with shrink=...: ((shrink, sigma) of the target, (shrink, sigma) of the moving image), coarsest first
         self.world_matrix = None    # device_loop with voxel sizes: [B,nd+1,nd+1], the best theta as moving_mm = M target_mm (rows / columns x, y(, z))
         self.world_init = None      # optim(moving_affine=, target_affine=): T0 [B,nd+1,nd+1] fp64, the fixed world transform in front of what was optimised
         self.world_search = None    # optim(world_init='principal_axes' / 'search'): the WorldSearch record behind world_init (candidates, scores, kept, refined, chosen, eigenvalues)
@@ -142,6 +157,61 @@ class Register():
         self.moving_shape = None    # the spatial shape of the moving image optim ran on (the finest level's): what to_moving(x) returns
         self.initial = None         # optim(initial=...): the effective theta [B,nd,nd+1] the deformation is composed with
         self.valid_fraction = None  # optim(overlap=True / moving_mask=...): [B], N_valid / (target-mask voxels or N) at the returned transform
+
+    def _init_schedule(self, mode, criterion, weight, flow_model, levels, device_loop, diffeomorphic, shrink, smoothing, moving_shrink, moving_smoothing):
+        '''The schedule keywords of __init__: their ValueErrors (what does not need the images' number of axes), and the values as given.'''
+        self.shrink, self.smoothing, self.moving_shrink, self.moving_smoothing = shrink, smoothing, moving_shrink, moving_smoothing
+        rest = (smoothing, moving_shrink, moving_smoothing)
+        if shrink is None and all(v is None for v in rest):
+            return
+        if levels == 1:
+            raise ValueError("shrink / smoothing / moving_shrink / moving_smoothing describe the levels of a pyramid: they need levels > 1")
+        if shrink is None:
+            raise ValueError("smoothing, moving_shrink and moving_smoothing go with shrink=[...]: without it the pyramid halves every axis behind its fixed blur")
+        if isinstance(shrink, str):
+            if shrink != 'voxel' or any(v is not None for v in rest):
+                raise ValueError(f"shrink is a list of per-level factors or 'voxel' (which takes no smoothing / moving_shrink / moving_smoothing: "
+                                 f"each image's schedule comes from its own voxel sizes), got {shrink!r}")
+            return
+        fs = _factors(shrink, None, levels, 'shrink')
+        _level_sigmas(smoothing, fs, None, levels, 'smoothing')
+        if moving_shrink is None and moving_smoothing is None:
+            return
+        mfs = fs if moving_shrink is None else _factors(moving_shrink, None, levels, 'moving_shrink')
+        _level_sigmas(moving_smoothing, mfs, None, levels, 'moving_smoothing')
+        if mode == 'flow':
+            from .utils import MILoss
+            alone = criterion is not None and weight is not None and len(criterion) == 1 and isinstance(criterion[0], MILoss)
+            own = flow_model == 'bspline' and alone and not diffeomorphic       # (the loop that takes optim(initial=...))
+        else:
+            own = bool(device_loop)
+        if not own:
+            raise ValueError("moving_shrink / moving_smoothing give the moving image levels of its own shape: that needs a loop in which the two images may "
+                             "lie on lattices of their own - mode 'rigid' / 'affine' with device_loop=True, or the B-spline mutual-information loop with "
+                             "optim(initial=...); everywhere else both images share one lattice and one schedule")
+
+    def _schedules(self, moving, target, moving_voxel, target_voxel, moving_affine, target_affine, initial):
+        '''None without a schedule, else ((shrink, sigma) of the target, (shrink, sigma) of the moving image) for these images: host arithmetic only.'''
+        if self.shrink is None or self.levels == 1:
+            return None
+        L, nd, ndm = self.levels, target.dim() - 2, moving.dim() - 2
+        if isinstance(self.shrink, str):
+            if moving_affine is not None and target_affine is not None:      # columns in the tensor's axis order: their norms are the voxel sizes
+                world_geometry(moving.shape[2:], target.shape[2:], moving_affine, target_affine)      # (a malformed header: its ValueError, here)
+                norms = lambda A, n: torch.as_tensor(A, dtype=torch.float64).cpu().reshape(-1, n + 1, n + 1)[:, :n, :n].norm(dim=1).mean(0).tolist()  # noqa: E731
+                moving_voxel, target_voxel = norms(moving_affine, ndm), norms(target_affine, nd)
+            if moving_voxel is None or target_voxel is None:
+                raise ValueError("shrink='voxel' derives each image's schedule from its voxel sizes: give moving_voxel= and target_voxel=, or "
+                                 "moving_affine= and target_affine=")
+            return pyramid_schedule(target.shape[2:], L, target_voxel), pyramid_schedule(moving.shape[2:], L, moving_voxel)
+        fs = _factors(self.shrink, nd, L, 'shrink')
+        tsched = (fs, _level_sigmas(self.smoothing, fs, nd, L, 'smoothing'))
+        if self.moving_shrink is None and self.moving_smoothing is None:
+            return tsched, tsched
+        if self.mode == 'flow' and initial is None:
+            raise ValueError("moving_shrink / moving_smoothing need optim(initial=...) in mode='flow': without it both images share one lattice and one schedule")
+        mfs = fs if self.moving_shrink is None else _factors(self.moving_shrink, ndm, L, 'moving_shrink')
+        return tsched, (mfs, _level_sigmas(self.moving_smoothing, mfs, ndm, L, 'moving_smoothing'))
 
     def _flow_kw(self, n, lr, max_epochs):
         kw = dict(mode='bilinear', n=n, lr=lr, max_epochs=max_epochs, optimizer=self.optimizer, smooth_weight=self.smooth_weight,
@@ -202,7 +272,7 @@ class Register():
         return overlap_args(overlap, moving_mask, moving)
 
     def _check_world(self, moving, target, moving_affine, target_affine, world_init, moving_voxel, target_voxel, mask, moving_mask, overlap=False,
-                     world_search=None):
+                     world_search=None, sched=None):
         '''moving_affine=... / target_affine=... / world_init=... of optim: ValueError unless the loop is the fused mutual-information loop of mode
         'rigid' / 'affine' (device_loop=True) - GRIDS_SUPPORT's rule - and for every malformed header, before any device work (world_init='moments'
         then runs trx_image_moments on each image).  Returns the WorldGeometry, made once from the full-resolution headers, or None.'''
@@ -224,8 +294,9 @@ class Register():
         on = None
         if self.levels > 1:
             L = self.levels
-            on = (pyramid(moving, L)[0], pyramid(target, L)[0], None if mask is None else pyramid_masks(mask, L)[0],
-                  None if moving_mask is None else pyramid_masks(moving_mask.to(moving.device), L)[0])
+            tk, mk = ({}, {}) if sched is None else (dict(shrink=s[0], sigma=s[1]) for s in sched)      # the run's own coarsest level
+            on = (pyramid(moving, L, **mk)[0], pyramid(target, L, **tk)[0], None if mask is None else pyramid_masks(mask, L, **tk)[0],
+                  None if moving_mask is None else pyramid_masks(moving_mask.to(moving.device), L, **mk)[0])
         return world_setup(moving, target, moving_affine, target_affine, world_init, mask, moving_mask, world_search, overlap, mi, on)
 
     def _set_grids(self, grids, target, info):
@@ -315,10 +386,12 @@ class Register():
         self.initial = initial
         if mask is not None:
             mask = self._check_mask(mask, target)
+        sched = self._schedules(moving, target, moving_voxel, target_voxel, moving_affine, target_affine, initial)
         world = self._check_world(moving, target, moving_affine, target_affine, world_init, moving_voxel, target_voxel, mask, moving_mask, overlap,
-                                  world_search) if headers else None
+                                  world_search, sched) if headers else None
         if self.levels > 1:
-            return self._optim_levels(moving, target, lr, max_epochs, n, per, mask, moving_voxel, target_voxel, initial, overlap, moving_mask, world)
+            return self._optim_levels(moving, target, lr, max_epochs, n, per, mask, moving_voxel, target_voxel, initial, overlap, moving_mask, world,
+                                      sched)
         okw = dict(overlap=True, moving_mask=moving_mask) if overlap else {}
         if self.mode == 'flow':
             flowreg = flow_register(target.shape[2:], **self._flow_kw(n, lr, max_epochs)).to(moving.device)
@@ -358,7 +431,7 @@ class Register():
         self._set_grids(grids, target, info)
 
     def _optim_levels(self, moving, target, lr, max_epochs, n, per, mask=None, moving_voxel=None, target_voxel=None, initial=None, overlap=False,
-                      moving_mask=None, world=None):
+                      moving_mask=None, world=None, sched=None):
         '''Coarse-to-fine: the single-level machinery (flow_register / _affine_family) on each level of pyramid(moving) and
         pyramid(target), coarsest first; each level starts from the previous level's FINAL parameters (rigid: the pose, drawn by
         torch.rand for the coarsest level as a single-level run draws it; affine: theta; flow: upsample_flow of the flow).  Optimiser
@@ -366,21 +439,24 @@ class Register():
         Two lattices (rigid / affine, device_loop): moving and target each get their own pyramid, so a level halves both lattices and doubles both
         voxel sizes - the half extents, and with them the scale, are the same at every level; the theta handed up is the unscaled one.
         initial (flow, B-spline mutual information): moving and target get their own pyramids (align_corners=True) and level k runs with
-        level_theta(initial, ...), the theta between the two level lattices; the flow is handed up by upsample_flow as without it.'''
+        level_theta(initial, ...), the theta between the two level lattices; the flow is handed up by upsample_flow as without it.
+        sched (shrink=...): the levels come from pyramid(x, L, shrink=, sigma=) with each image's own schedule and have the shapes ceil(S / f); nothing
+        else changes - theta does not depend on the level, a level's voxel is v S / S_l per axis, level_theta and upsample_flow take any shapes.'''
         grids = world is not None or two_lattices(moving, target, moving_voxel, target_voxel)      # (refused by optim unless the loop is the fused mutual-information one)
         L = self.levels
         lrs, epochs = _per_level(lr, L, 'lr'), _per_level(max_epochs, L, 'max_epochs')
-        shapes = pyramid_shapes(target.shape[2:], L)
+        tk, mk = ({}, {}) if sched is None else (dict(shrink=s[0], sigma=s[1]) for s in sched)
+        shapes = pyramid_shapes(target.shape[2:], L) if sched is None else schedule_shapes(target.shape[2:], sched[0][0])
         if tuple(moving.shape[2:]) != tuple(target.shape[2:]) and not grids and initial is None:
             raise ValueError(f"moving {tuple(moving.shape)} and target {tuple(target.shape)} differ in spatial size")
         flow = self.mode == 'flow'
-        movs, tgts = pyramid(moving, L, align_corners=flow), pyramid(target, L, align_corners=flow)
-        masks = [None] * L if mask is None else pyramid_masks(mask, L, align_corners=flow)      # raises for a pair whose mask empties at some level
-        mmasks = [None] * L if moving_mask is None else pyramid_masks(moving_mask.to(moving.device), L, align_corners=flow)      # over the MOVING pyramid's shapes
+        movs, tgts = pyramid(moving, L, align_corners=flow, **mk), pyramid(target, L, align_corners=flow, **tk)
+        masks = [None] * L if mask is None else pyramid_masks(mask, L, align_corners=flow, **tk)      # raises for a pair whose mask empties at some level
+        mmasks = [None] * L if moving_mask is None else pyramid_masks(moving_mask.to(moving.device), L, align_corners=flow, **mk)      # over the MOVING pyramid's shapes
         okw = (lambda k: dict(overlap=True, moving_mask=mmasks[k])) if overlap else (lambda k: {})      # the flag goes to every level
         init = None if flow else self.init
-        mshapes = None if initial is None else pyramid_shapes(moving.shape[2:], L)
-        self.level_losses, self.level_shapes = [], shapes
+        mshapes = None if initial is None else pyramid_shapes(moving.shape[2:], L) if sched is None else schedule_shapes(moving.shape[2:], sched[1][0])
+        self.level_losses, self.level_shapes, self.level_schedule = [], shapes, sched
         for k in range(L):
             if flow:
                 reg = flow_register(shapes[k], **self._flow_kw(n, lrs[k], epochs[k])).to(moving.device)
