@@ -4,8 +4,8 @@
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 CSRC    := torchregister_amd/csrc
-SRCS    := $(CSRC)/api.hip $(CSRC)/affine.hip $(CSRC)/affine_finalize.hip $(CSRC)/affine_lattice.hip $(CSRC)/flow.hip $(CSRC)/lncc.hip $(CSRC)/kde.hip $(CSRC)/peer.hip $(CSRC)/pyramid.hip $(CSRC)/bspline.hip $(CSRC)/mi.hip $(CSRC)/affine_mi.hip $(CSRC)/svf.hip $(CSRC)/affine_flow.hip $(CSRC)/spline.hip $(CSRC)/moments.hip $(CSRC)/jacobian.hip $(CSRC)/flowops.hip $(CSRC)/chain.hip $(CSRC)/distance.hip $(CSRC)/gaussian.hip
-HDRS    := $(CSRC)/trx_common.h $(CSRC)/trx_dev.h $(CSRC)/affine_host.h $(CSRC)/affine_finalize.h $(CSRC)/affine_tile.h $(CSRC)/affine_zstream.h $(CSRC)/affine_eft.h $(CSRC)/mi_dev.h $(CSRC)/jacobian.h $(CSRC)/svf_sample.h $(CSRC)/flow_sample.h $(CSRC)/spline_sample.h $(CSRC)/resample_plan.h include/trx.h
+SRCS    := $(CSRC)/api.hip $(CSRC)/affine.hip $(CSRC)/affine_finalize.hip $(CSRC)/affine_lattice.hip $(CSRC)/flow.hip $(CSRC)/lncc.hip $(CSRC)/kde.hip $(CSRC)/peer.hip $(CSRC)/pyramid.hip $(CSRC)/bspline.hip $(CSRC)/mi.hip $(CSRC)/affine_mi.hip $(CSRC)/svf.hip $(CSRC)/affine_flow.hip $(CSRC)/spline.hip $(CSRC)/moments.hip $(CSRC)/jacobian.hip $(CSRC)/flowops.hip $(CSRC)/chain.hip $(CSRC)/distance.hip $(CSRC)/gaussian.hip $(CSRC)/ngf.hip
+HDRS    := $(CSRC)/trx_common.h $(CSRC)/trx_dev.h $(CSRC)/affine_host.h $(CSRC)/affine_finalize.h $(CSRC)/affine_tile.h $(CSRC)/affine_zstream.h $(CSRC)/affine_eft.h $(CSRC)/mi_dev.h $(CSRC)/jacobian.h $(CSRC)/ngf.h $(CSRC)/svf_sample.h $(CSRC)/flow_sample.h $(CSRC)/spline_sample.h $(CSRC)/resample_plan.h include/trx.h
 OBJS    := $(SRCS:$(CSRC)/%.hip=build/%.o)
 LIB     := torchregister_amd/lib/libtrx.so
 # -fno-slp-vectorize: on gfx950 v_pk_*_f32 is no faster than two scalar VALU ops, and the SLP

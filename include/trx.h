@@ -76,7 +76,9 @@ extern "C" {
  *        initialiser) - new entry points only.
  *        Later addition under the same number: trx_distance_transform and its workspace query, trx_mask_surface, trx_label_overlap (the exact Euclidean
  *        distance transform of a binary mask in millimetres, the surface voxels of a mask and the overlap counts of two label maps: what Dice and
- *        the surface distances are computed from) - new entry points only. */
+ *        the surface distances are computed from) - new entry points only.
+ *        Later addition under the same number: trx_ngf_cfg, trx_ngf_loss_grad, trx_bspline_ngf_run and their workspace queries (the normalised gradient
+ *        field criterion, alone and as the data term of the free-form deformation loop) - new entry points and one new struct only. */
 #define TRX_VERSION 240
 #define TRX_PSTRIDE 12  /* floats per pair in theta / param / adam / best_theta arrays */
 
@@ -1009,6 +1011,60 @@ size_t trx_gaussian_workspace_bytes(int ndim, int N, int D, int H, int W, int Do
 int trx_gaussian_resample(const float *in, float *out, int ndim, int N, int D, int H, int W, int Do, int Ho, int Wo,
                           const float *sigma /*[host] [ndim], voxels of `in`*/, float truncate, int align_corners, int padding /*0 zeros, 1 border*/,
                           void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- Normalised gradient field criterion (NGF, Haber & Modersitzki 2006): a local multimodal data term - edges of the two images
+ * should be parallel or antiparallel, whatever the intensities on either side.  Extension: the reference has none.  Later addition under TRX_VERSION 240:
+ * new entry points only.  CPU restatement: tests/ngf_ref.py.
+ * target / warped: [B][D][H][W] fp32, dense (D = 1 for ndim 2).  Voxel sizes h_a: cfg->voxel, 1 without.  eps[b] = (eps_t, eps_w): device [B][2], the
+ * edge parameters (noise levels) of the two images.  mask: as trx_mi_cfg.mask (NULL = every voxel, N_m = the number of non-zero voxels of the pair).
+ *   differences  (D_a I)(n) = sc_a(n) / h_a (I(n + (ip - n_a) e_a) - I(n - (n_a - im) e_a)), ip = min(n_a + 1, S_a - 1), im = max(n_a - 1, 0), sc = 1/2
+ *                where ip - im == 2, else 1: central inside, one-sided on the faces, 0 on an axis of one voxel (trx_flow_jacobian's convention and
+ *                torch.gradient's).  The kernels form (sc fl(1 / h_a)) (I(+) - I(-)) in fp32.
+ *   loss         gT = D target, gW = D warped, s = <gW, gT>, a = |gW|^2 + eps_w^2, b = |gT|^2 + eps_t^2, r = s^2 / (a b), r = 0 where a b == 0 (a select:
+ *                no NaN); loss[b] = alpha (1 - (1 / N_m) sum_{v in M} r(v)), in [0, alpha] up to rounding.  N_m == 0: loss and gradient 0, the other
+ *                pairs untouched, as for trx_mi_loss_grad.
+ *   gradient     q = dr / dgW = 2 s gT / (a b) - 2 s^2 gW / (a^2 b), 0 outside the mask and where a b == 0; grad_warped = -(alpha / N_m) D^T q, in
+ *                gather form
+ *                  (D^T q)(y) = sum_a (1 / h_a) [ [y_a >= 1] sc_a(y - e_a) q_a(y - e_a) + [y_a = S_a - 1] sc_a(y) q_a(y)
+ *                                                - [y_a <= S_a - 2] sc_a(y + e_a) q_a(y + e_a) - [y_a = 0] sc_a(y) q_a(y) ]
+ *                (the two face terms cancel on an axis of one voxel).  The target gets no gradient; eps is held constant under the gradient.  With a
+ *                mask, q is 0 outside it, so grad_warped is 0 at every voxel none of whose face neighbours (nor itself) lies in the mask; a voxel
+ *                just outside the mask is read by the difference at its neighbour inside and has a gradient.
+ *   properties   loss(T, c W + d) == loss(T, W) for c != 0 when eps_w is scaled by |c|; in particular loss(T, 1 - W) == loss(T, W): contrast inversion
+ *                costs nothing.  The zero padding of a warp outside the moving field of view is an edge like any other: `mask` is the remedy (the
+ *                overlap rule of trx_moving_grid is not built for this criterion).
+ * Launches: forward (2 ndim loads of each image per voxel, the y / z neighbours cache hits; r summed in fp64 per thread in ascending voxels, a fixed
+ * shuffle tree, the waves in order -> one fp64 partial and one mask count per block of 2048 voxels; q [B][ndim][N] into the workspace when a gradient is
+ * wanted), reduce (one wave per pair: loss[b] and the scale -alpha / N_m into the workspace - N_m never goes to the host), backward (the gather above
+ * times the pair's scale; grad_warped is fully written).  grad_warped == NULL skips the q stores and the backward pass.  No atomics, no floating-point
+ * sum in a data-dependent order: the same bits on every call, a pair's bits do not depend on its batch, an all-ones mask gives the bits of no mask, and a
+ * loss-only call gives the loss bits of the call with a gradient.  3-D traffic: forward 8 (+ 1 with a mask) B/voxel read and 12 B/voxel written,
+ * backward 12 B/voxel read and 4 B/voxel written.  No host sync, no allocation.  Refusals before any HIP call: TRX_ERR_ARG (target, warped, cfg,
+ * cfg->eps, loss or workspace NULL, a size < 1, B outside 1 .. 65535, >= 2^31 voxels, alpha not finite, a voxel size that is not finite or not > 0),
+ * TRX_ERR_NDIM (ndim not 2 or 3, ndim 2 with D != 1), TRX_ERR_WORKSPACE. */
+typedef struct {
+    float alpha;
+    const float *eps;            /* device [B][2]: eps_t, eps_w; read on every evaluation: it must outlive the call / run */
+    const float *voxel;          /* [host] [ndim] in the tensor's axis order, (z, y, x) or (y, x), > 0, finite; NULL = 1 */
+    const unsigned char *mask;   /* as trx_mi_cfg.mask */
+} trx_ngf_cfg;
+size_t trx_ngf_workspace_bytes(int ndim, int B, int D, int H, int W);   /* 0 = arguments rejected */
+int trx_ngf_loss_grad(const float *target, const float *warped, int ndim, int B, int D, int H, int W, const trx_ngf_cfg *cfg, float *loss /*[B]*/,
+                      float *grad_warped /*nullable, [B][D][H][W]*/, void *workspace, size_t workspace_bytes, void *stream);
+/* Free-form deformation + NGF: trx_bspline_mi_run with this criterion where trx_mi_loss_grad stands - per iteration expand -> warp -> trx_ngf_loss_grad ->
+ * warp backward -> (folding) -> reduce -> the bending / decide / update launches of trx_bspline_run.  One entry point for every route: mg and theta both
+ * NULL - one lattice, trx_flow_warp / _backward; both given - trx_affine_flow_warp / _backward, one interpolation through the initial affine theta, the
+ * moving image on a lattice of its own (one of the two alone: TRX_ERR_ARG).  fold NULL or fold->weight == 0: the unpenalised loop, launch for launch;
+ * otherwise the folding penalty of trx_bspline_run_fold.  mg->overlap or mg->mask: TRX_ERR_ARG (the overlap rule is not built for this criterion).
+ * trx_bspline_state keeps its whole meaning (base, bending_weight, stop_crit, stopped, flow_last, losses = data term + lambda E + w P); the pairs'
+ * losses take the place of terms at stride 1, as on the mutual-information route.  vol->target: dense [B][D][H][W].  Workspace: one query whatever the
+ * route (the folding penalty's part included); one byte short is TRX_ERR_WORKSPACE; 0 = arguments rejected.  Refusals before any HIP call: those of
+ * trx_bspline_run, trx_ngf_loss_grad's, trx_moving_grid's when mg is given, trx_fold_cfg's when fold is given; iters > losses_capacity:
+ * TRX_ERR_CAPACITY.  Arbiter: tests/bspline_ref.py::expand + oracle/compose.py::flow_warp + tests/ngf_ref.py under torch autograd. */
+size_t trx_bspline_ngf_workspace_bytes(int ndim, int B, int D, int H, int W, int sz, int sy, int sx, const trx_moving_grid *mg /*[host], nullable*/);
+int trx_bspline_ngf_run(const trx_volumes *vol, const trx_moving_grid *mg /*[host], nullable*/, const float *theta /*nullable*/, const trx_ngf_cfg *cfg,
+                        const trx_opt_cfg *opt, const trx_bspline_state *st, const int *spacing /*[host]*/, const trx_fold_cfg *fold /*[host], nullable*/,
+                        int iters, void *workspace, size_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -830,16 +830,30 @@ class BSplineSolver:
     forward (the *_fold entry points: trx_bspline_run_fold, trx_bspline_mi_run_fold): `losses` and the early stop see the total, `base` gets no
     gradient.  It works with every route above - fused criteria, mi, initial, mask, overlap, bending_weight - except squarings (ValueError: the
     exponential of a velocity field does not fold).  0 (default): the entry points, launches and bits of before.  The threshold's default 0.3 is
-    a margin, see folding_penalty."""
+    a margin, see folding_penalty.
+    ngf = dict(eta=1.0, alpha=1.0, voxel=None, target_eps=None, moving_eps=None) (NGFLoss.settings): the data term is the normalised gradient field
+    (ngf_loss_grad) instead of `loss` / `mi`, and the loop runs in trx_bspline_ngf_run; an eps of None is fitted once, here, to (target, moving)
+    (ngf_edge_parameters; kept as `.ngf_eps`).  It takes mask, initial, base, bending_weight and folding_weight; squarings, overlap and
+    moving_mask raise ValueError."""
 
     def __init__(self, moving, target, spacing, loss=None, optimizer="sgd", lr=1e-3, init=None, base=None, capacity=1000, stop_crit=None,
                  keep_last=False, betas=(0.9, 0.999), eps=1e-8, bending_weight=0.0, mi=None, squarings=None, mask=None, initial=None,
-                 initial_scale=None, overlap=None, moving_mask=None, folding_weight=0.0, folding_threshold=0.3):
+                 initial_scale=None, overlap=None, moving_mask=None, folding_weight=0.0, folding_threshold=0.3, ngf=None):
         self.folding_weight, self.folding_threshold = _folding_weight(folding_weight), _folding_threshold(folding_threshold)
+        if ngf is not None:
+            unknown = set(ngf) - {"eta", "alpha", "voxel", "target_eps", "moving_eps"}
+            if unknown:
+                raise ValueError(f"unknown normalised-gradient-field settings {sorted(unknown)}")
+            if loss is not None or mi is not None:
+                raise ValueError("ngf is a data term of its own: give it without `loss` and without `mi`")
+            if squarings is not None:
+                raise ValueError("squarings (the diffeomorphic model) runs the fused criteria only: the normalised gradient field on a velocity field is not built")
+            if overlap or moving_mask is not None:
+                raise ValueError("overlap / moving_mask (the overlap rule) are not built for the normalised gradient field: `mask` is its region of interest")
         if squarings is not None and self.folding_weight != 0:
             raise ValueError("folding_weight is the folding penalty of the displacement models: with squarings the deformation is the exponential of a "
                              "velocity field, which does not fold")
-        if initial is not None and (mi is None or squarings is not None):
+        if initial is not None and ((mi is None and ngf is None) or squarings is not None):
             raise ValueError("initial (an affine composed into the deformation) runs the mutual-information loop only: give it with `mi` and without `squarings`")
         self.overlap, moving_mask = overlap_args(overlap, moving_mask, moving)
         if self.overlap and initial is None:
@@ -847,7 +861,7 @@ class BSplineSolver:
         if initial is None and initial_scale is not None:
             raise ValueError("initial_scale is the scale of `initial`: give it with `initial`")
         if mask is not None:
-            if mi is None:
+            if mi is None and ngf is None:
                 raise ValueError("mask is the region of interest of the mutual-information data term: give it with `mi`")
             mask = _mask_u8(mask, target)
         self.mask = None
@@ -901,9 +915,23 @@ class BSplineSolver:
         self.flow_last = torch.empty(fshape, device=dev) if (keep_last or stop_crit is not None) else None
         self.velocity_last = self.flow_last if squarings is not None else None
         self.vol = self.batch.vol()
-        self.mi = None
+        self.mi = self.ngf = None
         self.fold = _lib.FoldCfg(self.folding_weight, self.folding_threshold) if self.folding_weight > 0 else None
-        if squarings is not None:
+        if ngf is not None:
+            # eps is fitted once, here, to (target, moving); with `initial` to the moving image as that affine puts it on the target lattice
+            voxel = _ngf_voxel(ngf.get("voxel"), nd)
+            self.mask = None if mask is None else mask.to(dev)
+            seen = self.batch.moving
+            if initial is not None and ngf.get("moving_eps") is None:
+                seen = affine_flow_warp(self.batch.moving, initial.detach().to(dev), torch.zeros(fshape, device=dev), initial_scale)
+            self.ngf_eps = ngf_settings_eps(ngf, self.batch.target, seen, voxel, self.mask)
+            self.ngf, self._ngf_voxel = _ngf_cfg_c(ngf.get("alpha", 1.0), self.ngf_eps, voxel, self.mask)
+            self.ws_bytes = self.lib.trx_bspline_ngf_workspace_bytes(nd, b, *_dhw(self.batch.spatial), *self.sp3,
+                                                                     None if self.moving_grid is None else ctypes.byref(self.moving_grid))
+            if self.ws_bytes == 0:
+                raise _lib.TrxError(f"trx_bspline_ngf_workspace_bytes rejected {b} x {tuple(self.batch.spatial)} with spacing {self.spacing}")
+            self.workspace = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
+        elif squarings is not None:
             self.ws_bytes = self.lib.trx_bspline_svf_workspace_bytes(nd, b, *_dhw(self.batch.spatial), *self.sp3, squarings)
             if self.ws_bytes == 0:
                 raise _lib.TrxError(f"trx_bspline_svf_workspace_bytes rejected {b} x {tuple(self.batch.spatial)} with spacing {self.spacing}")
@@ -983,6 +1011,14 @@ class BSplineSolver:
 
     def run(self, iters):
         iters = _reserve(self, iters)
+        if self.ngf is not None:      # one entry point for every route: one lattice or through `initial`, with or without the folding penalty
+            mg, theta = (None, None) if self.initial is None else (ctypes.byref(self.moving_grid), _lib.ptr(self.initial))
+            with torch.cuda.device(self.batch.device):
+                rc = self.lib.trx_bspline_ngf_run(ctypes.byref(self.vol), mg, theta, ctypes.byref(self.ngf), ctypes.byref(self.opt), ctypes.byref(self.state),
+                                                  self.sp3, None if self.fold is None else ctypes.byref(self.fold), iters, _lib.ptr(self.workspace),
+                                                  self.ws_bytes, _lib.current_stream(self.batch.device))
+            _lib.check(rc, "trx_bspline_ngf_run")
+            return self._expand()
         if self.fold is not None:
             with torch.cuda.device(self.batch.device):
                 rc, what = self._run_fold(iters)
@@ -1725,6 +1761,112 @@ def mi_loss_grad(target, warped, rng, bins=32, alpha=1.0, normalized=False, need
         rc = lib.trx_mi_loss_grad(_lib.ptr(y), _lib.ptr(w), nd, B, D, H, W, ctypes.byref(cfg), _lib.ptr(loss), _lib.ptr(grad), _lib.ptr(ws), ws_bytes,
                                   _lib.current_stream(y.device))
     _lib.check(rc, "trx_mi_loss_grad")
+    return loss, grad
+
+
+def _ngf_voxel(voxel, nd):
+    """voxel= of the normalised-gradient-field entry points -> None or a tuple of nd positive finite floats in the tensor's axis order."""
+    if voxel is None:
+        return None
+    try:
+        v = tuple(float(h) for h in voxel)
+    except TypeError:
+        raise ValueError(f"voxel is one size per axis, (z, y, x) or (y, x), got {voxel!r}") from None
+    if len(v) != nd or not all(math.isfinite(h) and h > 0 for h in v):
+        raise ValueError(f"voxel is {nd} positive finite sizes in the tensor's axis order, got {voxel!r}")
+    return v
+
+
+def ngf_gradient(x, voxel=None):
+    """[B,nd,*spatial]: the differences of include/trx.h (trx_ngf_loss_grad) of x [B,1,*spatial] - central inside, one-sided on the faces, 0 on an
+    axis of one voxel, over the voxel sizes - as plain torch ops with clamped indices (differentiable)."""
+    nd = x.dim() - 2
+    v = _ngf_voxel(voxel, nd) or (1.0,) * nd
+    out = []
+    for a in range(nd):
+        S = x.shape[2 + a]
+        idx = torch.arange(S, device=x.device)
+        ip, im = (idx + 1).clamp(max=S - 1), (idx - 1).clamp(min=0)
+        sc = torch.where(ip - im == 2, 0.5, 1.0).to(x.dtype) / v[a]
+        shape = [1] * x.dim()
+        shape[2 + a] = S
+        out.append((x.index_select(2 + a, ip) - x.index_select(2 + a, im)) * sc.reshape(shape))
+    return torch.cat(out, dim=1)
+
+
+def ngf_edge_parameters(target, moving, eta=1.0, voxel=None, mask=None):
+    """[B,2] fp32 on the tensors' device: (eps_t, eps_w) of the normalised gradient field per pair - eta times the mean of |grad I| (ngf_gradient:
+    the kernel's differences, over `voxel`) of the target and of the moving (or warped) image; 0 for a constant image, which the criterion
+    defines (r = 0 where the denominator is 0).  mask (see _mask_u8, on the target lattice): the mean is taken over the voxels that count, for
+    every image on that lattice - an image of another shape, and a pair whose mask is empty, use the whole image.  Plain torch ops, no host
+    sync: it runs once per optimisation."""
+    B = target.shape[0]
+    m = None if mask is None else _mask_u8(mask, target).reshape(B, -1).float()
+    cols = []
+    for x in (target, moving):
+        x = x.detach().float()
+        mag = ngf_gradient(x, voxel).square().sum(1).sqrt().reshape(B, -1)
+        mean = mag.mean(1)
+        if m is not None and mag.shape == m.shape:
+            n = m.sum(1)
+            mean = torch.where(n > 0, (mag * m).sum(1) / n.clamp(min=1.0), mean)
+        cols.append(float(eta) * mean)
+    return torch.stack(cols, dim=1).contiguous()
+
+
+def _ngf_cfg_c(alpha, eps, voxel, mask):
+    """(trx_ngf_cfg, the host voxel array it points to or None) over the eps tensor [B,2] and the uint8 mask (or None): the caller keeps all alive."""
+    cfg = _lib.NGFCfg()
+    vox = None if voxel is None else (ctypes.c_float * len(voxel))(*voxel)
+    cfg.alpha, cfg.eps = float(alpha), eps.data_ptr()
+    cfg.voxel = None if vox is None else ctypes.cast(vox, ctypes.POINTER(ctypes.c_float))
+    cfg.mask = None if mask is None else mask.data_ptr()
+    return cfg, vox
+
+
+def _ngf_eps(eps, B, device):
+    if not isinstance(eps, torch.Tensor) or tuple(eps.shape) != (B, 2):
+        raise ValueError(f"expected an eps tensor [{B}, 2] (ngf_edge_parameters), got {tuple(eps.shape) if isinstance(eps, torch.Tensor) else type(eps).__name__}")
+    return eps.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def ngf_settings_eps(ngf, target, moving, voxel, mask):
+    """eps [B,2] of a settings dict (NGFLoss.settings): a given target_eps / moving_eps serves every pair, None is fitted (ngf_edge_parameters)."""
+    eps = ngf_edge_parameters(target, moving, ngf.get("eta", 1.0), voxel, mask)
+    for col, key in enumerate(("target_eps", "moving_eps")):
+        if ngf.get(key) is not None:
+            eps[:, col] = float(ngf[key])
+    return eps
+
+
+def ngf_loss_grad(target, warped, eps, alpha=1.0, voxel=None, need_grad=True, mask=None):
+    """Normalised gradient field criterion (extension, include/trx.h: trx_ngf_loss_grad): target / warped [B,1,*spatial] fp32 on the GPU, eps [B,2]
+    (ngf_edge_parameters), voxel = the voxel sizes in the tensor's axis order or None = 1, mask (see _mask_u8) or None = every voxel.  Returns
+    (loss [B], d loss / d warped (same shape as warped; zero beyond the face neighbours of the mask's voxels, whose differences read them) or None)."""
+    if target.shape != warped.shape or target.dim() not in (4, 5) or target.shape[1] != 1:
+        raise ValueError(f"expected two [B,1,*spatial] tensors of equal shape, got {tuple(target.shape)} and {tuple(warped.shape)}")
+    nd = target.dim() - 2
+    voxel = _ngf_voxel(voxel, nd)
+    if mask is not None:
+        mask = _mask_u8(mask, target)
+    lib = _lib.load()
+    if not (target.is_cuda and warped.is_cuda):
+        raise _lib.TrxError("ngf_loss_grad needs CUDA (HIP) tensors: there is no CPU fallback")
+    y, w = target.detach().contiguous().float(), warped.detach().contiguous().float()
+    B = y.shape[0]
+    eps = _ngf_eps(eps, B, y.device)
+    D, H, W = (1, *y.shape[2:]) if nd == 2 else y.shape[2:]
+    cfg, _vox = _ngf_cfg_c(alpha, eps, voxel, mask)
+    loss = torch.empty(B, device=y.device)
+    grad = torch.empty_like(w) if need_grad else None
+    ws_bytes = lib.trx_ngf_workspace_bytes(nd, B, D, H, W)
+    if ws_bytes == 0:
+        raise _lib.TrxError(f"trx_ngf_workspace_bytes rejected {B} x {tuple(y.shape[2:])}")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=y.device)
+    with torch.cuda.device(y.device):
+        rc = lib.trx_ngf_loss_grad(_lib.ptr(y), _lib.ptr(w), nd, B, D, H, W, ctypes.byref(cfg), _lib.ptr(loss), _lib.ptr(grad), _lib.ptr(ws), ws_bytes,
+                                   _lib.current_stream(y.device))
+    _lib.check(rc, "trx_ngf_loss_grad")
     return loss, grad
 
 

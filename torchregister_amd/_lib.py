@@ -81,6 +81,10 @@ class MICfg(ctypes.Structure):
                 ("mask", ctypes.c_void_p)]
 
 
+class NGFCfg(ctypes.Structure):
+    _fields_ = [("alpha", ctypes.c_float), ("eps", ctypes.c_void_p), ("voxel", ctypes.POINTER(ctypes.c_float)), ("mask", ctypes.c_void_p)]
+
+
 class MovingGrid(ctypes.Structure):
     _fields_ = [("D", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("scale", ctypes.c_float * PSTRIDE),
                 ("overlap", ctypes.c_int), ("mask", ctypes.c_void_p),      # zero / None: every target voxel counts (zero padding)
@@ -217,6 +221,11 @@ SIGNATURES = {
     "trx_label_overlap": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 7 + [_P, _P]),
     "trx_gaussian_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 8),
     "trx_gaussian_resample": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 8 + [c_float_p, ctypes.c_float, ctypes.c_int, ctypes.c_int, _P, ctypes.c_size_t, _P]),
+    "trx_ngf_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 5),
+    "trx_ngf_loss_grad": (ctypes.c_int, [_P, _P] + [ctypes.c_int] * 5 + [ctypes.POINTER(NGFCfg), _P, _P, _P, ctypes.c_size_t, _P]),
+    "trx_bspline_ngf_workspace_bytes": (ctypes.c_size_t, [ctypes.c_int] * 8 + [ctypes.POINTER(MovingGrid)]),
+    "trx_bspline_ngf_run": (ctypes.c_int, [ctypes.POINTER(Volumes), ctypes.POINTER(MovingGrid), _P, ctypes.POINTER(NGFCfg), ctypes.POINTER(OptCfg),
+                                           ctypes.POINTER(BSplineState), c_int_p, ctypes.POINTER(FoldCfg), ctypes.c_int, _P, ctypes.c_size_t, _P]),
 }
 
 _lib = None

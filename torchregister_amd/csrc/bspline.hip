@@ -3,7 +3,8 @@
 // (trx_bspline_run), and the bending energy of the lattice with its gradient (trx_bspline_bending; in the loop: trx_bspline_state.bending_weight).
 // The same loop with other data terms: mutual information (trx_bspline_mi_run, csrc/mi.hip) and the diffeomorphic form, in which the expanded
 // lattice is a stationary velocity field (trx_bspline_svf_run, csrc/svf.hip).  The displacement loops with a folding penalty on the Jacobian determinant
-// of the total flow: trx_bspline_run_fold, trx_bspline_mi_run_fold (the penalty's kernels: csrc/jacobian.hip).
+// of the total flow: trx_bspline_run_fold, trx_bspline_mi_run_fold (the penalty's kernels: csrc/jacobian.hip).  The normalised gradient field as the data
+// term, every route behind one entry point: trx_bspline_ngf_run (csrc/ngf.hip).
 // CPU restatements: tests/bspline_ref.py, tests/bspline_bending_ref.py, tests/jacobian_ref.py.
 //
 // Definition (include/trx.h): an axis of S voxels with spacing d has G = (S - 1) / d + 4 control points, point i at voxel (i - 1) d; at
@@ -24,6 +25,7 @@
 // read again at once by the loss-and-gradient passes behind it, so its stores carry none.
 #include "affine_host.h"   // ami_grid_check (trx_bspline_mi_run_grids); includes trx_common.h
 #include "jacobian.h"      // the folding penalty of the *_fold entry points (csrc/jacobian.hip)
+#include "ngf.h"           // the data term of trx_bspline_ngf_run (csrc/ngf.hip)
 
 #include <algorithm>
 #include <cmath>
@@ -986,6 +988,73 @@ extern "C" int trx_bspline_mi_run_fold(const trx_volumes *vol, const trx_moving_
 {
     if ((mg == nullptr) != (theta == nullptr)) return TRX_ERR_ARG;
     return bspline_mi_run_impl(vol, mg, theta, cfg, opt, st, spacing, iters, workspace, workspace_bytes, stream, fold, true);
+}
+
+// Free-form deformation + normalised gradient field (csrc/ngf.hip): the mutual-information loop's layout with trx_ngf_loss_grad's workspace where
+// trx_mi_loss_grad's stands, and the folding penalty's workspace behind it whatever the weight - one query for every route.
+struct BsNgfLayout {
+    size_t o_warped, o_go, o_ngf, o_fold, ws_bytes;
+};
+
+static int bspline_ngf_layout(const BsGeom &g, BsNgfLayout *l)
+{
+    const size_t ngf = trx_ngf_workspace_bytes(g.ndim, g.B, g.S[0], g.S[1], g.S[2]), fold = trx_flow_folding_workspace_bytes(g.ndim, g.B, g.S[0], g.S[1], g.S[2]);
+    if (ngf == 0 || fold == 0) return TRX_ERR_ARG;
+    const size_t vols = (((size_t)g.B * g.S[0] * g.S[1] * g.S[2] * sizeof(float)) + 255) & ~(size_t)255;
+    l->o_warped = (g.ws_bytes + 255) & ~(size_t)255;
+    l->o_go = l->o_warped + vols;
+    l->o_ngf = l->o_go + vols;
+    l->o_fold = fold_ws_offset(l->o_ngf + ngf);
+    l->ws_bytes = l->o_fold + fold;
+    return TRX_OK;
+}
+
+extern "C" size_t trx_bspline_ngf_workspace_bytes(int ndim, int B, int D, int H, int W, int sz, int sy, int sx, const trx_moving_grid *mg)
+{
+    BsGeom g;
+    BsNgfLayout l;
+    if (bspline_geom(ndim, B, D, H, W, sz, sy, sx, &g) != TRX_OK || bspline_ngf_layout(g, &l) != TRX_OK) return 0;
+    if (mg && (ami_grid_check(ndim, mg) != TRX_OK || mg->overlap || mg->mask)) return 0;
+    return l.ws_bytes;
+}
+
+extern "C" int trx_bspline_ngf_run(const trx_volumes *vol, const trx_moving_grid *mg, const float *theta, const trx_ngf_cfg *cfg, const trx_opt_cfg *opt,
+                                   const trx_bspline_state *st, const int *spacing, const trx_fold_cfg *fold, int iters, void *workspace,
+                                   size_t workspace_bytes, void *stream)
+{
+    if (!cfg || (mg == nullptr) != (theta == nullptr)) return TRX_ERR_ARG;
+    BsGeom g;
+    int rc = bspline_run_checks(vol, opt, st, spacing, iters, workspace, &g);
+    if (rc == TRX_OK && mg) rc = ami_grid_check(vol->ndim, mg);
+    if (rc != TRX_OK) return rc;
+    if (mg && (mg->overlap || mg->mask)) return TRX_ERR_ARG;      // the overlap rule is not built for this criterion
+    NgfGeom ng;
+    if ((rc = ngf_geom(g.ndim, g.B, g.S[0], g.S[1], g.S[2], &ng)) != TRX_OK) return rc;
+    if ((rc = ngf_cfg_check(cfg, &ng)) != TRX_OK) return rc;
+    if (fold && (rc = fold_cfg_check(fold)) != TRX_OK) return rc;
+    const size_t nvox = (size_t)vol->D * vol->H * vol->W;
+    if (vol->B > 1 && vol->target_stride != nvox) return TRX_ERR_ARG;   // the criterion takes a dense [B][D][H][W] target
+    BsNgfLayout l;
+    if ((rc = bspline_ngf_layout(g, &l)) != TRX_OK) return rc;
+    if (workspace_bytes < l.ws_bytes) return TRX_ERR_WORKSPACE;
+    FoldRun fr;
+    const FoldRun *frp = nullptr;
+    if (fold && fold->weight > 0.f) {
+        if ((rc = fold_geom(g.ndim, g.B, g.S[0], g.S[1], g.S[2], &fr.g)) != TRX_OK) return rc;
+        fr.weight = fold->weight; fr.threshold = fold->threshold;
+        fr.ws = (char *)workspace + l.o_fold;
+        frp = &fr;
+    }
+    if (st->losses && iters > st->losses_capacity) return TRX_ERR_CAPACITY;
+    char *ws = (char *)workspace;
+    float *nloss = (float *)(ws + g.terms_offset), *warped = (float *)(ws + l.o_warped), *go = (float *)(ws + l.o_go);
+    hipStream_t s = (hipStream_t)stream;
+    return bspline_loop(g, vol, opt, st, iters, nloss, 1, workspace, s, [&]() {
+        int r = mg ? trx_affine_flow_warp(vol, mg, theta, st->flow, 1, warped, stream) : trx_flow_warp(vol, st->flow, 1, warped, stream);
+        if (r != TRX_OK) return r;
+        if ((r = ngf_loss_grad_impl(ng, vol->target, warped, cfg, nloss, go, ws + l.o_ngf, s)) != TRX_OK) return r;
+        return mg ? trx_affine_flow_warp_backward(vol, mg, theta, st->flow, 1, go, st->dflow, stream) : trx_flow_warp_backward(vol, st->flow, 1, go, st->dflow, stream);
+    }, frp);
 }
 
 // Diffeomorphic free-form deformation (csrc/svf.hip): the expanded lattice is a stationary velocity field.  Behind the loop's workspace lie

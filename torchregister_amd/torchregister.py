@@ -121,6 +121,9 @@ class Register():
             from .utils import MILoss
             if any(isinstance(c, MILoss) for c in (criterion or [])):
                 raise ValueError("diffeomorphic=True runs the fused criteria only (nn.MSELoss, NCCLoss, SSDLoss): mutual information on a velocity field is not built")
+            from .utils import NGFLoss
+            if any(isinstance(c, NGFLoss) for c in (criterion or [])):
+                raise ValueError("diffeomorphic=True runs the fused criteria only (nn.MSELoss, NCCLoss, SSDLoss): the normalised gradient field on a velocity field is not built")
         self.diffeomorphic, self.squarings = bool(diffeomorphic), squarings
         self.velocity = self.inverse_flow = None
         self._inverse_warp = None
@@ -180,8 +183,8 @@ class Register():
         mfs = fs if moving_shrink is None else _factors(moving_shrink, None, levels, 'moving_shrink')
         _level_sigmas(moving_smoothing, mfs, None, levels, 'moving_smoothing')
         if mode == 'flow':
-            from .utils import MILoss
-            alone = criterion is not None and weight is not None and len(criterion) == 1 and isinstance(criterion[0], MILoss)
+            from .utils import MILoss, NGFLoss
+            alone = criterion is not None and weight is not None and len(criterion) == 1 and isinstance(criterion[0], (MILoss, NGFLoss))
             own = flow_model == 'bspline' and alone and not diffeomorphic       # (the loop that takes optim(initial=...))
         else:
             own = bool(device_loop)
@@ -225,12 +228,31 @@ class Register():
             kw.update(weights=self.weight)
         return kw
 
+    def _ngf_alone(self):
+        '''Whether optim runs the normalised-gradient-field B-spline loop (trx_bspline_ngf_run): mode 'flow', flow_model 'bspline', NGFLoss alone.'''
+        from .utils import NGFLoss
+        alone = self.criterion is not None and self.weight is not None and len(self.criterion) == 1 and isinstance(self.criterion[0], NGFLoss)
+        return self.mode == 'flow' and self.flow_model == 'bspline' and alone and not self.diffeomorphic
+
+    def _level_criteria(self, full_shape, level_shape):
+        '''The criterion list of a pyramid level: an NGFLoss with voxel sizes gets a copy whose voxel is the level's, v S / S_l per axis (a level keeps
+        the image's field of view), so that its differences stay in millimetres on every level; everything else is passed as it is.'''
+        from .utils import NGFLoss
+        out = []
+        for c in self.criterion:
+            if isinstance(c, NGFLoss) and c.voxel is not None and len(c.voxel) == len(level_shape):
+                voxel = tuple(v * s / sl for v, s, sl in zip(c.voxel, full_shape, level_shape))
+                c = NGFLoss(eta=c.eta, alpha=c.alpha, voxel=voxel, target_eps=c.target_eps, moving_eps=c.moving_eps)
+            out.append(c)
+        return out
+
     def _check_mask(self, mask, target):
         '''mask=... of optim: ValueError unless the loop is one of the device-side mutual-information loops; the uint8 mask [B,1,*spatial].'''
         if self.mode == 'flow':
             from .utils import MILoss
             alone = self.criterion is not None and self.weight is not None and len(self.criterion) == 1 and isinstance(self.criterion[0], MILoss)
             ok = alone and not self.diffeomorphic and (self.flow_model == 'bspline' or (self.flow_model == 'direct' and target.dim() == 5))
+            ok = ok or self._ngf_alone()
         else:
             ok = self.device_loop
         if not ok:
@@ -248,10 +270,10 @@ class Register():
         return True
 
     def _check_initial(self, initial, moving, target, moving_voxel, target_voxel):
-        '''initial=... of optim: ValueError unless the loop is the B-spline mutual-information loop (mode 'flow', flow_model 'bspline', MILoss
-        alone, not diffeomorphic, no voxel sizes), before any device work.  Returns the effective theta [B,nd,nd+1].'''
-        from .utils import MILoss
-        alone = self.criterion is not None and self.weight is not None and len(self.criterion) == 1 and isinstance(self.criterion[0], MILoss)
+        '''initial=... of optim: ValueError unless the loop is the B-spline mutual-information loop or the B-spline normalised-gradient-field loop
+        (mode 'flow', flow_model 'bspline', MILoss or NGFLoss alone - trx_bspline_mi_run_grids / trx_bspline_ngf_run -, not diffeomorphic, no voxel sizes), before any device work.  Returns the effective theta [B,nd,nd+1].'''
+        from .utils import MILoss, NGFLoss
+        alone = self.criterion is not None and self.weight is not None and len(self.criterion) == 1 and isinstance(self.criterion[0], (MILoss, NGFLoss))
         if not (self.mode == 'flow' and self.flow_model == 'bspline' and alone and not self.diffeomorphic) or moving_voxel is not None or target_voxel is not None:
             raise ValueError(INITIAL_SUPPORT)
         return resolve_initial(initial, moving, target)
@@ -321,7 +343,7 @@ class Register():
             [B,*spatial], non-zero = the voxel counts.  Only those voxels enter the mutual information (histogram, normalisation, gradient) and
             the fitted target range - a couch, a coil or a lesion the moving image lacks is left out.  Supported where the loop is one of the
             device-side mutual-information loops: mode 'rigid' / 'affine' with device_loop=True, or mode 'flow' with flow_model 'direct' (3-D) or
-            'bspline' and MILoss alone; ValueError anywhere else, before any device work.  With levels > 1 a level's mask is the float mask sent
+            'bspline' and MILoss alone, or with 'bspline' and NGFLoss alone; ValueError anywhere else, before any device work.  With levels > 1 a level's mask is the float mask sent
             through the pyramid call of the target and thresholded at >= 0.5; a pair whose mask is empty at some level raises ValueError.
         moving_voxel, target_voxel : (keyword-only extension) voxel sizes in mm, in the tensors' axis order (dz, dy, dx) / (dy, dx), both or
             neither.  With them theta acts between the two volumes in millimetres (their centres coinciding, their axes aligned): mode='rigid' is
@@ -331,7 +353,7 @@ class Register():
             reg(moving) -, reg(x) warps any [B,c,*moving spatial] onto the target lattice, .world_matrix is the best theta in mm (None without
             voxel sizes), .target_shape the lattice, .final_pose keeps its meaning and mask= stays on the target lattice.  With levels > 1 each
             image gets its own pyramid, so both fields of view and the scale are the same at every level; .level_shapes are the target's.
-        initial : (keyword-only extension, mode 'flow' with flow_model='bspline' and MILoss alone; ValueError anywhere else, before any device work)
+        initial : (keyword-only extension, mode 'flow' with flow_model='bspline' and MILoss or NGFLoss alone; ValueError anywhere else, before any device work)
             the result of the rigid / affine stage before - an effective theta [B,nd,nd+1], or a Register of mode 'rigid' / 'affine' that has run
             onto this target lattice (its .theta is used).  The deformation is composed with it and the ORIGINAL moving image, on its own lattice,
             is sampled once (affine_flow_warp; the loop runs in trx_bspline_mi_run_grids) - no resampling in between, nothing lost outside the
@@ -459,7 +481,10 @@ class Register():
         self.level_losses, self.level_shapes, self.level_schedule = [], shapes, sched
         for k in range(L):
             if flow:
-                reg = flow_register(shapes[k], **self._flow_kw(n, lrs[k], epochs[k])).to(moving.device)
+                fkw = self._flow_kw(n, lrs[k], epochs[k])
+                if 'criterions' in fkw:
+                    fkw['criterions'] = self._level_criteria(target.shape[2:], shapes[k])
+                reg = flow_register(shapes[k], **fkw).to(moving.device)
                 up = None if init is None else upsample_flow(init, shapes[k])
                 if self.flow_model == 'bspline':
                     reg.base_flow = up       # the level's lattice starts from zero and adds to what the coarser levels found
@@ -481,7 +506,7 @@ class Register():
                 kw = dict(lr=lrs[k], epochs=epochs[k], per=per, device=self.device, debug=False, grad_edges=self.grad_edges,
                           honor_criterion=self.honor_criterion, optimizer=self.optimizer, init=init, info=info, device_loop=self.device_loop)
                 if self.criterion is not None and self.weight is not None:
-                    kw.update(criterions=self.criterion, weights=self.weight)
+                    kw.update(criterions=self._level_criteria(target.shape[2:], shapes[k]), weights=self.weight)
                 elif self.weight is not None:
                     kw.update(weights=self.weight)
                 if masks[k] is not None:

@@ -142,6 +142,65 @@ class MILoss(nn.Module):
         return _MIFn.apply(y, yp, rng, self.bins, self.alpha, self.normalized, mask).mean()
 
 
+class _NGFFn(torch.autograd.Function):
+    """loss [B] = normalised-gradient-field loss of (target, warped) through the HIP kernels; gradient wrt warped only (eps is held constant)."""
+
+    @staticmethod
+    def forward(ctx, y, yp, eps, alpha, voxel, mask=None):
+        loss, grad = _engine.ngf_loss_grad(y, yp, eps, alpha, voxel, need_grad=yp.requires_grad, mask=mask)
+        ctx.save_for_backward(grad)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gl):
+        (grad,) = ctx.saved_tensors
+        if grad is None:
+            return None, None, None, None, None, None
+        return None, grad * gl.view(-1, *([1] * (grad.dim() - 1))), None, None, None, None      # the mask gets no gradient
+
+
+class NGFLoss(nn.Module):
+    """alpha * (1 - mean of <gW, gT>^2 / ((|gW|^2 + eps_w^2) (|gT|^2 + eps_t^2))) over the (masked) voxels, gT / gW the finite-difference
+    gradients of the target and the warped image - the normalised gradient field of Haber & Modersitzki (2006): edges should be parallel or
+    antiparallel, whatever the intensities on either side.  A LOCAL multimodal criterion, where MILoss is a global one: loss(T, c W + d) ==
+    loss(T, W) for c != 0 (eps_w scaled by |c|, which a fitted eps is), in particular loss(T, 1 - W) == loss(T, W) - contrast inversion costs
+    nothing - and a slowly varying bias field changes little.  In [0, alpha].  EXTENSION: the reference has no such criterion; defined by
+    include/trx.h (trx_ngf_loss_grad; CPU restatement tests/ngf_ref.py).  Runs on the GPU only; call order (target, warped); batch mean.
+    eta: the fitted edge parameters are eta * mean |grad I| per image (_engine.ngf_edge_parameters), refitted on every call from (y, yp.detach())
+    unless target_eps / moving_eps give them; voxel: the voxel sizes in the tensor's axis order, None = 1 (Register(levels=L) hands each pyramid
+    level a copy with that level's voxel sizes, v S / S_l per axis).  The zero padding of a warp outside
+    the moving field of view is an edge like any other: mask= is the remedy.
+    Alone in flow_register(flow_model='bspline') / Register('flow', flow_model='bspline', criterion=[NGFLoss()]) the whole loop runs on the
+    device (trx_bspline_ngf_run) with eps fitted once to (target, moving), and optim takes mask=, initial= and levels; anywhere else it is an
+    ordinary autograd criterion of the generic loops."""
+
+    def __init__(self, eta=1.0, alpha=1.0, voxel=None, target_eps=None, moving_eps=None):
+        super().__init__()
+        self.eta, self.alpha = float(eta), float(alpha)
+        if not self.eta >= 0:
+            raise ValueError(f"eta must be >= 0, got {eta!r}")
+        self.voxel = None if voxel is None else tuple(float(h) for h in voxel)
+        if self.voxel is not None:
+            _engine._ngf_voxel(self.voxel, len(self.voxel))
+        for e in (target_eps, moving_eps):
+            if e is not None and not float(e) >= 0:
+                raise ValueError(f"an edge parameter is a number >= 0, got {e!r}")
+        self.target_eps = None if target_eps is None else float(target_eps)
+        self.moving_eps = None if moving_eps is None else float(moving_eps)
+
+    def settings(self, weight=1.0):
+        """The dict BSplineSolver(ngf=...) takes, alpha multiplied by `weight`."""
+        return dict(eta=self.eta, alpha=self.alpha * float(weight), voxel=self.voxel, target_eps=self.target_eps, moving_eps=self.moving_eps)
+
+    def forward(self, y, yp, mask=None):
+        """mask: a region of interest on the target lattice (see MILoss.forward): only those voxels enter the mean, the gradient is zero
+        beyond their face neighbours, fitted edge parameters are taken inside it.  It gets no gradient."""
+        if mask is not None:
+            mask = _engine._mask_u8(mask, y)
+        eps = _engine.ngf_settings_eps(self.settings(), y, yp.detach(), self.voxel, mask)
+        return _NGFFn.apply(y, yp, eps, self.alpha, self.voxel, mask).mean()
+
+
 class SSDLoss(nn.Module):
     """alpha * sum((y - yp)^2) (ref:utils.py:208-221)."""
 

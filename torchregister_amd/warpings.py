@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 from . import _engine
 from ._engine import AffineMISolver, AffineSolver, FlowSolver, LossSpec
-from .utils import LocalNCCLoss, MILoss, NCCLoss, NMILoss, SSDLoss, SpatialTransformer  # noqa: F401
+from .utils import LocalNCCLoss, MILoss, NCCLoss, NGFLoss, NMILoss, SSDLoss, SpatialTransformer  # noqa: F401
 
 
 class _AffineWarpFn(torch.autograd.Function):
@@ -281,7 +281,8 @@ def _nmi_affine_loop(moving, target, mode, spec, nmi, w_nmi, lr, epochs, init):
 
 MASK_SUPPORT = ("mask is the region of interest of the device-side mutual-information loops: mode='rigid' / 'affine' with device_loop=True and "
                 "criterion=[MILoss()], or mode='flow' with flow_model='direct' (3-D) or 'bspline' (2-D, 3-D) and MILoss alone; "
-                "the other criteria and loops have no mask")
+                "the other criteria and loops have no mask; "
+                "it is also the region of interest of the normalised-gradient-field B-spline loop: mode='flow' with flow_model='bspline' and NGFLoss alone")
 
 
 GRIDS_SUPPORT = ("a moving image on a lattice of its own (another spatial shape) and voxel sizes (moving_voxel=, target_voxel=) are honoured by the "
@@ -297,7 +298,8 @@ WORLD_SUPPORT = ("voxel-to-world matrices (moving_affine=, target_affine=) and w
 INITIAL_SUPPORT = ("initial= (the rigid / affine result of the stage before, composed into the deformation so that the moving image is sampled once, on "
                    "its own lattice) is honoured by the B-spline mutual-information loop: mode='flow' with flow_model='bspline' and criterion=[MILoss()] "
                    "alone, without diffeomorphic=True and without voxel sizes (the effective theta carries them); `initial` is an effective theta "
-                   "[B,nd,nd+1] or a Register of mode 'rigid' / 'affine' that has run onto the same target lattice")
+                   "[B,nd,nd+1] or a Register of mode 'rigid' / 'affine' that has run onto the same target lattice; "
+                   "the normalised-gradient-field B-spline loop (criterion=[NGFLoss()] alone) honours it in the same way")
 
 
 OVERLAP_SUPPORT = ("overlap=True / moving_mask= (mutual information over the overlap only: a target voxel counts while its sample lies inside the moving "
@@ -519,7 +521,7 @@ class flow_register(nn.Module):
     `optimize` reports 'Converged' only when every pair has stopped (`.iterations` holds the per-pair counts).
     flow_model='bspline' (extension): cubic B-spline free-form deformation - a control lattice with `spacing` voxels between control
     points (an int or one per axis) parameterises the flow, flow = base_flow + expand(control), optimised by trx_bspline_run like
-    'direct' (fused MSE / NCC / SSD criteria, or MILoss alone - trx_bspline_mi_run; smooth_weight must stay 0).  bending_weight = lambda > 0 adds lambda * (bending energy of
+    'direct' (fused MSE / NCC / SSD criteria, or MILoss alone - trx_bspline_mi_run -, or NGFLoss alone - trx_bspline_ngf_run, with mask=, initial=, bending_weight and folding_weight, without diffeomorphic / overlap / moving_mask; smooth_weight must stay 0).  bending_weight = lambda > 0 adds lambda * (bending energy of
     the control lattice, bspline_bending: per voxel of this image size, in its voxel coordinates) to each pair's loss - `.losses` and
     stop_crit see the total, `base_flow` is not penalised; the other flow models raise for it.  `.control` is the final
     control tensor [B, nd, *grid]; `.init_control` (None = zero) and `.base_flow` (None = none) set the start.
@@ -549,6 +551,8 @@ class flow_register(nn.Module):
                 raise ValueError(f"diffeomorphic=True is the velocity-field form of flow_model='bspline'; flow_model={flow_model!r} has none")
             if any(isinstance(c, MILoss) for c in (criterions or [])):
                 raise ValueError("diffeomorphic=True runs the fused criteria only (nn.MSELoss, NCCLoss, SSDLoss): mutual information on a velocity field is not built")
+            if any(isinstance(c, NGFLoss) for c in (criterions or [])):
+                raise ValueError("diffeomorphic=True runs the fused criteria only (nn.MSELoss, NCCLoss, SSDLoss): the normalised gradient field on a velocity field is not built")
         self.img_size = tuple(int(s) for s in img_size)
         if flow_model != "bspline" and spacing is not None:
             raise ValueError(f"spacing is the control-point spacing of flow_model='bspline'; flow_model={flow_model!r} has none")
@@ -568,9 +572,9 @@ class flow_register(nn.Module):
             if smooth_weight != 0:
                 raise ValueError("flow_model='bspline' takes no smooth_weight: its regularisers are the control-point spacing and bending_weight")
             used = [nn.MSELoss(), NCCLoss(), NMILoss()] if criterions is None else criterions
-            if loss_spec_from(used, weights[: len(used)]) is None and not (len(used) == 1 and isinstance(used[0], MILoss)):
+            if loss_spec_from(used, weights[: len(used)]) is None and not (len(used) == 1 and isinstance(used[0], (MILoss, NGFLoss))):
                 raise ValueError("flow_model='bspline' runs the fused criteria only: nn.MSELoss (mean), NCCLoss and SSDLoss, or MILoss alone, "
-                                 f"got {[type(c).__name__ for c in used]}")
+                                 f"got {[type(c).__name__ for c in used]} (NGFLoss alone runs too)")
         self.flow_model = flow_model
         self.criterions = [nn.MSELoss(), NCCLoss(), NMILoss()] if criterions is None else criterions
         if len(weights) < len(self.criterions):
@@ -610,11 +614,17 @@ class flow_register(nn.Module):
     def mask_supported(self, ndim):
         """Whether optimize() on `ndim`-dimensional images runs one of the device-side mutual-information loops, the ones that take a mask."""
         alone = len(self.criterions) == 1 and isinstance(self.criterions[0], MILoss)
+        if self.ngf_alone():
+            return True
         return alone and not self.diffeomorphic and (self.flow_model == "bspline" or (self.flow_model == "direct" and ndim == 3))
 
+    def ngf_alone(self):
+        """Whether optimize() runs the normalised-gradient-field B-spline loop (trx_bspline_ngf_run): NGFLoss alone, flow_model='bspline'."""
+        return self.flow_model == "bspline" and not self.diffeomorphic and len(self.criterions) == 1 and isinstance(self.criterions[0], NGFLoss)
+
     def initial_supported(self):
-        """Whether optimize() takes initial=: the B-spline mutual-information loop (MILoss alone, not diffeomorphic)."""
-        return self.flow_model == "bspline" and not self.diffeomorphic and len(self.criterions) == 1 and isinstance(self.criterions[0], MILoss)
+        """Whether optimize() takes initial=: the B-spline mutual-information loop (MILoss alone, not diffeomorphic) and the normalised-gradient-field one."""
+        return self.flow_model == "bspline" and not self.diffeomorphic and len(self.criterions) == 1 and isinstance(self.criterions[0], (MILoss, NGFLoss))
 
     def optimize(self, moving, target, device=None, debug=True, grad_edges=False, *, mask=None, initial=None, overlap=None, moving_mask=None):
         """mask (keyword-only extension): a region of interest on the target lattice, [B,1,*spatial] or [B,*spatial], non-zero = the voxel counts,
@@ -627,7 +637,7 @@ class flow_register(nn.Module):
             raise NotImplementedError("grad_edges=True is not supported (SURVEY Q6)")
         self.initial = self.valid_fraction = None
         if overlap or moving_mask is not None:
-            if initial is None or not self.initial_supported():
+            if initial is None or not self.initial_supported() or self.ngf_alone():
                 raise ValueError(OVERLAP_SUPPORT)
             overlap, moving_mask = _engine.overlap_args(overlap, moving_mask, moving)
         if initial is not None:
@@ -682,8 +692,9 @@ class flow_register(nn.Module):
     def _optimize_bspline(self, moving, target, spec, debug, mask=None, initial=None, overlap=None, moving_mask=None):
         """The 'direct' loop with a control lattice as the parameter: one trx_bspline_run call, per-pair early stop on the device, one host sync."""
         from ._engine import BSplineSolver
-        mi = self.criterions[0].settings(self.weights[0]) if spec is None else None     # __init__ admits MILoss alone beside the fused criteria
-        solver = BSplineSolver(moving, target, self.spacing, loss=spec, mi=mi, optimizer=self.optimizer_kind, lr=self.lr, init=self.init_control,
+        ngf = self.criterions[0].settings(self.weights[0]) if self.ngf_alone() else None      # __init__ admits MILoss or NGFLoss alone beside the fused criteria
+        mi = self.criterions[0].settings(self.weights[0]) if spec is None and ngf is None else None
+        solver = BSplineSolver(moving, target, self.spacing, loss=spec, mi=mi, ngf=ngf, optimizer=self.optimizer_kind, lr=self.lr, init=self.init_control,
                                base=self.base_flow, capacity=max(1, self.max_epochs), stop_crit=self.stop_crit, keep_last=True,
                                bending_weight=self.bending_weight, squarings=self.squarings if self.diffeomorphic else None, mask=mask, initial=initial,
                                overlap=overlap, moving_mask=moving_mask, folding_weight=self.folding_weight, folding_threshold=self.folding_threshold)
